@@ -19,9 +19,14 @@ ranks itself (one child process per GPU, dist.launch_local) and forwards
 rank 0's JSON line; under torchrun / torch.distributed.run each process is
 one rank.
 
-Rank 0 prints ONE JSON line.  It carries `roofline` for the dominant kernel
-(algorithmic bytes from HIP events around each kernel on the launch stream)
-and `cpu_baseline` (the NumPy/SciPy oracle on a bounded sample, 1 core).
+Rank 0 prints ONE JSON line.  It carries `ms_per_step` (the timed region over
+--steps) and `roofline` for the dominant kernel (algorithmic bytes from HIP
+events around each kernel on the launch stream).  A plain run sets up, warms
+up, times its steps and prints that line; --dump-outputs DIR also writes the
+last timed step's result records (DIR/results.npy; the inputs are seeded, so
+two builds can be compared record for record).  With --full the line also
+carries `cpu_baseline` (the NumPy/SciPy oracle on a bounded sample, 1 core
+and all-core) and `parity` (the device fits of that sample against it).
 """
 import argparse
 import hashlib
@@ -111,7 +116,8 @@ def parse():
                     "the Newton trust region (default) or scipy trust-ncg's "
                     "own path (PPF_OPT_SCIPY_TR)")
     ap.add_argument("--cpu-sample", type=int, default=48,
-                    help="sub-integrations for the CPU baseline (0: skip)")
+                    help="sub-integrations for the CPU baseline of --full "
+                    "(0: skip)")
     ap.add_argument("--cpu-workers", type=int, default=16,
                     help="processes for the all-core CPU aggregate (the GPU "
                     "box's CPU share is 16)")
@@ -120,7 +126,44 @@ def parse():
                     "only to rehearse several ranks on one GPU)")
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles",
                                                   "pmc_summary.json"))
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baseline "
+                    "(the oracle on --cpu-sample sub-ints, one core and "
+                    "--cpu-workers processes) and the parity check of the "
+                    "device fits against it; off: the timed steps and the "
+                    "result line only (cpu_baseline null, no parity)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as "
+                    "DIR/<name>.npy (float64): results.npy, the gathered "
+                    "result records [sub-int, _lib.RESULT_FIELDS]; --fit "
+                    "align: template.npy, the iteration's portrait, and "
+                    "results.npy, its fits' records (at most 64 MB in all: a "
+                    "fixed seeded sample of the rows beyond that)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.fit in ("gettoas", "single"):
+        ap.error("--dump-outputs: not available with --fit %s" % args.fit)
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy (float64).  The arrays
+    share the 64 MB limit in proportion to their sizes; one above its share
+    keeps a sorted sample of its rows drawn with a fixed seed, so two builds
+    write the same rows."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64)
+              for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            keep = int(len(a) * DUMP_MAX_BYTES // total)
+            rows = np.random.default_rng(20250217).choice(
+                len(a), keep, replace=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def _noop(_):
@@ -483,7 +526,13 @@ def bench_align(args):
                            fit="align", parallelism="dp%d" % world, launcher=LAUNCHER),
                roofline=roof, solver_fp64=solver, kernels=kernels, cpu_baseline=None,
                template_peak=float(torch.as_tensor(m).abs().max()), **fitstats)
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if rank == 0 and args.dump_outputs:
+        # (at N > 1 the template is the all-reduced one, the records rank 0's)
+        arrays = dict(template=torch.as_tensor(m).cpu().numpy())
+        if lr is not None:
+            arrays["results"] = lr
+        dump_outputs(args.dump_outputs, arrays)
+    if rank == 0 and world == 1 and args.full and args.cpu_sample > 0:
         out["cpu_baseline"], out["parity"] = _align_cpu_baseline(
             b, noise, model0, min(args.cpu_sample, count), step, R, dev)
     if rank == 0:
@@ -794,6 +843,12 @@ def bench_single(args):
                 t0 = time.perf_counter()
                 gpu()
                 ts.append(time.perf_counter() - t0)
+            call = calls["%s_%dx%d" % (name, nchan, nbin)] = dict(
+                gpu_ms_median=round(1e3 * float(np.median(ts)), 3),
+                gpu_ms_min=round(1e3 * float(np.min(ts)), 3),
+                cpu_oracle_ms_median=None, speedup=None)
+            if not args.full:
+                continue
             with threadpool_limits(1):
                 cpu()
                 tc = []
@@ -801,9 +856,7 @@ def bench_single(args):
                     t0 = time.perf_counter()
                     cpu()
                     tc.append(time.perf_counter() - t0)
-            calls["%s_%dx%d" % (name, nchan, nbin)] = dict(
-                gpu_ms_median=round(1e3 * float(np.median(ts)), 3),
-                gpu_ms_min=round(1e3 * float(np.min(ts)), 3),
+            call.update(
                 cpu_oracle_ms_median=round(1e3 * float(np.median(tc)), 3),
                 speedup=round(float(np.median(tc) / np.median(ts)), 2))
     key = "fit_portrait_full_64x512"
@@ -823,7 +876,7 @@ def bench_single(args):
                                  unit="ms", cores=1, kind="port",
                                  sample="the oracle's fit_portrait_full of "
                                         "the same 64x512 sub-int, median of "
-                                        "3 calls"))
+                                        "3 calls") if args.full else None)
     print(json.dumps(out), flush=True)
 
 
@@ -979,6 +1032,8 @@ def main():
     sgot = lib.ppf_solver_ms_history(ctx, ncalls, shist.ctypes.data)
     solv_ms = shist[:max(sgot, 0)].sum(axis=0)
     res_np = last.cpu().numpy()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(results=res_np))
     I = _lib.RESULT_INDEX
     nfev = res_np[:, I["nfeval"]]
     npass = res_np[:, I["npass"]]
@@ -1242,7 +1297,7 @@ def main():
             ((pr[:, 3] - truth) / pe[:, 3]) ** 2))), 3)
         out["alpha_pull_rms"] = round(float(np.sqrt(np.mean(
             ((pr[:, 4] - synth.GMODEL_ALPHA) / pe[:, 4]) ** 2))), 3)
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_sample > 0:
         # scattering fits take ~10x longer on the CPU: a 12x smaller sample
         # (C5's 16384-channel fits ~30 s each: 48x smaller); the default
         # --cpu-sample 48 gives C3 4 and C5 1 one-core sub-ints, 192 gives

@@ -17,6 +17,7 @@ if [ "$mode" = tests ] && [ "${PART:-ab}" != b ]; then
 fi
 run() {
   name=$1; lim=$2; shift 2
+  set -- --full "$@"      # every line with its CPU baseline and parity sample
   timeout -k 10 $lim python bench.py "$@" > gpurun_out/bench_${name}_$tag.log 2>&1
   rc=$?
   echo "$name rc=$rc $(python tools/show.py gpurun_out/bench_${name}_$tag.log | head -1)" >> $st

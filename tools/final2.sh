@@ -7,9 +7,9 @@ rc=$?; echo "tests rc=$rc $(tail -1 $out/pytest.log)" >> $st
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1
 rc=$?; echo "smoke rc=$rc $(tail -1 $out/smoke.txt)" >> $st
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py > $out/bench_c2.log 2>&1
+timeout -k 10 300 python bench.py --full > $out/bench_c2.log 2>&1
 rc=$?; echo "c2 rc=$rc $(python tools/show.py $out/bench_c2.log 2>/dev/null | head -1)" >> $st
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --fit align --nsub 1000 --nchan 256 --nbin 1024 --steps 50 --warmup 5 > $out/bench_c4.log 2>&1
+timeout -k 10 300 python bench.py --full --fit align --nsub 1000 --nchan 256 --nbin 1024 --steps 50 --warmup 5 > $out/bench_c4.log 2>&1
 rc=$?; echo "c4 rc=$rc $(python tools/show.py $out/bench_c4.log 2>/dev/null | head -1)" >> $st
 echo end >> $st

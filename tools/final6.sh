@@ -8,7 +8,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smok
 rc=$?; echo "smoke rc=$rc $(tail -1 $out/smoke.txt)" >> $st
 [ $rc -eq 0 ] || exit $rc
 run() {   # name, args
-  timeout -k 10 400 python bench.py $2 > $out/bench_$1.log 2>&1
+  timeout -k 10 400 python bench.py --full $2 > $out/bench_$1.log 2>&1
   rc=$?; echo "$1 rc=$rc $(python tools/show.py $out/bench_$1.log 2>/dev/null | head -1)" >> $st
   return $rc
 }
