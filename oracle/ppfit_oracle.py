@@ -460,7 +460,7 @@ def fit_portrait_full(data_port, model_port, init_params, P, freqs,
                 covariance_matrix=cov_full, chi2=chi2, red_chi2=chi2 / dof,
                 snr=snr, channel_snrs=channel_snrs, duration=duration,
                 nfeval=res.nfev, return_code=res.status, Sd=Sd,
-                fun=res.fun, x_fit=res.x)
+                fun=res.fun, x_fit=res.x, dof=dof)
 
 
 def get_scales_full(params, Dft, Mft, errs_FT, P, freqs, nu_DM, nu_GM,
@@ -673,7 +673,9 @@ def get_toas_archive(subints, models, freqs, weights, SNRs, Ps, DM_stored,
     [rot] at nu_fit scatters the mean model profile of the phase guess, and
     with log10_tau a zero tau_guess becomes log10(1 / nbin); scat_guess =
     (tau [s], its reference frequency [MHz], alpha) overrides them per
-    sub-int as pptoas.py:469-472 does."""
+    sub-int as pptoas.py:469-472 does.  out["fits"][isub] keeps the whole
+    fit_portrait_full result of a sub-int (its arrays over the channels of
+    nonzero weight), for tests that compare more than the TOA fields."""
     nsub, nchan, nbin = subints.shape
     if ok_isubs is None:
         ok_isubs = np.arange(nsub)
@@ -686,6 +688,7 @@ def get_toas_archive(subints, models, freqs, weights, SNRs, Ps, DM_stored,
     out["scales"] = np.zeros((nsub, nchan))
     nfit = int(np.sum(fit_flags))
     out["covariances"] = np.zeros((nsub, nfit, nfit))
+    out["fits"] = [None] * nsub
     for isub in ok_isubs:
         ok = np.where(weights[isub] != 0.0)[0]
         freqsx = freqs[isub, ok]
@@ -736,6 +739,7 @@ def get_toas_archive(subints, models, freqs, weights, SNRs, Ps, DM_stored,
         out["nu_refs"][isub] = [r["nu_DM"], r["nu_GM"], r["nu_tau"]]
         out["nu_fits"][isub] = [nu_fit] * 3
         out["scales"][isub, ok] = r["scales"]
+        out["fits"][isub] = r
         cm = r["covariance_matrix"]
         if cm.shape == out["covariances"][isub].shape:
             out["covariances"][isub] = cm

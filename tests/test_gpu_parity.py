@@ -672,16 +672,20 @@ def test_chime_shape_16384ch_scattering_fit_properties():
 
 
 # ------------------------------------------------------------- ppalign (C4) --
-@pytest.mark.parametrize("nbin", [512, 511])
-def test_align_accum_matches_numpy(nbin):
+@pytest.mark.parametrize("nbin,nchan", [(512, 12), (511, 12), (512, 37),
+                                        (511, 37), (512, 100), (511, 100)],
+                         ids=["512", "511", "512-37ch", "511-37ch",
+                              "512-100ch", "511-100ch"])
+def test_align_accum_matches_numpy(nbin, nchan):
     """ppf_align_accum: sum_s w rotate(x_s, phi_s) per channel (frequency-
     domain accumulation) equals the time-domain rotate-then-sum of the
-    oracle to rounding (odd nbin: the unpaired harmonic partials)."""
+    oracle to rounding (odd nbin: the unpaired harmonic partials; 37 and
+    100 channels: a partial last channel tile)."""
     import torch
     import oracle as O
     from pulseportraiture_amd import engine
     rng = np.random.default_rng(5)
-    nsub, nchan = 37, 12
+    nsub = 37
     x = rng.normal(size=(nsub, nchan, nbin)).astype(np.float32)
     ph = rng.uniform(-0.5, 0.5, size=(nsub, nchan))
     w = rng.uniform(0.1, 2.0, size=(nsub, nchan))

@@ -1,0 +1,88 @@
+"""Ragged channel counts and per-sub-int masks on every fit kernel family,
+against the f64 oracle on host-built inputs (tests/ragged.py; the host
+side of the same cases: tests/test_ragged_inputs.py).
+
+Each case is ONE engine.fit_batch call on four sub-integrations that differ
+in their channel masks (none; a random 20 % plus both band edges; whole
+64-channel groups, those of the k_pass warm start among them; one channel
+in eight), compared sub-int by sub-int with the oracle's fit of the kept
+channels.  Bars: the project's (goldens.SIGMA_TOL, goldens.RCHI2_RTOL) and
+the per-channel forms of test_gpu_fullshape.py."""
+import numpy as np
+import pytest
+
+import goldens as G
+import ragged as R
+
+pytestmark = pytest.mark.gpu
+
+SIG, RCHI2 = G.SIGMA_TOL, G.RCHI2_RTOL
+
+
+def _compare(c, r, j, i):
+    """Row j of the device output r against the oracle's fit of sub-int i."""
+    from pulseportraiture_amd import _lib
+    I = _lib.RESULT_INDEX
+    b = R.inputs(c)
+    o = R.oracle_fit(c, i)
+    keep = b["keep"][i]
+    tag = (c["name"], i)
+    assert o["return_code"] == 2, tag
+    res = r["results"][j]
+    assert (int(res[I["status"]]) & 0xff) in (1, 2), (tag, res[I["status"]])
+    assert int(res[I["status"]]) >> 8 == 0, (tag, res[I["status"]])
+    assert res[I["nchanx"]] == keep.sum(), tag
+    assert res[I["dof"]] == o["dof"], tag
+    got = dict(params=res[I["params"]], nu_DM=res[I["nu_out"]][0],
+               nu_GM=res[I["nu_out"]][1], nu_tau=res[I["nu_out"]][2])
+    dev = G.param_deviation_sigma(got, o, b["P"], b["scat"])
+    rel = abs(res[I["red_chi2"]] / o["red_chi2"] - 1)
+    print("RAGGED %s sub %d kept %d: dev %.2e sigma, chi2_red rel %.1e" %
+          (c["name"], i, keep.sum(), dev.max(), rel))
+    assert dev.max() < SIG, (tag, dev)
+    assert rel < RCHI2, (tag, rel)
+    np.testing.assert_allclose(res[I["param_errs"]], o["param_errs"],
+                               rtol=1e-4, err_msg=str(tag))
+    np.testing.assert_allclose(res[I["snr"]], o["snr"], rtol=1e-6,
+                               err_msg=str(tag))
+    np.testing.assert_allclose(r["scale_errs"][j][keep], o["scale_errs"],
+                               rtol=1e-4, err_msg=str(tag))
+    atol = 1e-3 * np.abs(o["scale_errs"]).min()
+    for key in ("scales", "channel_snrs"):
+        np.testing.assert_allclose(r[key][j][keep], o[key], rtol=1e-4,
+                                   atol=atol, err_msg="%s %s" % (key, tag))
+    for key in ("scales", "scale_errs", "channel_snrs"):
+        assert np.all(r[key][j][~keep] == 0.0), (key, tag)
+    return dev.max(), rel
+
+
+@pytest.mark.parametrize("name", R.CASE_NAMES)
+def test_ragged_batch_matches_oracle(name):
+    """A partial last channel tile and masks that empty whole tiles, in one
+    batch: k_xspec_w2 + k_moments with the guess in the spectrum pass (f32
+    and f64 rows; 250 channels: 8 blocks, swizzled, the last of 26) and
+    through k_dsum_w, the fused k_xmom_g, forced moments from X, k_xspec_w +
+    k_pass, the k_pass warm start at strides 2 and 4 with a one-channel
+    last group, the mixed-radix and odd-nbin wave passes (unpaired rows),
+    the block-FFT k_xspec (fewer than 32 channels; 4096 and 128 bins) and
+    rows past the LDS transforms."""
+    c = R.case(name)
+    r = R.device_fit(c)
+    for i in range(R.inputs(c)["nsub"]):
+        _compare(c, r, i, i)
+
+
+@pytest.mark.parametrize("name", ["w2_guess-250x2048-pd-cut-f32",
+                                  "warm-257x256-pdta-cut-f32"])
+def test_ragged_single_equals_batch(name):
+    """Each sub-int fitted alone is bitwise the batch's (as
+    test_batch_equals_single_and_is_deterministic at 64 channels), with a
+    ragged last block and differing masks."""
+    c = R.case(name)
+    full = R.device_fit(c)
+    for i in range(R.inputs(c)["nsub"]):
+        one = R.device_fit(c, [i])
+        for k in ("results", "scales", "scale_errs", "channel_snrs",
+                  "covariance"):
+            np.testing.assert_array_equal(one[k][0], full[k][i],
+                                          err_msg="%s sub %d" % (k, i))

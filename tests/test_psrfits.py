@@ -144,11 +144,15 @@ def _host_baseline(u, wts, frac=0.15):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("npol,elem", [(2, "I"), (1, "I")])
-def test_device_unpack_matches_restatement(tmp_path, npol, elem):
+@pytest.mark.parametrize("npol,elem,nchan", [(2, "I", 32), (1, "I", 32),
+                                             (2, "I", 37), (1, "I", 37)],
+                         ids=["2-I", "1-I", "2-I-37ch", "1-I-37ch"])
+def test_device_unpack_matches_restatement(tmp_path, npol, elem, nchan):
+    """37 channels: ppf_unpack_psrfits_batch works in blocks of 16 channels;
+    the last block holds 5."""
     import torch
     from pulseportraiture_amd import engine
-    fn, q, scl, offs, fr, wts = _archive(tmp_path, npol=npol)
+    fn, q, scl, offs, fr, wts = _archive(tmp_path, npol=npol, nchan=nchan)
     f = PF.PSRFITS(fn)
     raw, dt = f.data_bytes()
     s, o = f.scales_offsets()
@@ -256,6 +260,16 @@ def _baseline_removed(R, wts, frac=0.15):
 
 @pytest.mark.gpu
 def test_load_data_dedisperse_tscrunch(tmp_path):
+    _check_dedisperse_tscrunch(tmp_path, 32)
+
+
+@pytest.mark.gpu
+def test_load_data_dedisperse_tscrunch_37_channels(tmp_path):
+    """A last 16-channel block of 5 channels."""
+    _check_dedisperse_tscrunch(tmp_path, 37)
+
+
+def _check_dedisperse_tscrunch(tmp_path, nchan):
     """load_data(dedisperse, tscrunch) on the device against the DataBunch
     rows transformed on the host side of the API: rotate_data (pplib.py:
     2427-2515) by the stored DM to OBSFREQ per sub-int period, the baseline
@@ -263,9 +277,10 @@ def test_load_data_dedisperse_tscrunch(tmp_path):
     DAT_WTS-weighted mean over sub-ints (PSRCHIVE's weighted Profile
     average; PSRCHIVE parity itself unpinned)."""
     from pulseportraiture_amd import pplib
-    fn = _archive(tmp_path, wvals=True)[0]
+    fn = _archive(tmp_path, wvals=True, nchan=nchan)[0]
     f = PF.PSRFITS(fn)
     wts = f.weights()                # DAT_WTS as stored (float32 values)
+    assert wts.shape[1] == nchan
     f.close()
     base = PF.load_data(fn, pscrunch=True, rm_baseline=False, quiet=True)
     U = np.asarray(base.subints)[:, 0]
