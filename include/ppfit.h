@@ -86,10 +86,18 @@ enum ppf_option {
     PPF_OPT_NO_X = 2,        /* the caller has checked that no sub-int
                                 streams the cross spectrum (no scattering
                                 flag, zero initial tau): on the fused
-                                phase+DM path no X slot is reserved and the
-                                cross-spectrum pass is not launched (a
-                                sub-int that would need X ends with
-                                PPF_ST_NOSPACE) */
+                                phase+DM path no X slot is reserved, the
+                                cross-spectrum pass is not launched and the
+                                host does not read back which kinds of fit
+                                the batch holds (a sub-int that would need X
+                                ends with PPF_ST_NOSPACE).  Everywhere else
+                                (block-FFT and long rows, moments from X:
+                                PPF_OPT_MOM_X or its default) the option
+                                changes no result: every sub-int holds an X
+                                slot and a scattering sub-int is fitted as
+                                without it; the host only learns of such a
+                                sub-int with the first read-back of its
+                                iteration loop instead of before it */
     PPF_OPT_SCIPY_TR = 4,    /* the fits follow scipy's trust-ncg path
                                 step by step (pptoaslib.py:1055-1060:
                                 radius 1 in raw parameter units,

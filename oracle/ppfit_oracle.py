@@ -367,8 +367,11 @@ def fit_portrait_full(data_port, model_port, init_params, P, freqs,
                       nu_fits=(None, None, None), nu_outs=(None, None, None),
                       errs=None, fit_flags=(1, 1, 1, 1, 1), log10_tau=True,
                       option=0, is_toa=True, messages=None,
-                      method="trust-ncg", bounds=None, x_fit=None):
+                      method="trust-ncg", bounds=None, x_fit=None,
+                      maxiter=None):
     """pptoaslib.py:974-1144 (Schur covariance instead of the dense cube).
+    maxiter (test infrastructure): trust-ncg's iteration cap; None leaves
+    scipy's own (200 per parameter), as the reference does.
     method 'TNC' minimises with scipy TNC under `bounds` exactly as
     pptoaslib.py:1041-1060 does (minfev = dof - Sd, xtol 1e-10; maxiter is
     not a TNC option and scipy ignores it); x_fit (test infrastructure)
@@ -418,7 +421,9 @@ def fit_portrait_full(data_port, model_port, init_params, P, freqs,
         res = opt.minimize(lambda x: objective(terms(x)), np.asarray(
             init_params, dtype=float), method="trust-ncg",
             jac=lambda x: gradient(terms(x), flags),
-            hess=lambda x: hessian(terms(x), flags), options={"gtol": -1})
+            hess=lambda x: hessian(terms(x), flags),
+            options={"gtol": -1} if maxiter is None else
+            {"gtol": -1, "maxiter": int(maxiter)})
     duration = time.time() - t0
     phi_fit, DM_fit, GM_fit, tau_fit, alpha_fit = res.x
     nu_out = list(nu_outs)

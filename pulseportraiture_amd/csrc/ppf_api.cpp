@@ -796,14 +796,26 @@ int ppf_fit_batch(ppf_ctx *ctx, const ppf_fit_desc *d, void *stream) {
     if (sa.moments) sa.any_plain = 0;      // plain fits go through the moments
     if ((e = ppf::launch_tr_init(sa, st)) != hipSuccess) return hip_fail(ctx, e, "k_tr_init");
     // how many fits iterate on the moments and how many on streaming passes:
-    // the iteration loop launches only the kernels some fit needs.  With
-    // PPF_OPT_NO_X the caller has ruled out every streaming fit (no X slot
-    // exists), so the answer is known without the read-back and its stream
-    // synchronisation (round 6: one host round trip less per call, a few
-    // percent of a ppalign iteration); the moment kernels of a batch with
-    // nothing left to fit exit at once
+    // the iteration loop launches only the kernels some fit needs.  Where
+    // PPF_OPT_NO_X took effect (fit_layout: the fused path without moments
+    // from X, xcap == 0) no X slot exists, a sub-int that would stream has
+    // ended with PPF_ST_NOSPACE in k_tr_init and every other fit is a
+    // moment fit, so the answer is known without the read-back and its
+    // stream synchronisation (round 6: one host round trip less per call, a
+    // few percent of a ppalign iteration); the moment kernels of a batch
+    // with nothing left to fit exit at once.  Everywhere else (block-FFT and
+    // long rows, moments from X) the option reserves nothing less and every
+    // streaming sub-int holds a valid slot, so the counts decide.  Without
+    // the option they are read here.  With it (the C2 pipeline: moments from
+    // X at 2048 bins) the caller expects no streaming fit, and the counts
+    // ride along with the first read-back of the iteration loop instead
+    // (kinds_late): no round trip of their own, and a streaming sub-int that
+    // is there after all gets its k_pass from the second group on -- a
+    // sub-int's iterations do not depend on the round they start in
+    const bool no_stream = sa.moments && L.fused && L.xcap == 0;
+    bool kinds_late = !no_stream && sa.moments && (d->options & PPF_OPT_NO_X);
     bool any_mom = true, any_pass = false;
-    if (!((d->options & PPF_OPT_NO_X) && sa.moments)) {
+    if (!no_stream && !kinds_late) {
         if ((rc = read_back(ctx, ctx->host_active + 1, sa.kinds, 2, st, d->options & PPF_OPT_SPIN_WAIT))) return rc;
         any_mom = ctx->host_active[1] != 0;
         any_pass = ctx->host_active[2] != 0;
@@ -893,7 +905,19 @@ int ppf_fit_batch(ppf_ctx *ctx, const ppf_fit_desc *d, void *stream) {
             }
         }
         iter += group;
+        // (the same stream, in order: the counts have landed when the
+        // read-back behind them has)
+        if (kinds_late && (e = hipMemcpyAsync(ctx->host_active + 1, sa.kinds, 2 * sizeof(unsigned),
+                                              hipMemcpyDeviceToHost, st)) != hipSuccess)
+            return hip_fail(ctx, e, "hipMemcpyAsync");
         if ((rc = read_back(ctx, ctx->host_active, sa.active, 1, st, d->options & PPF_OPT_SPIN_WAIT))) return rc;
+        if (kinds_late) {
+            kinds_late = false;
+            if (ctx->host_active[2] != 0) {
+                any_pass = true;      // fits still in PH_INIT: not counted in active yet
+                continue;
+            }
+        }
         if (*ctx->host_active == 0 || iter > maxiter + 2) break;
     }
     {

@@ -699,11 +699,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void k
     // per-lane channel tables: lane l holds channel cbase + l
     double ch_d0 = 0.0, ch_d1 = 0.0, ch_e = 0.0;
     int ch_use = 0;
-    // the harmonic cutoff of the block's channels, also per lane: a global
-    // load of KC[n] inside the round would wait (vmcnt is in order) for the
-    // next round's prefetch
+    // the harmonic cutoff of the block's channels (of the wave's own model),
+    // also per lane: a global load of KC[n] inside the round would wait
+    // (vmcnt is in order) for the next round's prefetch
     int ch_kc = NH;
-    if (SH && a.KC && lane < cend - cbase) ch_kc = a.KC[cbase + lane];
+    if (a.KC && lane < cend - cbase) ch_kc = a.KC[(int64_t)mi * a.nchan + cbase + lane];
     if (act && lane < cend - cbase) {
         const int64_t row = (int64_t)sv * a.nchan + cbase + lane;
         ch_d0 = a.dphi[row * 2];
@@ -715,7 +715,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void k
     const int arow = lane & 15, kk = lane >> 4, bj = lane & 15;
     const double *abase = reinterpret_cast<const double *>(lds + (arow >> 1) * SLW) + (arow & 1);
     constexpr double ih = 2.0 / (double)N;
-    const int k0 = wave * KPW;
 
     vd2 mp[MPT];
     double mpw = 0.0;
@@ -827,7 +826,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void k
             // in-flight row prefetch
             int lpp = lane;
             asm volatile("" : "+v"(lpp));
-            auto pair = [&](const double2 *Mr, int i, double2 &w) {
+            // the row's cutoff rounded up to a block of four folded harmonics
+            const int kz = (__builtin_amdgcn_readlane(ch_kc, n - cbase) + 3) & ~3;
+            (void)kz;
+            auto pair =[&](const double2 *Mr, int i, double2 &w) {
                     const int klo = lpp + 64 * i, khi = N - klo;
                     double2 Dlo, Dhi;
                     rfft_pair<LOG2N>(buf, klo, w, Dlo, Dhi);
@@ -840,9 +842,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void k
                     const double2 Ylo = klo == 0 ? cmk(0.0, 0.0) : cmulc(Dlo, Mr[klo]);
                     const double2 Yhi = cmulc(Dhi, Mr[khi]);
                     const double uk = (double)(klo - N / 2) * ih;
-                    buf[wfft::pad<LOG2N>(klo)] = cadd(Ylo, Yhi);
-                    buf[klo == 0 ? wfft::pad<LOG2N>(N / 2) : wfft::pad<LOG2N>(khi)] =
-                        cscale(csub(Ylo, Yhi), uk);
+                    double2 ys = cadd(Ylo, Yhi), yd = cscale(csub(Ylo, Yhi), uk);
+                    if constexpr (!SH) {
+                        // past the row's own cutoff (see the moment loop)
+                        if (klo >= kz) ys = yd = cmk(0.0, 0.0);
+                    }
+                    buf[wfft::pad<LOG2N>(klo)] = ys;
+                    buf[klo == 0 ? wfft::pad<LOG2N>(N / 2) : wfft::pad<LOG2N>(khi)] = yd;
             };
             const double2 *Mr = SH ? mrow : Mwave + (int64_t)n * NH;
             double2 w = w_seed;
@@ -884,21 +890,24 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void k
 
         f64x4 d0 = {0.0, 0.0, 0.0, 0.0}, d1 = d0;
         // folded pairs (k, N - k) with k >= KC_n hold only harmonics whose
-        // model amplitude is below 1e-14 of its peak (k_model_cut): the
-        // needed range [0, KC_n) is spread over the eight waves instead
-        int kpw = KPW, kw0 = k0;
-        if constexpr (SH) {
-            const int kn = __builtin_amdgcn_readlane(ch_kc, n - cbase);
-            if (kn < N / 2) {
-                kpw = min(KPW, ((kn + 4 * XW - 1) / (4 * XW)) * 4);
-                kw0 = wave * kpw;
-            }
-        }
+        // model amplitude is below 1e-14 of its peak (k_model_cut) and are
+        // left out, in whole blocks of four.  The blocks are dealt to the
+        // eight waves in turn (block b to wave b mod 8), so a shorter range
+        // stays spread over all of them AND the summation order does not
+        // depend on the cutoff: with one shared model the loop stops at
+        // the channel's cutoff; with a model per sub-int it runs over the
+        // whole range and each wave has zeroed its own row past its own
+        // cutoff (pair(), kz), which adds exact zeros.  A sub-int's moments
+        // are therefore bitwise the same whether its model comes alone or
+        // among several.
+        int nb = N / 8;
+        if constexpr (SH) nb = min(nb, (__builtin_amdgcn_readlane(ch_kc, n - cbase) + 3) >> 2);
 #ifndef G_NOMFMA
 #pragma unroll 4
         for (int t = 0; t < KPW / 4; ++t) {
-            if (t >= (kpw >> 2)) break;                       // wave-uniform
-            const int k = kw0 + 4 * t + kk;
+            const int b = XW * t + wave;
+            if (b >= nb) break;                               // wave-uniform
+            const int k = 4 * b + kk;
             const int se = wfft::pad<LOG2N>(k);
             const int so = k == 0 ? wfft::pad<LOG2N>(N / 2) : wfft::pad<LOG2N>(N - k);
             // B[k][j] = v_k^j, v = u_k^2 (same arithmetic as k_btab)

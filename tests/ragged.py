@@ -249,6 +249,44 @@ def oracle_refit(c, i, first):
         log10_tau=b["scat"])
 
 
+def compare_row(label, tag, r, j, o, keep, P, log10_tau):
+    """Row j of the device tables r against the oracle fit o of the kept
+    channels, at the project's bars (goldens.SIGMA_TOL, goldens.RCHI2_RTOL,
+    errors 1e-4, S/N 1e-6, per-channel scales and S/N, zeros where masked);
+    shared by tests/test_gpu_ragged.py and tests/test_gpu_mixed.py.  Prints
+    one line (label ...) and returns (max deviation in sigma, chi2_red
+    rel)."""
+    from pulseportraiture_amd import _lib
+    I = _lib.RESULT_INDEX
+    assert o["return_code"] == 2, tag
+    res = r["results"][j]
+    assert (int(res[I["status"]]) & 0xff) in (1, 2), (tag, res[I["status"]])
+    assert int(res[I["status"]]) >> 8 == 0, (tag, res[I["status"]])
+    assert res[I["nchanx"]] == keep.sum(), tag
+    assert res[I["dof"]] == o["dof"], tag
+    got = dict(params=res[I["params"]], nu_DM=res[I["nu_out"]][0],
+               nu_GM=res[I["nu_out"]][1], nu_tau=res[I["nu_out"]][2])
+    dev = G.param_deviation_sigma(got, o, P, log10_tau)
+    rel = abs(res[I["red_chi2"]] / o["red_chi2"] - 1)
+    print("%s kept %d: dev %.2e sigma, chi2_red rel %.1e" %
+          (label, keep.sum(), dev.max(), rel))
+    assert dev.max() < G.SIGMA_TOL, (tag, dev)
+    assert rel < G.RCHI2_RTOL, (tag, rel)
+    np.testing.assert_allclose(res[I["param_errs"]], o["param_errs"],
+                               rtol=1e-4, err_msg=str(tag))
+    np.testing.assert_allclose(res[I["snr"]], o["snr"], rtol=1e-6,
+                               err_msg=str(tag))
+    np.testing.assert_allclose(r["scale_errs"][j][keep], o["scale_errs"],
+                               rtol=1e-4, err_msg=str(tag))
+    atol = 1e-3 * np.abs(o["scale_errs"]).min()
+    for key in ("scales", "channel_snrs"):
+        np.testing.assert_allclose(r[key][j][keep], o[key], rtol=1e-4,
+                                   atol=atol, err_msg="%s %s" % (key, tag))
+    for key in ("scales", "scale_errs", "channel_snrs"):
+        assert np.all(r[key][j][~keep] == 0.0), (key, tag)
+    return dev.max(), rel
+
+
 def device_fit(c, subs=None):
     """engine.fit_batch on the case's batch (or on the sub-ints subs of it)
     -> dict of numpy arrays."""

@@ -21,39 +21,10 @@ SIG, RCHI2 = G.SIGMA_TOL, G.RCHI2_RTOL
 
 def _compare(c, r, j, i):
     """Row j of the device output r against the oracle's fit of sub-int i."""
-    from pulseportraiture_amd import _lib
-    I = _lib.RESULT_INDEX
     b = R.inputs(c)
-    o = R.oracle_fit(c, i)
-    keep = b["keep"][i]
-    tag = (c["name"], i)
-    assert o["return_code"] == 2, tag
-    res = r["results"][j]
-    assert (int(res[I["status"]]) & 0xff) in (1, 2), (tag, res[I["status"]])
-    assert int(res[I["status"]]) >> 8 == 0, (tag, res[I["status"]])
-    assert res[I["nchanx"]] == keep.sum(), tag
-    assert res[I["dof"]] == o["dof"], tag
-    got = dict(params=res[I["params"]], nu_DM=res[I["nu_out"]][0],
-               nu_GM=res[I["nu_out"]][1], nu_tau=res[I["nu_out"]][2])
-    dev = G.param_deviation_sigma(got, o, b["P"], b["scat"])
-    rel = abs(res[I["red_chi2"]] / o["red_chi2"] - 1)
-    print("RAGGED %s sub %d kept %d: dev %.2e sigma, chi2_red rel %.1e" %
-          (c["name"], i, keep.sum(), dev.max(), rel))
-    assert dev.max() < SIG, (tag, dev)
-    assert rel < RCHI2, (tag, rel)
-    np.testing.assert_allclose(res[I["param_errs"]], o["param_errs"],
-                               rtol=1e-4, err_msg=str(tag))
-    np.testing.assert_allclose(res[I["snr"]], o["snr"], rtol=1e-6,
-                               err_msg=str(tag))
-    np.testing.assert_allclose(r["scale_errs"][j][keep], o["scale_errs"],
-                               rtol=1e-4, err_msg=str(tag))
-    atol = 1e-3 * np.abs(o["scale_errs"]).min()
-    for key in ("scales", "channel_snrs"):
-        np.testing.assert_allclose(r[key][j][keep], o[key], rtol=1e-4,
-                                   atol=atol, err_msg="%s %s" % (key, tag))
-    for key in ("scales", "scale_errs", "channel_snrs"):
-        assert np.all(r[key][j][~keep] == 0.0), (key, tag)
-    return dev.max(), rel
+    return R.compare_row("RAGGED %s sub %d" % (c["name"], i), (c["name"], i),
+                         r, j, R.oracle_fit(c, i), b["keep"][i], b["P"],
+                         b["scat"])
 
 
 @pytest.mark.parametrize("name", R.CASE_NAMES)
