@@ -124,7 +124,12 @@ enum ppf_option {
                                 overridden: nsub * nchan * (nbin/2 + 1) * 16
                                 bytes of workspace, 8.4 MB per 512 x 2048
                                 sub-int; ppf_fit_workspace_bytes includes
-                                it).  Default (neither this nor
+                                it.  At nbin = 2048 the slots of the fits
+                                without scattering are tiled, 8 consecutive
+                                harmonics of a channel per 128-byte line, and
+                                every slot holds the harmonics rounded up to
+                                whole tiles: nsub * nchan * 1032 * 16 bytes).
+                                Default (neither this nor
                                 PPF_OPT_FUSED_MOM) where the GetTOAs guess
                                 rides along in the spectrum pass: guess != 0
                                 and nbin = 2048 */

@@ -216,7 +216,7 @@ int cz_tables(ppf_ctx *ctx, const ppf::CzPlan &c, hipStream_t st, const double2 
 #endif
 struct FitLayout {
     size_t M, X, chan, stats, x0, gP, gw, nuref, Msum, gpart, gwx, gflag, state, partials, active, mom, dphi,
-        mres, hcen, Mpow, MP, KC, needx, xslot, rclist, Bt, total;
+        mres, hcen, Mpow, MP, KC, needx, xslot, xtile, rclist, Bt, total;
     // rows past the LDS transforms (round 6): their rFFTs (data spectra,
     // long-transform chirp tables and work rows, rows per chunk)
     int lng;
@@ -226,6 +226,8 @@ struct FitLayout {
     int fused;    // phase+DM fits on the fused moment pass (k_xmom_g), X only for scattering fits
     int momx;     // wave shapes, PPF_OPT_MOM_X: every fit's moments from X (k_xspec_w + k_moments)
     int xcap;     // X slots
+    int tiled;    // momx at 2048 bins: the moment-mode sub-ints' slots are tiled (ppf::xspec_tiled)
+    int xnh;      // harmonics per channel of an X slot
 };
 
 // 16 moments about each wave's band centre where the moments come from a
@@ -285,7 +287,11 @@ FitLayout fit_layout(const ppf_fit_desc *d) {
     L.nblkd = (d->nchan + L.cbd - 1) / L.cbd;
     size_t o = 0;
     L.M = o;     o += align256(sizeof(double2) * (size_t)(d->nmodel > 0 ? d->nmodel : 1) * nchan * nharm);
-    L.X = o;     o += align256(sizeof(double2) * (size_t)L.xcap * nchan * nharm);
+    // tiled slots hold whole tiles of 8 harmonics per channel (1032 at 2048
+    // bins); the harmonic-major slots of the same call keep that stride
+    L.tiled = (L.momx && ppf::xspec_tiled(rfft_log2(d->nbin))) ? 1 : 0;
+    L.xnh = L.tiled ? (int)ppf::xtile_harm((int64_t)nharm) : (int)nharm;
+    L.X = o;     o += align256(sizeof(double2) * (size_t)L.xcap * nchan * (size_t)L.xnh);
     L.chan = o;  o += align256(sizeof(double) * nsub * nchan * 4);
     L.stats = o; o += align256(sizeof(double) * nsub * 2 * nchan * 10);
     L.x0 = o;    o += align256(sizeof(double) * nsub * 8);
@@ -301,6 +307,7 @@ FitLayout fit_layout(const ppf_fit_desc *d) {
     L.KC = o;    o += align256(sizeof(int32_t) * (size_t)(d->nmodel > 0 ? d->nmodel : 1) * nchan);
     L.needx = o; o += align256(nsub);
     L.xslot = o; o += align256(sizeof(int32_t) * nsub);
+    L.xtile = o; o += L.tiled ? align256(nsub) : 0;
     L.rclist = o; o += align256(sizeof(int32_t) * nsub);
     L.Bt = o;    o += align256(sizeof(double) * (nharm - 1) / 2 * 16);
     if (d->guess) {
@@ -637,8 +644,9 @@ int ppf_fit_batch(ppf_ctx *ctx, const ppf_fit_desc *d, void *stream) {
     const int use_moments = 1;
     uint8_t *needx = (uint8_t *)(ws + L.needx);
     int32_t *xslot = (int32_t *)(ws + L.xslot);
+    uint8_t *xtile = L.tiled ? (uint8_t *)(ws + L.xtile) : nullptr;
     if ((e = ppf::launch_classify(d->nsub, d->fit_flags, d->init, d->log10_tau, L.fused && !L.momx, L.xcap,
-                                  needx, xslot, st)) != hipSuccess)
+                                  needx, xslot, xtile, st)) != hipSuccess)
         return hip_fail(ctx, e, "k_classify");
     // fused guess: the sub-ints k_xspec_w streams whose mean-model cutoff
     // fits its guess harmonics accumulate the guess spectrum there
@@ -669,6 +677,8 @@ int ppf_fit_batch(ppf_ctx *ctx, const ppf_fit_desc *d, void *stream) {
     xa.X = (double2 *)(ws + L.X); xa.chan = (double *)(ws + L.chan);
     xa.Mpow = Mpow;
     xa.xslot = xslot;
+    xa.xtile = xtile;
+    xa.xnh = L.xnh;
     xa.gflag = gflag;
     if (gflag) {
         xa.gpart = (double2 *)(ws + L.gpart);
@@ -793,6 +803,8 @@ int ppf_fit_batch(ppf_ctx *ctx, const ppf_fit_desc *d, void *stream) {
     sa.mom16 = m16;
     sa.hcen = m16 ? (double *)(ws + L.hcen) : nullptr;
     sa.xslot = xslot;
+    sa.xtile = xtile;
+    sa.xnh = L.xnh;
     if (sa.moments) sa.any_plain = 0;      // plain fits go through the moments
     if ((e = ppf::launch_tr_init(sa, st)) != hipSuccess) return hip_fail(ctx, e, "k_tr_init");
     // how many fits iterate on the moments and how many on streaming passes:

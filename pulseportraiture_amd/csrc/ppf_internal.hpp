@@ -23,7 +23,7 @@ struct XspecArgs {
     const double *errs;          // [nsub][nchan] or null
     const double *freqs, *P;
     const double2 *T, *T2;
-    double2 *X;                  // [nsub][N+1][nchan] (harmonic-major)
+    double2 *X;                  // [slot][xnh][nchan] (harmonic-major; tiled slots: xtile below)
     double *chan;                // [nsub][nchan][4]
     const double2 *spec;         // k_xspec_spec: the rows' rFFTs [nsub][nchan][N+1] (long rows)
     // wave path: model row power sum_{k>=1} |M_nk|^2 ([nmodel][nchan]) and
@@ -34,6 +34,13 @@ struct XspecArgs {
     const int32_t *KC;           // [nmodel][nchan] harmonic cutoff (k_model_cut) or null: X is
                                  // written only below the cutoff of each 64-channel group
     const int32_t *xslot;        // [nsub] X slot of each sub-int (k_classify), or null: slot = s
+    // tiled slots (k_xspec_w2 -> k_moments, xspec_tiled()): xtile[s] set = the
+    // sub-int's slot is X[k/8][n][k%8] (one channel's 8 consecutive harmonics
+    // in one 128-byte line) instead of harmonic-major; null: no tiled slot.
+    // xnh: harmonics per channel of a slot, tiled or not (xtile_harm(N + 1)
+    // where slots are tiled, else N + 1)
+    const uint8_t *xtile;        // [nsub] or null
+    int xnh;
     // GetTOAs guess spectrum fused into the wave pass (gflag[s] set, see
     // k_gflag): sum_n w_n D_nk exp(2 pi i k dphi_n(DM_guess)) of the block's
     // rows for the harmonics guess_pairs() covers, per (sub-int, block)
@@ -166,6 +173,8 @@ struct SolveArgs {
     int mom16;
     double *hcen;                // [nsub][2][nchan]: h_n of each moment set (mom16)
     const int32_t *xslot;        // [nsub] X slot (k_classify; -1 none, -2 no room) or null
+    const uint8_t *xtile;        // [nsub] tiled X slot (XspecArgs::xtile) or null
+    int xnh;                     // harmonics per channel of an X slot (XspecArgs::xnh)
     unsigned *rc_count;          // sub-ints k_tr_mom sent back for a new moment centre
     int32_t *rc_list;            // [nsub] their indices (slot order of the atomic)
 };
@@ -382,8 +391,18 @@ hipError_t launch_xspec_wm(const XspecArgs &a, hipStream_t st);
 hipError_t launch_xspec_wave(const XspecArgs &a, hipStream_t st);
 hipError_t launch_xmom(const XmomArgs &a, bool full, hipStream_t st);
 hipError_t launch_btab(int N, double *Bt, hipStream_t st);
+// xtile (or null): 1 for the sub-ints whose X slot is tiled (the moment-mode
+// ones: no scattering), 0 for those k_pass streams
 hipError_t launch_classify(int nsub, const int32_t *fit_flags, const double *init, int log10_tau,
-                           int fused, int xcap, uint8_t *needx, int32_t *xslot, hipStream_t st);
+                           int fused, int xcap, uint8_t *needx, int32_t *xslot, uint8_t *xtile,
+                           hipStream_t st);
+// k_xspec_w2 writes the moment-mode sub-ints' X tiled (X[k/8][n][k%8]) for
+// k_moments: 1024-point rows on k_xspec_w2, unless PPF_XTILE=0 (environment,
+// read once) selects the harmonic-major slots and the round's write-out
+bool xspec_tiled(int log2N);
+// harmonics per channel of a tiled slot: whole tiles of 8
+constexpr int kXTile = 8;
+inline int64_t xtile_harm(int64_t nharm) { return (nharm + kXTile - 1) / kXTile * kXTile; }
 hipError_t launch_model_pow(const double2 *Mft, int nchan, int nharm, int nmodel, double *out,
                             hipStream_t st);
 hipError_t launch_model_sum(const double2 *Mft, int nchan, int nharm, int nmodel, double2 *out,

@@ -19,6 +19,7 @@
 // Splitting the cold trust-region / post-fit code out of the streaming pass
 // keeps the pass at <= 128 VGPRs (>= 4 waves/SIMD) with every harmonic load
 // of a channel row in flight.
+#include <type_traits>
 #include "ppf_device.hpp"
 #include "ppf_internal.hpp"
 #include "ppf_state.hpp"
@@ -162,19 +163,20 @@ constexpr int kClassifyBlock = 1024;
 __global__ __launch_bounds__(kClassifyBlock) void k_classify(int nsub, const int32_t *fit_flags,
                                                              const double *init, int log10_tau,
                                                              int fused, int xcap, uint8_t *needx,
-                                                             int32_t *xslot) {
+                                                             int32_t *xslot, uint8_t *xtile) {
     __shared__ int wtot[kClassifyBlock / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int base_slot = 0;
     for (int s0 = 0; s0 < nsub; s0 += kClassifyBlock) {
         const int s = s0 + tid;
-        int need = 0;
+        int need = 0, tile = 0;
         if (s < nsub) {
             const double x3 = init[(int64_t)s * 5 + 3];
             const double tau0 = log10_tau ? pow(10.0, x3) : x3;
             const bool scat =
                 fit_flags[(int64_t)s * 5 + 3] || fit_flags[(int64_t)s * 5 + 4] || tau0 != 0.0;
             need = (!fused || scat) ? 1 : 0;
+            tile = scat ? 0 : 1;             // moment mode: k_moments reads the slot
         }
         const unsigned long long bal = __ballot(need);
         const int below = __popcll(bal & ((1ull << lane) - 1ull));
@@ -188,6 +190,7 @@ __global__ __launch_bounds__(kClassifyBlock) void k_classify(int nsub, const int
             const int slot = off + below;
             needx[s] = (need && slot < xcap) ? 1 : 0;
             xslot[s] = need ? (slot < xcap ? slot : -2) : -1;
+            if (xtile) xtile[s] = (uint8_t)tile;
         }
         base_slot += chunk;
         __syncthreads();
@@ -453,7 +456,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_PASS
         const double phin = th[0] + kDconst * th[1] * (pow(nu, -2.0) - nuDM2) / g.P +
                             kDconst * kDconst * th[2] * (pow(nu, -4.0) - nuGM4) / g.P;
         const double2 W = cexp2pi(phin);
-        const double2 *Xc = a.X + (int64_t)(a.xslot ? a.xslot[s] : s) * nharm * a.nchan + n;
+        // (scattering sub-ints' slots are harmonic-major, never tiled)
+        const double2 *Xc = a.X + (int64_t)(a.xslot ? a.xslot[s] : s) *
+                                      a.xnh * a.nchan + n;
         const double *Pc = a.MP + (int64_t)mi * nharm * a.nchan + n;
         const int64_t xs = a.nchan;
         if (SCAT) {
@@ -1146,7 +1151,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_MOM_
     const double h = 0.5 * (double)(nharm - 1);
     const int ci = lane & 15, kk = lane >> 4;
     const int nbase = blk * kMomChans + wave * 16;
-    const int n = nbase + ci;
+    // Tiled slot (XspecArgs::xtile: X[k/8][n][k%8], one channel's 8
+    // consecutive harmonics in one 128-byte line): MFMA row r holds channel
+    // r / 2 (even r) or 8 + r / 2 (odd r) of the wave's 16, so that a load
+    // instruction covers whole lines (ldt below).  A row's sum does not
+    // depend on which row it is: the moments are those of the
+    // harmonic-major read, bit for bit.
+    const bool tiled = M16 && a.xtile && a.xtile[s];
+    auto rowchan = [&](int r) { return tiled ? (r >> 1) + 8 * (r & 1) : r; };
+    const int n = nbase + rowchan(ci);
     const bool valid = n < a.nchan && (!a.mask || a.mask[(int64_t)s * a.nchan + n]);
     double phin = 0.0;
     if (valid) {
@@ -1154,8 +1167,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_MOM_
         phin = c0 + c1 * dp[0] + c2 * dp[1];
         if (kk == 0) a.mres[((int64_t)s * 2 + q) * a.nchan + n] = 0.0;   // exact centre
     }
-    const double2 *Xr = a.X + (int64_t)(a.xslot ? a.xslot[s] : s) * nharm * a.nchan +
-                         (valid ? n : 0);   // X[slot][k][n]
+    const double2 *Xslot = a.X + (int64_t)(a.xslot ? a.xslot[s] : s) *
+                                     a.xnh * a.nchan;
+    const double2 *Xr = Xslot + (valid ? n : 0);   // X[slot][k][n]
     // harmonic cutoff of the wave's 16 channels (k_model_cut; they lie in one
     // aligned 64-channel group): X past it carries |M_k| < 1e-14 of the
     // channel's peak, and k_xspec_w writes X only below the group's largest
@@ -1208,8 +1222,36 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_MOM_
             xv[t] = ld_stream(Xr + (int64_t)kc * a.nchan);
         }
     };
+    // Tiled: per tile of 8 harmonics (two K-steps) two loads of 8 whole
+    // lines each.  Load A: channel ci / 2, harmonic kk + 4 (ci & 1); load B:
+    // channel 8 + ci / 2, harmonic kk + 4 (~ci & 1).  An even row then holds
+    // its channel's first K-step in A and its odd neighbour's second K-step
+    // in B, an odd row the other way round: one quad_perm swap per tile
+    // (opt).  Channels past nchan are clamped, tiles past the cutoff's tile
+    // too (k_xspec_w2 writes whole tiles below the group's cutoff).
+    static_assert(KU % 2 == 0, "a tile is two K-steps");
+    const bool odd = (ci & 1) != 0;
+    const double2 *XtA = Xslot + (int64_t)min(nbase + (ci >> 1), a.nchan - 1) * kXTile + kk + (odd ? 4 : 0);
+    const double2 *XtB = Xslot + (int64_t)min(nbase + 8 + (ci >> 1), a.nchan - 1) * kXTile + kk + (odd ? 0 : 4);
+    const int gmax = (kend - 1) >> 3;
+    auto ldt = [&](double2 (&xv)[KU], int kb) {
+#pragma unroll
+        for (int t = 0; t < KU; t += 2) {
+            const int g = min((kb >> 3) + (t >> 1), gmax);
+            const int64_t go = (int64_t)g * a.nchan * kXTile;
+            xv[t] = ld_stream(XtA + go);
+            xv[t + 1] = ld_stream(XtB + go);
+        }
+    };
+    // K-step t's operand of the lane's own channel from a tiled batch
+    auto opt = [&](const double2 (&xv)[KU], int t) {
+        const double2 A = xv[t & ~1], B = xv[t | 1];
+        if ((t & 1) == 0) return odd ? B : A;
+        const double2 snd = odd ? A : B;
+        return cmk(dpp_d<0xB1, 0xf>(snd.x), dpp_d<0xB1, 0xf>(snd.y));   // quad_perm [1,0,3,2]
+    };
     auto keep = [&](int k) { return valid && k < kend; };
-    auto mm = [&](const double2 (&xv)[KU], int kb) {
+    auto mm = [&](const double2 (&xv)[KU], int kb, auto tl) {
 #if PPF_MOM_ILP
         // base phasor of the batch (k = kb + kk), re-seeded exactly every
         // 64 harmonics (kb is a multiple of 4 KU)
@@ -1228,7 +1270,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_MOM_
             else E = cmul(E, W4);
             const double2 Et = E;
 #endif
-            const double2 xk = keep(k) ? xv[t] : cmk(0.0, 0.0);
+            double2 xt;
+            if constexpr (decltype(tl)::value) xt = opt(xv, t);
+            else xt = xv[t];
+            const double2 xk = keep(k) ? xt : cmk(0.0, 0.0);
             const double2 y = cmul(xk, Et);
             const double u = ((double)k - hw) * ihw;
             const double u2 = u * u, u4 = u2 * u2, u8 = u4 * u4, u16 = u8 * u8;
@@ -1254,14 +1299,22 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_MOM_
     };
     // two batches in flight, the buffers alternating (no register copy, so
     // no wait for the batch just issued)
-    ld(xa, 0);
-    ld(xb, 4 * KU);
-    for (int kb = 0; kb < kend; kb += 8 * KU) {
-        mm(xa, kb);
-        ld(xa, kb + 8 * KU);
-        if (kb + 4 * KU < kend) mm(xb, kb + 4 * KU);    // (uniform)
-        ld(xb, kb + 12 * KU);
-    }
+    auto run = [&](auto tl) {
+        auto ldx = [&](double2 (&xv)[KU], int kb) {
+            if constexpr (decltype(tl)::value) ldt(xv, kb);
+            else ld(xv, kb);
+        };
+        ldx(xa, 0);
+        ldx(xb, 4 * KU);
+        for (int kb = 0; kb < kend; kb += 8 * KU) {
+            mm(xa, kb, tl);
+            ldx(xa, kb + 8 * KU);
+            if (kb + 4 * KU < kend) mm(xb, kb + 4 * KU, tl);    // (uniform)
+            ldx(xb, kb + 12 * KU);
+        }
+    };
+    if (tiled) run(std::true_type{});                  // (uniform)
+    else run(std::false_type{});
 #if PPF_MOM_ILP
     if constexpr (m16) {
 #pragma unroll
@@ -1275,7 +1328,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_MOM_
     double2 *M = a.mom + ((int64_t)s * 2 + q) * a.nchan * kMoments;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const int ch = nbase + kk + 4 * r;
+        const int ch = nbase + rowchan(kk + 4 * r);
         if (ch < a.nchan) {
             M[(int64_t)ch * kMoments + ci] = cmk(dre0[r], dim0[r]);
             if constexpr (!m16) M[(int64_t)ch * kMoments + 16 + ci] = cmk(dre1[r], dim1[r]);
@@ -2022,9 +2075,10 @@ __global__ __launch_bounds__(PB) PPF_POSTFIT_ATTR void k_postfit(SolveArgs a) {
 // launchers
 // ===========================================================================
 hipError_t launch_classify(int nsub, const int32_t *fit_flags, const double *init, int log10_tau,
-                           int fused, int xcap, uint8_t *needx, int32_t *xslot, hipStream_t st) {
+                           int fused, int xcap, uint8_t *needx, int32_t *xslot, uint8_t *xtile,
+                           hipStream_t st) {
     hipLaunchKernelGGL(k_classify, dim3(1), dim3(kClassifyBlock), 0, st, nsub, fit_flags, init,
-                       log10_tau, fused, xcap, needx, xslot);
+                       log10_tau, fused, xcap, needx, xslot, xtile);
     return hipGetLastError();
 }
 

@@ -1021,14 +1021,25 @@ __global__ __launch_bounds__(256) void k_model_sum(const double2 *Mft, int nchan
 // sigma~^2 (pptoaslib.py:1014-1031) as k_xspec_w; the fused GetTOAs guess
 // (GS, pptoas.py:461-464) as k_xspec_w, its terms in the slots of N - k.
 // PPF_XSPEC2=0 (environment) selects k_xspec_w instead.
+//
+// TL (round 7): the sub-ints whose slot is tiled (XspecArgs::xtile: the
+// moment-mode ones, read by k_moments).  X[slot][k/8][n][k%8] keeps one
+// channel's 8 consecutive harmonics in one 128-byte line, so the wave that
+// transformed a row also stores it: after wave_sum has given 1/sigma~^2 it
+// reads its staged X back in harmonic order (lane l: harmonic l + 64 j) and
+// each store instruction writes 8 whole lines.  No workgroup barrier in
+// the round loop; the fused guess terms are summed in registers per wave
+// (the lane that holds harmonic hl in slot i is the same for every row) and
+// the four waves' partials in wave order once, after the last round.  The
+// X values are those of the harmonic-major write-out bit for bit; the guess
+// spectrum differs in its last bits (summation order, and the row's phasors
+// taken as powers of one phasor per channel: see ch_e1).  !TL: the
+// harmonic-major slots (scattering sub-ints, which k_pass streams; every
+// sub-int with PPF_XTILE=0) and the round's write-out after a barrier.
 // ===========================================================================
-// waves per workgroup (= rows per round, channels per X line written:
-// 4 -> 64-B segments of the 128-B lines, two workgroups per CU; 8 -> whole
-// lines, one workgroup per CU)
-#ifndef PPF_X2W
-#define PPF_X2W 4
-#endif
-constexpr int kX2W = PPF_X2W;
+// waves per workgroup (= rows per round; !TL: channels per X line written,
+// 64-B segments of the 128-B lines); two workgroups per CU
+constexpr int kX2W = 4;
 constexpr int kX2SL = wf2::kXSlots + wf2::kSpSlots;       // 1072 slots per wave
 constexpr int kX2IE = 1041;                               // the row's 1/errs_FT^2 (.x)
 __device__ __forceinline__ int x2slot(int k) { return k + (k >> 6); }   // k <= 1024 -> <= 1040
@@ -1056,14 +1067,23 @@ __device__ __forceinline__ int x2slot(int k) { return k + (k >> 6); }   // k <= 
 #ifndef PPF_X2_DIAG
 #define PPF_X2_DIAG 0
 #endif
-#ifndef PPF_X2_WR
-#define PPF_X2_WR 0
+// TL guess sums: 1 = per-wave partials in registers, no barrier in the round
+// loop; 0 = the round's two barriers kept for the guess add only (the X
+// stores still go out whole lines, by the row's own wave, before the first)
+#ifndef PPF_X2_GREG
+#define PPF_X2_GREG 1
 #endif
 
-template <int DT, bool GS>
+template <int DT, bool GS, bool TL>
 __global__ __launch_bounds__(64 * kX2W) __attribute__((amdgpu_waves_per_eu(2)))
 void k_xspec_w2(XspecArgs a) {
     constexpr int N = 1024, NH = N + 1;
+    constexpr bool GR = TL && PPF_X2_GREG != 0;      // guess partials in registers
+    // GR with the guess: the per-lane constants of the transform and of
+    // the post-pass, and the channels' guess phasors, in an LDS table behind
+    // the wave buffers (one copy per workgroup, read back every row)
+    // instead of 16 VGPRs held across the round loop
+    constexpr bool LT = GR && GS;
     constexpr int MD = PPF_X2_MD;
     using RowT = typename std::conditional<DT == 0, vf2, vd2>::type;
     extern __shared__ __attribute__((aligned(16))) double2 lds[];
@@ -1076,6 +1096,7 @@ void k_xspec_w2(XspecArgs a) {
     int s, cb;
     block_map(a.xcd_swizzle, a.nblk, s, cb, a.nsub);
     if (a.needx && !a.needx[s]) return;               // uniform: moment-mode sub-int (or no slot)
+    if (a.xtile ? (a.xtile[s] != 0) != TL : TL) return;   // uniform: the other instantiation's slot layout
     const int cbase = cb * a.cb, cend = min(a.nchan, cbase + a.cb);
     const int nround = (a.cb + kX2W - 1) / kX2W;
     const int mi = a.model_index ? a.model_index[s] : 0;
@@ -1093,12 +1114,32 @@ void k_xspec_w2(XspecArgs a) {
         sincospi(-64.0 / (double)N, &sn, &cs);
         wstep = cmk(cs, sn);
     }
-    double2 *Xs = a.X + (int64_t)(a.xslot ? a.xslot[s] : s) * NH * a.nchan;
+    double2 *Xs = a.X + (int64_t)(a.xslot ? a.xslot[s] : s) * a.xnh * a.nchan;
     int kw = NH;
     if (a.KC) {
         const int nn = (cbase & ~63) + lane0;
         kw = (int)wave_max(nn < a.nchan ? (double)a.KC[(int64_t)mi * a.nchan + nn] : 1.0);
     }
+    // TL: the wave's own channel n, harmonics below kw rounded up to whole
+    // tiles (zeros past kw, and for a masked channel), lane l: harmonics l +
+    // 64 j -- per store instruction 8 tiles, each one whole 128-byte line
+    auto store_tiles = [&](int n, const double2 *b, double ie2, bool ok) {
+        const int kwp = (kw + kXTile - 1) & ~(kXTile - 1);
+        double2 *Xn = Xs + (int64_t)n * kXTile + (lane0 & (kXTile - 1));
+#pragma unroll 1
+        for (int h = lane0; h < kwp; h += 64) {
+            const double2 v = (ok && h < kw) ? cscale(b[x2slot(h)], ie2) : cmk(0.0, 0.0);
+#if PPF_X2_DIAG & 1
+            if (ie2 == 12345.0)            // (timing-only build: no X stores)
+#endif
+#if PPF_X2_NT & 2
+            __builtin_nontemporal_store(vd2{v.x, v.y},
+                                        reinterpret_cast<vd2 *>(Xn + (int64_t)(h >> 3) * a.nchan * kXTile));
+#else
+            Xn[(int64_t)(h >> 3) * a.nchan * kXTile] = v;
+#endif
+        }
+    };
     const int mlane = (cbase + lane0 < cend && (!mask || mask[cbase + lane0])) ? 1 : 0;
     auto usable = [&](int n) {
         return n < cend && __builtin_amdgcn_readlane(mlane, n - cbase) != 0;
@@ -1110,7 +1151,8 @@ void k_xspec_w2(XspecArgs a) {
     if constexpr (GS) {
         gon = a.gflag[s] != 0;                         // uniform
         if (gon) {
-            for (int t = threadIdx.x; t < NL; t += 64 * kX2W) gacc[t] = cmk(0.0, 0.0);
+            if constexpr (!GR)
+                for (int t = threadIdx.x; t < NL; t += 64 * kX2W) gacc[t] = cmk(0.0, 0.0);
             const double *fr = a.freqs + (int64_t)s * a.nchan;
             double v0 = 0.0, v1 = 0.0;
             for (int nn = lane0; nn < a.nchan; nn += 64)
@@ -1125,9 +1167,15 @@ void k_xspec_w2(XspecArgs a) {
             }
             g_Dg = readlane_d(kDconst * a.guess_DM[s] / a.P[s], 0);
             g_nrm2 = readlane_d(nu_ref_m2, 0);
-            __syncthreads();
+            if constexpr (!GR) __syncthreads();
         }
     }
+    // GR: the wave's guess partials, slot i of every row it transforms (the
+    // slot's harmonic hl is fixed per lane; only 1 <= hl < NL is written out
+    // at the end -- 7 of the 8 slots of a lane, the eighth sums unused terms)
+    double2 gr[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) gr[i] = cmk(0.0, 0.0);
     // the block's per-channel scalars in lane registers (lane l: channel
     // cbase + l): a global load of them inside the round loop would wait,
     // vmcnt being in order, for the next row's prefetch
@@ -1140,6 +1188,25 @@ void k_xspec_w2(XspecArgs a) {
         ch_wn = a.guess_weights[(int64_t)s * a.nchan + nl];
         const double f = a.freqs[(int64_t)s * a.nchan + nl];
         ch_dg = g_Dg * (1.0 / (f * f) - g_nrm2);
+    }
+    // GR: the channel's unit phasor e^{2 pi i dphi_n} once, here: the row's
+    // phasors are its powers (below).  A cexp2pi per row keeps sincospi's
+    // polynomial constants in VGPRs across the whole round loop, which with
+    // the 32 registers of gr spilled 27 of them to scratch, reloaded one
+    // by one behind vmcnt(0) in every row
+    double2 ch_e1 = cmk(1.0, 0.0);
+    if constexpr (GR) {
+        if (GS && gon) ch_e1 = cexp2pi(ch_dg);
+    }
+    double2 *ltab = lds + kX2W * kX2SL;              // [4][64]: w1, v1, wA0, e1
+    if constexpr (LT) {
+        if (wave == 0) {
+            ltab[lane0] = sd.w1;
+            ltab[64 + lane0] = sd.v1;
+            ltab[128 + lane0] = wA0;
+            ltab[192 + lane0] = ch_e1;
+        }
+        __syncthreads();
     }
     RowT zr[16];
     auto fetch = [&](int n) {
@@ -1179,7 +1246,7 @@ void k_xspec_w2(XspecArgs a) {
     for (int r = 0; r < nround; ++r, n += kX2W) {
         const bool live = usable(n);
 #if PPF_X2_EW
-        if (!PPF_X2_WR && n < cend && !live && lane0 < 4) a.chan[((int64_t)s * a.nchan + n) * 4 + lane0] = 0.0;
+        if (n < cend && !live && lane0 < 4) a.chan[((int64_t)s * a.nchan + n) * 4 + lane0] = 0.0;
         double2 x[16];
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
@@ -1248,7 +1315,14 @@ void k_xspec_w2(XspecArgs a) {
 #endif
             XP(0);
 #if !(PPF_X2_DIAG & 4)
-            wf2::fft1024(x, buf, lane, sd);
+            if constexpr (LT) {
+                wf2::Seeds sdl;
+                sdl.w1 = ltab[lane];
+                sdl.v1 = ltab[64 + lane];
+                wf2::fft1024(x, buf, lane, sdl);
+            } else {
+                wf2::fft1024(x, buf, lane, sd);
+            }
 #endif
             XP(1);
             if (PPF_X2_EW) __builtin_amdgcn_sched_barrier(0);
@@ -1259,7 +1333,30 @@ void k_xspec_w2(XspecArgs a) {
             XP(2);
             // guess phasor w_n e^{2 pi i hl dphi}, step e^{+-2 pi i 64 dphi}
             double2 El = cmk(0.0, 0.0), Est = El;
-            if (GS && gon) {
+            if constexpr (GR) {
+                if (GS && gon) {
+                    // hl0 = m (lanes <= 32) or 512 - m (the others), m = lane
+                    // mod 32 (lane 32: 32): e1^m by square and multiply over
+                    // the uniform e1^(2^b), e1^512 by four more squarings
+                    const double2 b1 = LT ? ltab[192 + rr] : cmk(readlane_d(ch_e1.x, rr), readlane_d(ch_e1.y, rr));
+                    const double2 b2 = cmul(b1, b1), b4 = cmul(b2, b2), b8 = cmul(b4, b4);
+                    const double2 b16 = cmul(b8, b8), b32 = cmul(b16, b16), b64 = cmul(b32, b32);
+                    const int m = lane == 32 ? 32 : (lane & 31);
+                    double2 pw = (m & 1) ? b1 : cmk(1.0, 0.0);
+                    if (m & 2) pw = cmul(pw, b2);
+                    if (m & 4) pw = cmul(pw, b4);
+                    if (m & 8) pw = cmul(pw, b8);
+                    if (m & 16) pw = cmul(pw, b16);
+                    if (m & 32) pw = b32;
+                    double2 E1 = pw;
+                    if (!lo) {
+                        const double2 b128 = cmul(b64, b64), b256 = cmul(b128, b128);
+                        E1 = cmulc(cmul(b256, b256), pw);
+                    }
+                    El = cscale(E1, readlane_d(ch_wn, rr));
+                    Est = lo ? b64 : cconj(b64);
+                }
+            } else if (GS && gon) {
                 const double dg = readlane_d(ch_dg, rr);
                 const double2 E1 = cexp2pi((double)hl0 * dg);
                 El = cscale(E1, readlane_d(ch_wn, rr));
@@ -1282,7 +1379,7 @@ void k_xspec_w2(XspecArgs a) {
             const double sg = lo ? 1.0 : -1.0;
             const int hcut = N - a.kc;            // N - hl >= kc  <=>  hl <= hcut
             double pn = 0.0, pd = 0.0;
-            double2 w = wA0;
+            double2 w = LT ? ltab[128 + lane] : wA0;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const double2 zk = x[i], zn = x[i + 8];
@@ -1311,9 +1408,11 @@ void k_xspec_w2(XspecArgs a) {
                 // (k = 0 -- lane 0, slot 0 only -- is zeroed after the loop)
                 if (hl < kw) buf[x2slot(hl)] = cmulc(Dl, Ml);
                 if (GS && gon) {
-                    // 2 x the row's guess term of harmonic hl, in the slot
-                    // of N - hl (past X's cutoff: kw <= NL < N/2)
-                    if (hl >= 1 && hl < NL) buf[x2slot(N - hl)] = cmul(Dl, El);
+                    // 2 x the row's guess term of harmonic hl: GR into the
+                    // wave's partial; else staged in the slot of N - hl
+                    // (past X's cutoff: kw <= NL < N/2)
+                    if constexpr (GR) gr[i] = cadd(gr[i], cmul(Dl, El));
+                    else if (hl >= 1 && hl < NL) buf[x2slot(N - hl)] = cmul(Dl, El);
                     El = cmul(El, Est);
                 } else if (kw > N / 2) {
                     // the group's cutoff passes N/2: the high harmonic too
@@ -1348,58 +1447,45 @@ void k_xspec_w2(XspecArgs a) {
             const double mpow = readlane_d(ch_mpow, rr);
             if (lane == 0) {
                 // for the write-out: the staged X are doubled
-                reinterpret_cast<double *>(buf + kX2IE)[0] = 0.5 * inv_e2;
-#if PPF_X2_WR
-                // the channel scalars go out with the round's write-out
-                buf[kX2IE + 1] = cmk(errs_FT, inv_e2);
-                buf[kX2IE + 2] = cmk(pd * inv_e2, mpow * inv_e2);    // Sd_n, S_n at tau = 0
-                (void)crow;
-#else
+                if constexpr (!TL) reinterpret_cast<double *>(buf + kX2IE)[0] = 0.5 * inv_e2;
                 double *chan = a.chan + crow * 4;
                 chan[0] = errs_FT;
                 chan[1] = inv_e2;
                 chan[2] = pd * inv_e2;                                  // Sd_n
                 chan[3] = mpow * inv_e2;                                // S_n at tau = 0
-#endif
             }
-        }
+            if constexpr (TL) {
 #if PPF_X2_EW
-        rows_ready();
+                rows_ready();
 #endif
-        XP(4);
+                XP(4);
+                // (a wave's LDS operations are ordered: the staged X of
+                // every lane is there, and read before the next row's
+                // exchange overwrites it)
+                wfft::wave_sync();
+                store_tiles(n, buf, 0.5 * inv_e2, true);
+                wfft::wave_sync();
+                XP(5);
+            }
+        } else if constexpr (TL) {
+#if PPF_X2_EW
+            rows_ready();
+#endif
+            if (n < cend) store_tiles(n, buf, 0.0, false);    // a zapped channel's tiles: zeros
+        }
+        if constexpr (GR) continue;
+        if (TL && !(GS && gon)) continue;         // (uniform) no guess terms to add: no barrier
+        if constexpr (!TL) {
+#if PPF_X2_EW
+            rows_ready();
+#endif
+            XP(4);
+        }
         __syncthreads();
         XP(5);
-#if PPF_X2_WR
-        // write-out by ONE wave per round (wave r mod 4, rotating): vmcnt
-        // counts stores and loads in issue order, so a wave that stores
-        // waits for the acknowledgements at its next load wait; here three
-        // of four waves issue no global store in a round.  Lane l: channel
-        // l % 4 of the round, harmonics l / 4 + 16 j; lanes < 16 also the
-        // round's channel scalars (zero for a zapped channel)
-        if (wave == r % kX2W) {
-            const int c = lane0 % kX2W, n0 = cbase + r * kX2W;
-            const int nc = n0 + c;
-            if (nc < cend) {
-                const bool ok = !mask || mask[nc];
-                const double2 *b = lds + c * kX2SL;
-                const double ie2 = ok ? reinterpret_cast<const double *>(b + kX2IE)[0] : 0.0;
-                for (int k = lane0 / kX2W; k < kw; k += 64 / kX2W)
-                    Xs[(int64_t)k * a.nchan + nc] = ok ? cscale(b[x2slot(k)], ie2) : cmk(0.0, 0.0);
-            }
-            if (lane0 < 4 * kX2W) {
-                const int cc = lane0 >> 2, comp = lane0 & 3, ncc = n0 + cc;
-                if (ncc < cend) {
-                    const bool okc = !mask || mask[ncc];
-                    const double v = reinterpret_cast<const double *>(lds + cc * kX2SL + kX2IE + 1)[comp];
-                    a.chan[((int64_t)s * a.nchan + ncc) * 4 + comp] = okc ? v : 0.0;
-                }
-            }
-        }
-        if (false)
-#endif
         // write-out: thread t -> channel c = t % 4 of the round, harmonics
         // k = t / 4 + 64 j
-        {
+        if constexpr (!TL) {
             const int c = threadIdx.x % kX2W, n0 = cbase + r * kX2W;
             const int nc = n0 + c;
             if (nc < cend) {
@@ -1444,11 +1530,38 @@ void k_xspec_w2(XspecArgs a) {
         if (gon) {
             double2 *gp = a.gpart + ((int64_t)s * a.nblk + cb) * NL;
             // (the staged guess terms are doubled: exact factor 1/2)
-            for (int t = threadIdx.x; t < NL; t += 64 * kX2W) gp[t] = cscale(gacc[t], 0.5);
+            if constexpr (!GR)
+                for (int t = threadIdx.x; t < NL; t += 64 * kX2W) gp[t] = cscale(gacc[t], 0.5);
             const double gwl = mlane ? a.guess_weights[(int64_t)s * a.nchan + cbase + lane0] : 0.0;
             const double wsum = wave_sum(gwl), cnt = wave_sum(mlane ? 1.0 : 0.0);
+            if constexpr (GR) {
+                // the wave's partials into its own buffer, slot hl (1 <= hl
+                // < NL; slot 0 takes g_w2e2 below): every wave is past its
+                // last row's reads of it
+                const bool lo = lane0 <= 32;
+                const int kA = wf2::pair_k0(lane0);
+                const int hl0 = lo ? kA : N - kA, hstep = lo ? 64 : -64;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const int hl = hl0 + hstep * i;
+                    if (hl >= 1 && hl < NL) buf[hl] = gr[i];
+                }
+            }
             if (lane0 == 0) reinterpret_cast<double *>(buf)[0] = g_w2e2;
             __syncthreads();
+            if constexpr (GR) {
+                // the four waves' partials in wave order (fixed: the result
+                // does not depend on timing)
+                for (int t = threadIdx.x; t < NL; t += 64 * kX2W) {
+                    double2 acc = cmk(0.0, 0.0);
+                    if (t > 0) {
+                        acc = lds[t];
+#pragma unroll
+                        for (int w2 = 1; w2 < kX2W; ++w2) acc = cadd(acc, lds[w2 * kX2SL + t]);
+                    }
+                    gp[t] = cscale(acc, 0.5);
+                }
+            }
             if (threadIdx.x == 0) {
                 double acc = 0.0;
                 for (int w2 = 0; w2 < kX2W; ++w2) acc += reinterpret_cast<const double *>(lds + w2 * kX2SL)[0];
@@ -1934,6 +2047,19 @@ static bool use_xspec2() {
     }();
     return on;
 }
+// tiled X slots for the moment-mode sub-ints of k_xspec_w2 unless PPF_XTILE=0
+// (environment, read once): then every slot is harmonic-major and written
+// by the round's write-out, as before round 7
+#ifndef PPF_XTILE
+#define PPF_XTILE 1
+#endif
+bool xspec_tiled(int log2N) {
+    static const bool on = [] {
+        const char *e = getenv("PPF_XTILE");
+        return e ? atoi(e) != 0 : (PPF_XTILE != 0);
+    }();
+    return on && log2N == 10 && use_xspec2();
+}
 
 // ===========================================================================
 // launchers
@@ -1944,10 +2070,19 @@ static void launch_w(const XspecArgs &a, hipStream_t st) {
         if (use_xspec2()) {
             const size_t lds = (size_t)kX2W * kX2SL * sizeof(double2);
             dim3 g((unsigned)((int64_t)a.nsub * a.nblk)), b(64 * kX2W);
+            // tiled slots (xtile): the moment-mode sub-ints on the TL
+            // instantiation, then the scattering ones (harmonic-major slots)
+            // on the other; each skips the other's sub-ints
+            if (a.xtile) {
+                if (a.gflag)
+                    hipLaunchKernelGGL((k_xspec_w2<DT, true, true>), g, b,
+                                       lds + (size_t)(PPF_X2_GREG ? 256 : guess_slots(10)) * sizeof(double2), st, a);
+                else hipLaunchKernelGGL((k_xspec_w2<DT, false, true>), g, b, lds, st, a);
+            }
             if (a.gflag)
-                hipLaunchKernelGGL((k_xspec_w2<DT, true>), g, b, lds + (size_t)guess_slots(10) * sizeof(double2),
-                                   st, a);
-            else hipLaunchKernelGGL((k_xspec_w2<DT, false>), g, b, lds, st, a);
+                hipLaunchKernelGGL((k_xspec_w2<DT, true, false>), g, b,
+                                   lds + (size_t)guess_slots(10) * sizeof(double2), st, a);
+            else hipLaunchKernelGGL((k_xspec_w2<DT, false, false>), g, b, lds, st, a);
             return;
         }
     }
