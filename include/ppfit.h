@@ -49,7 +49,9 @@ extern "C" {
 /* ABI 6 (round 6): ppf_noise_long, ppf_rotate_long (+ their workspace
  * queries), ppf_align_phases, PPF_OPT_SPIN_WAIT; ppf_fit_batch /
  * ppf_gauss_portrait_batch / ppf_phase_shift_batch accept nbin past the LDS
- * transforms (even > 8192, odd > 4095) on the long transforms. */
+ * transforms (even > 8192, odd > 4095) on the long transforms.
+ * ppf_inst_response_batch was added later without a bump (purely additive:
+ * no structure or existing signature changed). */
 #define PPF_ABI_VERSION 6
 
 enum ppf_error {
@@ -318,6 +320,27 @@ int ppf_rotate_batch(ppf_ctx *ctx, int64_t nrows, int32_t nbin,
 int ppf_rotate_batch_ref(ppf_ctx *ctx, int64_t nrows, int32_t nbin,
                          int32_t in_dtype, const void *in, const double *phases,
                          double *out, void *stream);
+
+/* Instrumental response on template rows (added within ABI 6: a library
+ * without the symbol is a stale build):
+ *   out_r = irfft(rfft(src[src_row[r]]) * table[k] * sinc(k * widths[r]))
+ * with sinc(x) = sin(pi x) / (pi x).  Replaces the convolution of
+ * pptoas.py:428-434, 983-989 and 1446-1452 with the multiplier of
+ * pptoaslib.instrumental_response_port_FT (pptoaslib.py:158-192): table is
+ * the product of its constant-width factors (wids / irf_types), widths[r] the
+ * row's dispersive-smearing rectangle 8.3e-6 chan_bw / (nu_r / 1e3)**3 / P
+ * [rot] (0: no such factor).  src_row lets one template portrait fan out into
+ * its several (P, chan_bw) variants in one launch; every src_row[r] must
+ * index a row of src (not checked on the device).  DC and Nyquist terms keep
+ * their real parts only, as numpy.fft.irfft does.
+ * src: [nsrc][nbin] double; src_row: [nrows] int32; table: [nbin / 2 + 1]
+ * double, or NULL for all ones; widths: [nrows] double; out: [nrows][nbin]
+ * double (must not overlap src).  Even nbin the LDS transforms take
+ * (32..8192); odd nbin and longer rows return PPF_EUNSUP. */
+int ppf_inst_response_batch(ppf_ctx *ctx, int64_t nrows, int32_t nbin,
+                            const double *src, const int32_t *src_row,
+                            const double *table, const double *widths,
+                            double *out, void *stream);
 
 /* ppalign.align_archives accumulation (ppalign.py:236-247, the inner
  * "aligned_port += weights * rotate_data(...)" / "total_weights += weights"

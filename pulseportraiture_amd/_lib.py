@@ -92,6 +92,8 @@ SIGNATURES = {
                                         _vp, _vp, _vp]),
     "ppf_rotate_batch_ref": (ctypes.c_int, [_vp, ctypes.c_int64, _i32, _i32,
                                             _vp, _vp, _vp, _vp]),
+    "ppf_inst_response_batch": (ctypes.c_int, [_vp, ctypes.c_int64, _i32, _vp,
+                                               _vp, _vp, _vp, _vp, _vp]),
     "ppf_noise_batch": (ctypes.c_int, [_vp, ctypes.c_int64, _i32, _i32, _vp,
                                        _i32, _vp, _vp]),
     "ppf_rotate_long_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64,
@@ -165,7 +167,14 @@ def load():
                     LIB_PATH)
             lib = ctypes.CDLL(LIB_PATH)
             for name, (res, args) in SIGNATURES.items():
-                fn = getattr(lib, name)
+                try:
+                    fn = getattr(lib, name)
+                except AttributeError:
+                    # an entry point added without an ABI bump
+                    # (ppf_inst_response_batch): a library built before it
+                    raise RuntimeError(
+                        "libppfit ABI mismatch: %s missing (rebuild with "
+                        "make)" % name) from None
                 fn.restype = res
                 fn.argtypes = args
             if lib.ppf_abi_version() != ABI_VERSION or \

@@ -982,6 +982,28 @@ int ppf_rotate_batch_ref(ppf_ctx *ctx, int64_t nrows, int32_t nbin, int32_t in_d
     return rotate_batch(ctx, nrows, nbin, in_dtype, in, phases, out, stream, true);
 }
 
+int ppf_inst_response_batch(ppf_ctx *ctx, int64_t nrows, int32_t nbin, const double *src,
+                            const int32_t *src_row, const double *table, const double *widths,
+                            double *out, void *stream) {
+    if (!ctx) return PPF_EINVAL;
+    // the block LDS transform of even rows only: odd nbin (the reference's
+    // length-less irfft gives nbin - 1 bins there) and long rows are refused
+    if ((nbin & 1) || !nbin_supported(nbin))
+        return fail(ctx, PPF_EUNSUP, "instrumental response: nbin=%d unsupported (even, 32..8192)", nbin);
+    if (nrows < 0 || nrows > 0x7fffffff || (nrows > 0 && (!src || !src_row || !widths || !out)))
+        return fail(ctx, PPF_EINVAL, "bad instrumental response arguments");
+    if (nrows == 0) return PPF_OK;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
+    hipStream_t st = (hipStream_t)stream;
+    const double2 *T, *T2;
+    int rc = twiddles(ctx, nbin, st, &T, &T2);
+    if (rc) return rc;
+    ppf::InstRespArgs a{nbin, src, src_row, table, widths, T, T2, out};
+    if ((e = ppf::launch_inst_resp(a, nrows, st)) != hipSuccess) return hip_fail(ctx, e, "k_inst_resp");
+    return PPF_OK;
+}
+
 size_t ppf_align_workspace_bytes(int32_t nsub, int32_t nchan, int32_t nbin) {
     if (nsub <= 0 || nchan <= 0 || nbin <= 0) return 0;
     const size_t g = (size_t)ppf::align_groups(nsub, nchan);

@@ -193,6 +193,18 @@ struct RotateArgs {
     const double2 *Te, *T2e;
 };
 
+// Instrumental response on template rows (pptoaslib.py:124-192):
+// out_r = irfft(rfft(src[src_row_r]) * table_k * sinc(k widths_r)), even nbin
+struct InstRespArgs {
+    int nbin;
+    const double *src;           // [nsrc][nbin]
+    const int32_t *src_row;      // [nrows] source row of each output row
+    const double *table;         // [nbin / 2 + 1] constant-width factors, or null (ones)
+    const double *widths;        // [nrows] rect width of the row [rot]; 0: factor 1
+    const double2 *T, *T2;
+    double *out;                 // [nrows][nbin]
+};
+
 // ppalign accumulation (ppalign.py:236-247): per channel, sum_s w_sn *
 // rotate(x_sn, phase_sn), done in the frequency domain
 struct AlignArgs {
@@ -427,6 +439,7 @@ hipError_t launch_postfit(const SolveArgs &a, hipStream_t st);
 size_t tr_state_bytes();
 int pass_blocks(int nchan);
 hipError_t launch_rotate(const RotateArgs &a, int64_t nrows, hipStream_t st);
+hipError_t launch_inst_resp(const InstRespArgs &a, int64_t nrows, hipStream_t st);
 hipError_t launch_noise(const NoiseArgs &a, int64_t nrows, hipStream_t st);
 int lf_pow_blocks(const LongNoiseArgs &a);
 hipError_t launch_chirp_ft(const LongNoiseArgs &a, double2 *Bf, double2 *Bs, const double2 *T1,

@@ -1214,6 +1214,56 @@ __global__ __launch_bounds__(kBlock) void k_rotate(RotateArgs a) {
 }
 
 // ===========================================================================
+// k_inst_resp: out_r = irfft(rfft(src[src_row_r]) * T_k * sinc(k w_r)), the
+// instrumental response on a template row (pptoaslib.py:124-192 with
+// pptoas.py:428-434): T the product of the constant-width factors (null: all
+// ones), w_r the row's dispersive-smearing width [rot].  Even nbin only; the
+// transforms and the harmonic pairing are k_rotate's.
+// ===========================================================================
+// sin(pi x) / (pi x); sinpi reduces the argument exactly (x reaches nharm * w)
+__device__ __forceinline__ double sinc_pi(double x) {
+    return x == 0.0 ? 1.0 : sinpi(x) / (kPi * x);
+}
+
+template <int KMAX, bool MX>
+__global__ __launch_bounds__(kBlock) void k_inst_resp(InstRespArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double2 lds[];
+    const int N = a.nbin >> 1;
+    const int64_t row = blockIdx.x;
+    load_row(lds, a.src, 1, (int64_t)a.src_row[row], a.nbin);
+    __syncthreads();
+    lds_fft_n<MX>(lds, N, a.T, false);
+    double2 Xk[KMAX], Xn[KMAX];
+    const double w = a.widths[row];
+    // harmonics of this thread: k = tid + 256 i < N, paired with N - k
+    // (k = 0 with the Nyquist term)
+#pragma unroll
+    for (int i = 0; i < KMAX; ++i) {
+        const int k = threadIdx.x + i * kBlock;
+        if (k < N) {
+            double f1 = sinc_pi((double)k * w), f2 = sinc_pi((double)(N - k) * w);
+            if (a.table) { f1 *= a.table[k]; f2 *= a.table[N - k]; }
+            double2 X1 = cscale(rfft_bin(lds, N, a.T2, k), f1);
+            double2 X2 = cscale(rfft_bin(lds, N, a.T2, N - k), f2);
+            if (k == 0) { X1.y = 0.0; X2.y = 0.0; }   // DC and Nyquist: real parts only
+            Xk[i] = X1;
+            Xn[i] = X2;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < KMAX; ++i) {
+        const int k = threadIdx.x + i * kBlock;
+        if (k < N) lds[k] = irfft_prebin(Xk[i], Xn[i], a.T2[k]);
+    }
+    __syncthreads();
+    lds_fft_n<MX>(lds, N, a.T, true);
+    const double sc = 1.0 / (double)N;
+    double2 *o = reinterpret_cast<double2 *>(a.out) + row * (int64_t)N;
+    for (int j = threadIdx.x; j < N; j += kBlock) o[j] = cscale(lds[j], sc);
+}
+
+// ===========================================================================
 // k_noise: get_noise_PS per row
 // ===========================================================================
 template <bool MX>
@@ -1794,6 +1844,21 @@ hipError_t launch_rotate(const RotateArgs &a, int64_t nrows, hipStream_t st) {
         case 4: MXL(mx, k_rotate, 4, g, b, lds, st, a); break;
         case 8: MXL(mx, k_rotate, 8, g, b, lds, st, a); break;
         case 16: MXL(mx, k_rotate, 16, g, b, lds, st, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+hipError_t launch_inst_resp(const InstRespArgs &a, int64_t nrows, hipStream_t st) {
+    const int N = a.nbin / 2;                // even nbin (checked by the caller)
+    size_t lds = (size_t)N * sizeof(double2);
+    dim3 g((unsigned)nrows), b(kBlock);
+    const bool mx = !is_pow2(N);
+    switch (kmax_pow2(N)) {
+        case 1: MXL(mx, k_inst_resp, 1, g, b, lds, st, a); break;
+        case 2: MXL(mx, k_inst_resp, 2, g, b, lds, st, a); break;
+        case 4: MXL(mx, k_inst_resp, 4, g, b, lds, st, a); break;
+        case 8: MXL(mx, k_inst_resp, 8, g, b, lds, st, a); break;
+        case 16: MXL(mx, k_inst_resp, 16, g, b, lds, st, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

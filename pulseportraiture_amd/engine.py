@@ -517,6 +517,56 @@ def rotate_rows(rows, phases, dev=None, ref_len=False):
     return out.reshape(tuple(shape[:-1]) + (nout,))
 
 
+def inst_response_len_ok(nbin):
+    """Row lengths ppf_inst_response_batch takes: even, 32..8192."""
+    return nbin % 2 == 0 and 32 <= nbin <= 8192
+
+
+def inst_response_rows(src, src_row, table, widths, dev=None):
+    """out[r] = irfft(rfft(src[src_row[r]]) * table * sinc(k widths[r])) on the
+    device (ppf_inst_response_batch, k_inst_resp): the instrumental response
+    of pptoaslib.instrumental_response_port_FT on template rows.  src
+    [nsrc, nbin] (array or device tensor, taken as float64); src_row [nrows]
+    indices into src (checked here: the kernel trusts them); table
+    [nbin // 2 + 1] or None (all ones); widths [nrows] in rotations.  Returns
+    a float64 device tensor [nrows, nbin].  Odd nbin and nbin > 8192 raise
+    NotImplementedError."""
+    dev = device(dev)
+    s = to_dev(src, dev, torch.float64)
+    if s.dim() != 2:
+        raise ValueError("src must be [nsrc, nbin]")
+    nsrc, nbin = s.shape
+    idx = np.ascontiguousarray(src_row, dtype=np.int32).reshape(-1)
+    w = np.ascontiguousarray(widths, dtype=np.float64).reshape(-1)
+    if w.size != idx.size:
+        raise ValueError("need one width per output row")
+    if idx.size and (idx.min() < 0 or idx.max() >= nsrc):
+        raise ValueError("src_row out of range")
+    if table is not None:
+        table = np.ascontiguousarray(table, dtype=np.float64).reshape(-1)
+        if table.size != nbin // 2 + 1:
+            raise ValueError("table must hold nbin // 2 + 1 harmonics")
+    if not inst_response_len_ok(nbin):
+        raise NotImplementedError(
+            "instrumental response at nbin = %d: even nbin from 32 to 8192 "
+            "only" % nbin)
+    out = torch.empty((idx.size, nbin), dtype=torch.float64, device=dev)
+    if not idx.size:
+        return out
+    # the small arrays in one staged upload
+    items = [(idx, torch.int32), (w, torch.float64)]
+    if table is not None:
+        items.append((table, torch.float64))
+    staged = _stage_host(items, dev)
+    ctx = _lib.context(dev.index)
+    rc = _lib.load().ppf_inst_response_batch(
+        ctx, idx.size, nbin, _p(s), _p(staged[0]),
+        None if table is None else _p(staged[2]), _p(staged[1]), _p(out),
+        _stream(dev))
+    _lib.check(rc, ctx)
+    return out
+
+
 def align_accum(data, phases, weights, out, wsum, dev=None):
     """ppalign accumulation on the device (ppf_align_accum):
     out[n] += sum_s w[s,n] rotate(data[s,n], phases[s,n]); wsum[n] += sum_s

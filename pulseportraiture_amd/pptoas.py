@@ -326,6 +326,26 @@ _ATTRS = ["obs", "doppler_fs", "nu0s", "nu_fits", "nu_refs", "ok_idatafiles",
           "zap_channels"]
 
 
+def _response_table(ird, nbin):
+    """The constant-width factors of the instrumental response dictionary as
+    one real table [nbin // 2 + 1] (None without wids), after the refusals
+    of the response path, all on the host.  Odd nbin: the reference's
+    length-less irfft (pptoas.py:433) turns the model into nbin - 1 bins,
+    then fitted against nbin-bin data; the batched fit takes one nbin for
+    both (as for the scattered .gmodel, _base_models).  nbin > 8192: past
+    the block LDS transform of ppf_inst_response_batch."""
+    if nbin % 2:
+        raise NotImplementedError(
+            "instrumental response at odd nbin = %d: the reference fits an "
+            "nbin - 1 bin model there" % nbin)
+    if not engine.inst_response_len_ok(nbin):
+        raise NotImplementedError(
+            "instrumental response at nbin = %d: rows of 32 to 8192 bins "
+            "only" % nbin)
+    return _pptl.instrumental_response_table(nbin, ird["wids"],
+                                             ird["irf_types"])
+
+
 class GetTOAs(object):
     """pptoas.py:87-159."""
 
@@ -356,6 +376,62 @@ class GetTOAs(object):
         in ONE ppf_gauss_portrait_batch launch (k_gauss_port)."""
         if self.is_FITS_model:
             raise NotImplementedError("FITS (archive) templates need PSRCHIVE")
+        respond = self._response_on()
+        if respond:
+            # refusals (odd or long nbin, bad widths) before any device work
+            table = _response_table(self.ird, len(d.phases))
+        models, index = self._base_models(d, ok_isubs, fit_scat, quiet)
+        if respond and len(index):
+            models, index = self._respond(d, ok_isubs, models, index, table)
+        if host and isinstance(models, torch.Tensor):
+            models = models.cpu().numpy()
+        return models, index
+
+    def _response_on(self):
+        """add_instrumental_response with a non-trivial response dictionary
+        (pptoas.py:428-429)."""
+        return bool(getattr(self, "add_instrumental_response", False) and
+                    (self.ird["DM"] or len(self.ird["wids"])))
+
+    def _respond(self, d, ok_isubs, models, index, table):
+        """The instrumental response on the archive's template portraits
+        (pptoas.py:428-434, 983-989): modelx = irfft(resp rfft(modelx)) with
+        resp = instrumental_response_port_FT(nbin, freqsx, DM, P, wids,
+        irf_types) of the sub-int's usable channels.  The response of a
+        channel depends on the sub-int only through P and chan_bw =
+        |freqsx[1] - freqsx[0]| (it doubles when channel 1 is zapped), so
+        every distinct (portrait, P, chan_bw) of the archive is built in ONE
+        ppf_inst_response_batch launch (k_inst_resp) and model_index
+        remapped; the unusable channels get a response too, and are masked in
+        the fit.  Fewer than two usable channels with DM raise the
+        reference's IndexError."""
+        nchan, nbin = models.shape[-2], models.shape[-1]
+        DM = self.ird["DM"]
+        cache, src_row, widths, new_index = {}, [], [], []
+        for j, isub in enumerate(ok_isubs):
+            key = (int(index[j]),)
+            if DM:
+                freqsx = np.asarray(d.freqs[isub])[
+                    np.asarray(d.ok_ichans[isub], dtype=int)]
+                chan_bw = abs(freqsx[1] - freqsx[0])
+                key += (float(d.Ps[isub]), float(chan_bw))
+            if key not in cache:
+                cache[key] = len(cache)
+                src_row.append(int(index[j]) * nchan + np.arange(nchan))
+                widths.append(
+                    _pptl.dispersive_smearing_widths(
+                        d.freqs[isub], DM, d.Ps[isub], chan_bw) if DM
+                    else np.zeros(nchan))
+            new_index.append(cache[key])
+        out = engine.inst_response_rows(
+            models.reshape(-1, nbin), np.concatenate(src_row), table,
+            np.concatenate(widths))
+        return out.view(len(cache), nchan, nbin), \
+            np.array(new_index, dtype=np.int32)
+
+    def _base_models(self, d, ok_isubs, fit_scat, quiet):
+        """_models before the instrumental response: device portraits (host
+        arrays when there is no sub-int) and their per-sub-int index."""
         # within one get_TOAs call the template file is read once and an
         # archive whose portraits (frequency sets, TAU) equal an earlier
         # archive's reuses that archive's device portraits: the same
@@ -370,7 +446,7 @@ class GetTOAs(object):
         except (UnboundLocalError, UnicodeDecodeError):
             # a make_spline_model template (pptoas.py:416-419): one device
             # portrait per distinct frequency set, unscattered
-            return self._spline_models(d, ok_isubs, host)
+            return self._spline_models(d, ok_isubs)
         if fit_scat:
             (self.model_code, self.model_nu_ref, self.gparams,
              self.alpha) = code, nu_ref, gparams, alpha
@@ -414,10 +490,9 @@ class GetTOAs(object):
                 mc["model"] = (self.model_name, code, nu_ref, self.ngauss,
                                gparams, _mff, alpha, _mfa)
             mc[ck] = models
-        return (models.cpu().numpy() if host else models,
-                np.array(index, dtype=np.int32))
+        return models, np.array(index, dtype=np.int32)
 
-    def _spline_models(self, d, ok_isubs, host=True):
+    def _spline_models(self, d, ok_isubs):
         """read_spline_model(modelfile, freqs, nbin) per sub-integration
         (pptoas.py:416-419), the distinct frequency sets of the archive in
         ONE ppf_spline_portrait_batch launch."""
@@ -437,8 +512,7 @@ class GetTOAs(object):
                 np.zeros(0, dtype=np.int32)
         models = engine.spline_portraits(mean_prof, eigvec, tck,
                                          np.stack(freqs), nbin)
-        return (models.cpu().numpy() if host else models,
-                np.array(index, dtype=np.int32))
+        return models, np.array(index, dtype=np.int32)
 
     def get_TOAs(self, datafile=None, tscrunch=False, nu_refs=None, DM0=None,
                  bary=True, fit_DM=True, fit_GM=False, fit_scat=False,
@@ -455,8 +529,10 @@ class GetTOAs(object):
                                       "path (SURVEY.md section 2, row 20)")
         if add_instrumental_response and (self.ird["DM"] or
                                           len(self.ird["wids"])):
-            raise NotImplementedError("instrumental response (SURVEY.md row "
-                                      "19) is not on the accelerated path")
+            # refuse a response that cannot be served before any archive is
+            # loaded (zero width, unknown type, too wide a 'gauss')
+            _pptl.instrumental_response_table(64, self.ird["wids"],
+                                              self.ird["irf_types"])
         if method not in ("trust-ncg", "Newton-CG", "TNC"):
             print("Method '%s' is not implemented." % method)
             raise SystemExit
@@ -1455,8 +1531,10 @@ class GetTOAs(object):
                             "scattering branch is incomplete)")
         if add_instrumental_response and (self.ird["DM"] or
                                           len(self.ird["wids"])):
-            raise NotImplementedError("instrumental response (SURVEY.md row "
-                                      "19) is not on the accelerated path")
+            # refuse a response that cannot be served before any archive is
+            # loaded (zero width, unknown type, too wide a 'gauss')
+            _pptl.instrumental_response_table(64, self.ird["wids"],
+                                              self.ird["irf_types"])
         print("You are using an experimental functionality of pptoas!")
         self._mcache = {}   # template portraits of this call (_models)
         self.nfit = 1
@@ -1655,10 +1733,33 @@ class GetTOAs(object):
         depend only on the channel frequencies and are cached per archive."""
         if self.is_FITS_model:
             raise NotImplementedError("FITS (archive) templates need PSRCHIVE")
-        if self.add_instrumental_response and \
-                (self.ird["DM"] or len(self.ird["wids"])):
-            raise NotImplementedError("instrumental response (SURVEY.md row "
-                                      "19) is not on the accelerated path")
+        if not self._response_on():
+            return self._plain_fit_model(data, ifile, isub, quiet, cache)
+        # pptoas.py:1446-1452: the response of ALL the channels' freqs and
+        # this sub-int's P, here on the scattered portrait: the reference
+        # applies it before the scattering kernel, and the two multipliers
+        # commute
+        table = _response_table(self.ird, data.nbin)
+        DM = self.ird["DM"]
+        freqs = np.asarray(data.freqs[isub], dtype=float)
+        P = data.Ps[isub]
+        chan_bw = abs(freqs[1] - freqs[0]) if DM else 0.0
+        rkey = ("irf", freqs.tobytes(), float(P) if DM else 0.0)
+        cached = self.taus[ifile][isub] == 0.0 and cache is not None
+        if cached and rkey in cache:
+            return cache[rkey]
+        model_name, model = self._plain_fit_model(data, ifile, isub, quiet,
+                                                  cache)
+        model = engine.inst_response_rows(
+            np.asarray(model, dtype=float), np.arange(len(freqs)), table,
+            _pptl.dispersive_smearing_widths(freqs, DM, P, chan_bw)
+        ).cpu().numpy()
+        if cached:
+            cache[rkey] = (model_name, model)
+        return model_name, model
+
+    def _plain_fit_model(self, data, ifile, isub, quiet, cache=None):
+        """_fit_model before the instrumental response."""
         freqs = data.freqs[isub]
         tau = self.taus[ifile][isub]
         key = freqs.tobytes()

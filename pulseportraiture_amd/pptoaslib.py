@@ -58,6 +58,97 @@ def DMc_from_GM(GM, D, a_perp):
     return (GM * (2.0 * a_perp * (4.8e-9) ** 2) / (c * D)) ** 0.5
 
 
+# widest 'gauss' response [rot] served: up to here the reference's factor is
+# the plain Gaussian to rounding (see instrumental_response_FT)
+GAUSS_IRF_MAX_WID = 0.1
+
+
+def instrumental_response_FT(nbin, wid=0.0, irf_type='rect'):
+    """pptoaslib.py:124-155: the Fourier transform [nbin // 2 + 1] of one
+    instrumental response of width wid [rot]: the width of the rectangle
+    ('rect') or the FWHM of the Gaussian ('gauss').
+
+    'rect' is np.sinc(k wid), as in the reference.  'gauss' is the closed
+    form exp(-(pi k wid)**2 / (4 ln 2)): the reference's
+    gaussian_profile_FT(nbin, 0, wid, 1) / [0] (pplib.py:1229-1263) is
+    exp(-b**2) Re erf(a + i b) normalised at k = 0, which equals the plain
+    Gaussian to 4e-16 for wid <= 0.12 and departs from it above (8e-15 at
+    0.15, 1.5e-4 and overflow artefacts at 0.3); so 0 < wid <=
+    GAUSS_IRF_MAX_WID = 0.1 is served and a wider 'gauss' raises
+    NotImplementedError.
+
+    wid == 0.0 returns None, as the reference does (its `inst_resp_FT` is
+    never returned, pptoaslib.py:143-144).  An unknown irf_type raises
+    ValueError; the reference prints a message and returns 0 (which silently
+    zeroes the model it multiplies)."""
+    nharm = nbin // 2 + 1
+    if wid == 0.0:
+        return None
+    if irf_type == 'rect':
+        return np.sinc(np.arange(nharm) * wid)
+    if irf_type == 'gauss':
+        if not abs(wid) <= GAUSS_IRF_MAX_WID:
+            raise NotImplementedError(
+                "'gauss' instrumental response of FWHM %g rot: only widths "
+                "up to %g rot are supported (beyond, the reference's erf "
+                "formula is no longer a Gaussian)" % (wid, GAUSS_IRF_MAX_WID))
+        return np.exp(-(np.pi * np.arange(nharm) * wid) ** 2 /
+                      (4.0 * np.log(2.0)))
+    raise ValueError("Unrecognized instrumental response function type '%s'."
+                     % irf_type)
+
+
+def instrumental_response_table(nbin, wids=[], irf_types=[]):
+    """The product [nbin // 2 + 1] of the constant-width factors of
+    instrumental_response_port_FT (pptoaslib.py:183-185), real, in the
+    reference's order; None without any.  A width of exactly 0 raises
+    TypeError (the reference multiplies by None there)."""
+    table = None
+    for wid, irf_type in zip(wids, irf_types):
+        f = instrumental_response_FT(nbin, wid, irf_type)
+        if f is None:
+            raise TypeError("instrumental response width 0.0: the reference "
+                            "multiplies by None (pptoaslib.py:143-144, 184)")
+        table = f if table is None else table * f
+    return table
+
+
+def dispersive_smearing_widths(freqs, DM, P, chan_bw):
+    """pptoaslib.py:189: the per-channel width [rot] of the 'rect' response
+    of dispersive smearing across a channel of chan_bw [MHz]."""
+    if not DM:
+        return np.zeros(len(freqs))
+    # scalar arithmetic per channel, as the reference's loop (an array power
+    # may round differently from the scalar one)
+    return np.array([8.3e-6 * chan_bw / (np.float64(f) / 1e3) ** 3 / P
+                     for f in freqs])
+
+
+def instrumental_response_port_FT(nbin, freqs, DM=0.0, P=1.0, wids=[],
+                                  irf_types=[]):
+    """pptoaslib.py:158-192: the combined instrumental responses
+    [nchan, nbin // 2 + 1]: one factor per entry of wids / irf_types
+    (instrumental_response_FT) and, if DM is non-zero, a per-channel 'rect' of
+    width 8.3e-6 chan_bw / (nu / 1e3)**3 / P with chan_bw = |freqs[1] -
+    freqs[0]|.  Ones (float) when DM == 0 and wids is empty, else complex
+    with zero imaginary part, as the reference returns.  A zero width raises
+    TypeError, an unknown type ValueError, 'gauss' above GAUSS_IRF_MAX_WID
+    NotImplementedError; fewer than two freqs with DM raise IndexError."""
+    nharm = nbin // 2 + 1
+    nchan = len(freqs)
+    if DM == len(wids) == 0.0:
+        return np.ones([nchan, nharm])
+    out = np.ones([nchan, nharm], dtype=np.complex128)
+    for wid, irf_type in zip(wids, irf_types):
+        f = instrumental_response_table(nbin, [wid], [irf_type])
+        out *= f
+    if DM:
+        chan_bw = abs(freqs[1] - freqs[0])
+        w = dispersive_smearing_widths(freqs, DM, P, chan_bw)
+        out *= np.sinc(np.arange(nharm) * w[:, None])
+    return out
+
+
 def rotate_portrait_full(port, phi, DM, GM, freqs, nu_DM=np.inf,
                          nu_GM=np.inf, P=None):
     """pptoaslib.py:61-90: per-channel phase on the host, rotation on the
