@@ -136,9 +136,6 @@ int twiddles(ppf_ctx *ctx, int nbin, hipStream_t st, const double2 **T, const do
 // with the stream synchronisation as the fallback after 2 s.  Opt-in: on
 // GetTOAs' threaded host pipeline the polling cost 20 % of the PSRFITS rate
 // even yielding the core (profiles/r06/ab_gtspin_status.txt).
-#ifndef PPF_SPIN_WAIT
-#define PPF_SPIN_WAIT 1
-#endif
 constexpr unsigned kUnset = 0xFFFFFFFFu;
 int read_back(ppf_ctx *ctx, unsigned *host, const unsigned *dev, int n, hipStream_t st, bool spin) {
     volatile unsigned *h = host;
@@ -146,7 +143,7 @@ int read_back(ppf_ctx *ctx, unsigned *host, const unsigned *dev, int n, hipStrea
     std::atomic_thread_fence(std::memory_order_seq_cst);
     hipError_t e = hipMemcpyAsync(host, dev, n * sizeof(unsigned), hipMemcpyDeviceToHost, st);
     if (e != hipSuccess) return hip_fail(ctx, e, "hipMemcpyAsync");
-    if (PPF_SPIN_WAIT && spin) {
+    if (spin) {
         const auto t0 = std::chrono::steady_clock::now();
         for (;;) {
             bool done = true;
@@ -173,11 +170,8 @@ int read_back(ppf_ctx *ctx, unsigned *host, const unsigned *dev, int n, hipStrea
 // (Round 6, first build: P was taken >= 2K - 1 = 1025, i.e. 2048, which
 // cz_fft refuses, so the A/B of ab_czc4_status.txt ran the direct sums on
 // both sides.)
-#ifndef PPF_GUESS_CZ
-#define PPF_GUESS_CZ 1
-#endif
 bool cz_plan(int Ns, int K, ppf::CzPlan &c) {
-    if (!PPF_GUESS_CZ || Ns < 2 * ppf::kBlock || K < 2) return false;
+    if (Ns < 2 * ppf::kBlock || K < 2) return false;
     // P >= K + J - 1 with chunks of J >= 256 outputs (nbin 1024: K = 513,
     // P = 1024, two chunks of 512)
     int P = 64;
@@ -208,12 +202,6 @@ int cz_tables(ppf_ctx *ctx, const ppf::CzPlan &c, hipStream_t st, const double2 
     return PPF_OK;
 }
 
-// 16-moment sets on the non-power-of-two shapes too (their moments always
-// come from X): nbin 1000 278-280k -> 293-294k, 1536 178-179k -> 183k fits/s
-// in one call (profiles/r05/ab_m16_status.txt)
-#ifndef PPF_MOM16_BLOCK
-#define PPF_MOM16_BLOCK 1
-#endif
 struct FitLayout {
     size_t M, X, chan, stats, x0, gP, gw, nuref, Msum, gpart, gwx, gflag, state, partials, active, mom, dphi,
         mres, hcen, Mpow, MP, KC, needx, xslot, xtile, rclist, Bt, total;
@@ -232,12 +220,14 @@ struct FitLayout {
 
 // 16 moments about each wave's band centre where the moments come from a
 // stored X and that was measured to pay (ab_m16_status.txt): the wave
-// shapes' MOM_X path and (PPF_MOM16_BLOCK) the non-power-of-two nbin.
+// shapes' MOM_X path and the non-power-of-two nbin, whose moments always
+// come from X (round 5's PPF_MOM16_BLOCK: nbin 1000 278-280k -> 293-294k,
+// 1536 178-179k -> 183k fits/s in one call).
 // Power-of-two nbin off the wave shapes (32-128, 4096, 8192) and block sizes
 // the wave kernels refuse keep 32 moments about the global centre (radius
 // 4.5 instead of 0.73, so fewer re-centring passes).
 static bool mom16_layout(const FitLayout &L, int nbin) {
-    return L.momx || (!L.fused && PPF_MOM16_BLOCK && !ppf::is_pow2(ppf::rfft_len(nbin)));
+    return L.momx || (!L.fused && !ppf::is_pow2(ppf::rfft_len(nbin)));
 }
 
 
@@ -666,12 +656,10 @@ int ppf_fit_batch(ppf_ctx *ctx, const ppf_fit_desc *d, void *stream) {
     // k_xspec_w: channel-block-major (mode 2) when the model spectra
     // outgrow the L2s, sub-int-major otherwise; k_xmom_g stages its model
     // row in LDS per workgroup and keeps mode 1
-#ifndef PPF_XSPEC_ORDER2_BYTES
-#define PPF_XSPEC_ORDER2_BYTES (32ll << 20)
-#endif
+    constexpr long long kOrder2Bytes = 32ll << 20;
     const long long model_bytes = (long long)d->nchan * (d->nbin / 2 + 1) * 16;
     const int xcd1 = (L.nblk % 8 == 0) ? 1 : 0;
-    xa.xcd_swizzle = (xcd1 && model_bytes > PPF_XSPEC_ORDER2_BYTES) ? 2 : xcd1;
+    xa.xcd_swizzle = (xcd1 && model_bytes > kOrder2Bytes) ? 2 : xcd1;
     xa.data = d->data; xa.Mft = Mft; xa.model_index = d->model_index; xa.mask = d->chan_mask;
     xa.errs = d->errs; xa.freqs = d->freqs; xa.P = d->P; xa.T = T; xa.T2 = T2;
     xa.X = (double2 *)(ws + L.X); xa.chan = (double *)(ws + L.chan);

@@ -33,16 +33,10 @@ __host__ __device__ __forceinline__ double2 cmk(double r, double i) {
 // do not evict what IS re-read from the XCD's L2 (model rows, |M|^2, twiddle
 // and moment tables).  C2: k_xspec_w2 24.09 vs 24.83 ms per 10k, 302.4k vs
 // 294.3k fits/s; C3 / C5 +1-2 % (profiles/r06/ab_nt_status.txt).
-#ifndef PPF_NT
-#define PPF_NT 1
-#endif
+// A plain-load build measured slower and the switch was removed.
 template <typename T>
 __device__ __forceinline__ T ld_stream(const T *p) {
-#if PPF_NT
     return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
 }
 __device__ __forceinline__ float2 ld_stream(const float2 *p) {
     typedef float v2 __attribute__((ext_vector_type(2)));
@@ -55,12 +49,8 @@ __device__ __forceinline__ double2 ld_stream(const double2 *p) {
     return cmk(v.x, v.y);
 }
 __device__ __forceinline__ void st_stream(double2 *p, double2 v) {
-#if PPF_NT
     typedef double v2 __attribute__((ext_vector_type(2)));
     __builtin_nontemporal_store(v2{v.x, v.y}, reinterpret_cast<v2 *>(p));
-#else
-    *p = v;
-#endif
 }
 __device__ __forceinline__ double2 cadd(double2 a, double2 b) { return cmk(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ double2 csub(double2 a, double2 b) { return cmk(a.x - b.x, a.y - b.y); }
@@ -135,18 +125,6 @@ __device__ __forceinline__ double2 scat_recip(double b) {
     return cmk(r / d, -1.0 / d);
 }
 
-#ifdef PPF_SHFL_REDUCE
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    return v;
-}
-#else
 __device__ __forceinline__ double wave_sum(double v) {
     return wave_reduce(v, [](double x, double y) { return x + y; });
 }
@@ -154,7 +132,6 @@ __device__ __forceinline__ double wave_sum(double v) {
 __device__ __forceinline__ double wave_max(double v) {
     return wave_reduce(v, [](double x, double y) { return fmax(x, y); });
 }
-#endif
 
 // wave-uniform copies of a double held by the first / a given lane
 __device__ __forceinline__ double readfirst_d(double v) {

@@ -470,12 +470,7 @@ __device__ double brute_fmin(const double2 *xm, int nharm, double inv_err2, int 
                              bool grid_done = false) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const double step = (Ns != 1) ? (hi - lo) / (double)(Ns - 1) : 1.0;
-#ifndef PPF_GUESS_DIAG
-#define PPF_GUESS_DIAG 0    // timing-only builds: 1 no brute grid, 2 no polish
-#endif
-    if (PPF_GUESS_DIAG & 1) {
-        for (int j = threadIdx.x; j < Ns; j += kBlock) sh[j] = (double)j;
-    } else if (grid_done) {
+    if (grid_done) {
     } else if (Ns >= 2 * kBlock) {
         // large grids (ppalign: Ns = nbin): one point per lane, two points
         // in flight; harmonics broadcast from LDS, phasor e^{2 pi i k ph} by
@@ -523,7 +518,7 @@ __device__ double brute_fmin(const double2 *xm, int nharm, double inv_err2, int 
         double f1 = wave_fps_eval(xm, nharm, sim1, inv_err2); ++nf;
         if (f1 < f0) { double t = sim0; sim0 = sim1; sim1 = t; t = f0; f0 = f1; f1 = t; }
         int iters = 1;
-        while (!(PPF_GUESS_DIAG & 2) && nf < 200 && iters < 200) {
+        while (nf < 200 && iters < 200) {
             if (fabs(sim1 - sim0) <= 1e-4 && fabs(f0 - f1) <= 1e-4) break;
             double xbar = sim0;
             double xr = 2.0 * xbar - sim1;
@@ -680,12 +675,9 @@ __global__ __launch_bounds__(64) void k_nu_ref(DsumArgs a) {
 // the row loop.  The four waves' sums are added in wave order through LDS
 // (deterministic) and the block's partial profile is written once.
 // ===========================================================================
-// rows in flight per wave (1: the one being summed has a successor loading;
-// 2 measured slower: C5 k_dsum_w 9.25 vs 8.39 ms per 500 sub-ints, the
-// extra VGPRs cost occupancy)
-#ifndef PPF_DSUM_DEPTH
-#define PPF_DSUM_DEPTH 1
-#endif
+// One row in flight per wave (the one being summed has a successor loading;
+// two measured slower: C5 k_dsum_w 9.25 vs 8.39 ms per 500 sub-ints, the
+// extra VGPRs cost occupancy).
 template <int DT, int LOG2NB>
 // (capped at four waves per SIMD -- 128 VGPRs, nine spills -- it measured
 // 8.2 vs 7.1 ms per 10,000 C2 sub-ints)
@@ -732,60 +724,6 @@ __global__ __launch_bounds__(kBlock) void k_dsum_w(DsumArgs a) {
 #pragma unroll
     for (int j = 0; j < J; ++j) acc[j] = 0.0;
     double wsum = 0.0, wcnt = 0.0;
-#if PPF_DSUM_DEPTH >= 2
-    // two rows in flight per wave: the row being summed comes from one
-    // register buffer while the next two are loading (the second buffer and
-    // the refill of the first)
-    auto next_usable = [&](int m) {
-        m += kWaves;
-        while (m < c1 && !usable(m)) m += kWaves;
-        return m;
-    };
-    auto load = [&](VecT (&p)[NL], int m) {
-        // unconditional (a valid row when past the block): keeps p in VGPRs
-        const VecT *src = rows + (int64_t)(m < c1 ? m : c1 - 1) * (NB / VW);
-#pragma unroll
-        for (int i = 0; i < NL; ++i) p[i] = ld_stream(src + lane + 64 * i);
-    };
-    auto row = [&](VecT (&p)[NL], int m, int m2) {
-        wave_lds_sync();                      // the previous row's reads are issued
-#pragma unroll
-        for (int i = 0; i < NL; ++i) reinterpret_cast<VecT *>(xs)[lane + 64 * i] = p[i];
-        load(p, m2);
-        const int r = m - c0;
-        const double w = readlane_d(r < 64 ? t_w[0] : t_w[1], r & 63),
-                     f0 = readlane_d(r < 64 ? t_f[0] : t_f[1], r & 63);
-        const double tau = Dg * (1.0 / (f0 * f0) - nu_mean_m2);
-        const double fl = floor(tau), f = tau - fl;
-        const int i0 = (int)(fl - (double)NB * floor(fl / (double)NB));   // mod nbin
-        const double wa = w * (1.0 - f), wb = w * f;
-        wave_lds_sync();
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-            const int ia = (lane + 64 * j + i0) & (NB - 1);
-            acc[j] = fma(wa, (double)xs[ia], fma(wb, (double)xs[(ia + 1) & (NB - 1)], acc[j]));
-        }
-        wsum += w;
-        wcnt += 1.0;
-    };
-    int n = c0 + wave;
-    while (n < c1 && !usable(n)) n += kWaves;
-    int n1 = next_usable(n);
-    VecT pa[NL], pb[NL];
-    load(pa, n);
-    load(pb, n1);
-    while (n < c1) {
-        int n2 = next_usable(n1);
-        row(pa, n, n2);                       // pa: n -> n2
-        n = n1;
-        n1 = n2;
-        if (n >= c1) break;
-        n2 = next_usable(n1);
-        row(pb, n, n2);                       // pb: n -> the row after n1
-        n = n1;
-        n1 = n2;
-    }
-#else
     int n = c0 + wave;
     while (n < c1 && !usable(n)) n += kWaves;
     VecT pre[NL];
@@ -824,7 +762,6 @@ __global__ __launch_bounds__(kBlock) void k_dsum_w(DsumArgs a) {
         wcnt += 1.0;
         n = nn;
     }
-#endif
     // fixed-order sum of the four waves' profiles (LDS reused as NB doubles)
     __syncthreads();
     double *part = dlds;
@@ -966,15 +903,7 @@ __global__ __launch_bounds__(kBlock) void k_dsum_wn(DsumArgs a) {
 // ===========================================================================
 // the block-partial sums of k_guess (fixed order, so bit-identical either
 // way) unrolled 8 deep: their loads independent, in flight together instead
-// of one latency each (PPF_GUESS_UNROLL 0: as through round 6's first builds)
-#ifndef PPF_GUESS_UNROLL
-#define PPF_GUESS_UNROLL 1
-#endif
-#if PPF_GUESS_UNROLL
-#define PPF_GU _Pragma("unroll 8")
-#else
-#define PPF_GU _Pragma("unroll 1")
-#endif
+// of one latency each (round 6)
 template <bool MX, int CZL = 0, bool GS = false>
 __global__ __launch_bounds__(kBlock) void k_guess(GuessArgs a) {
     // lds: z[max(rfft_len, czP)] (packed profile, FFT in place; then the
@@ -995,14 +924,14 @@ __global__ __launch_bounds__(kBlock) void k_guess(GuessArgs a) {
     if (tid == 0) {
         double w0 = 0.0, w1 = 0.0, w2 = 0.0;
         if (fused) {
-            PPF_GU
+#pragma unroll 8
             for (int b = 0; b < a.nblk; ++b) {
                 w0 += a.gwx[((int64_t)s * a.nblk + b) * 3 + 0];
                 w1 += a.gwx[((int64_t)s * a.nblk + b) * 3 + 1];
                 w2 += a.gwx[((int64_t)s * a.nblk + b) * 3 + 2];
             }
         } else {
-            PPF_GU
+#pragma unroll 8
             for (int b = 0; b < a.nblkd; ++b) {
                 w0 += a.gw[((int64_t)s * a.nblkd + b) * 2 + 0];
                 w1 += a.gw[((int64_t)s * a.nblkd + b) * 2 + 1];
@@ -1016,13 +945,13 @@ __global__ __launch_bounds__(kBlock) void k_guess(GuessArgs a) {
         // (odd nbin: z_j = p_j)
         for (int j = tid; odd && j < a.nbin; j += kBlock) {
             double pj = 0.0;
-            PPF_GU
+#pragma unroll 8
             for (int b = 0; b < a.nblkd; ++b) pj += a.gP[((int64_t)s * a.nblkd + b) * a.nbin + j];
             z[j] = cmk(pj, 0.0);
         }
         for (int j = tid; !odd && j < N; j += kBlock) {
             double pe = 0.0, po = 0.0;
-            PPF_GU
+#pragma unroll 8
             for (int b = 0; b < a.nblkd; ++b) {
                 const double *pp = a.gP + ((int64_t)s * a.nblkd + b) * a.nbin;
                 pe += pp[2 * j];
@@ -1038,7 +967,7 @@ __global__ __launch_bounds__(kBlock) void k_guess(GuessArgs a) {
     auto fused_bin = [&](int k) {
         double2 r = cmk(0.0, 0.0);
         if (k >= 1 && k < NL) {
-            PPF_GU
+#pragma unroll 8
             for (int b = 0; b < a.nblk; ++b) r = cadd(r, a.gpart[((int64_t)s * a.nblk + b) * NL + k]);
         }
         return r;
@@ -1098,9 +1027,8 @@ __global__ __launch_bounds__(kBlock) void k_guess(GuessArgs a) {
     // fused: the profile's expected noise, sqrt(sum w^2 errs_FT^2) / W
     const double err = fused ? sqrt(sh[2]) / wsum : sig * sqrt((double)a.nbin / 2.0);
     if constexpr (CZL > 0) {
-        if (!(PPF_GUESS_DIAG & 1))
-            cz_grid<CZL>(xm, (int)kmx[0], 1.0 / (err * err), a.Ns, -0.5, sh, z, a.czB, a.czT, a.czJ, a.czQ,
-                         a.czK);
+        cz_grid<CZL>(xm, (int)kmx[0], 1.0 / (err * err), a.Ns, -0.5, sh, z, a.czB, a.czT, a.czJ, a.czQ,
+                     a.czK);
     }
     const double phase = brute_fmin(xm, (int)kmx[0], 1.0 / (err * err), a.Ns, -0.5, 0.5, sh, nullptr,
                                     nullptr, CZL > 0);
@@ -1677,11 +1605,8 @@ hipError_t launch_xspec(const XspecArgs &a, hipStream_t st) {
         case 11: launch_xspec_t<11>(a, st); break;
         case 12: launch_xspec_t<12>(a, st); break;
         case 0: {      // nbin / 2 not a power of two
-#ifndef PPF_XSPEC_WM
-#define PPF_XSPEC_WM 1
-#endif
             // wave per row (k_xspec_wm) up to N = 1024; the block kernel above
-            if (PPF_XSPEC_WM && xspec_wm_supported(a.nbin) && a.cb <= 64) return launch_xspec_wm(a, st);
+            if (xspec_wm_supported(a.nbin) && a.cb <= 64) return launch_xspec_wm(a, st);
             dim3 g((unsigned)((int64_t)a.nsub * a.nblk)), b(kBlock);
             const size_t lds = (size_t)rfft_len(a.nbin) * sizeof(double2);
             if (a.dtype == 0) hipLaunchKernelGGL((k_xspec_any<0>), g, b, lds, st, a);
@@ -1693,10 +1618,6 @@ hipError_t launch_xspec(const XspecArgs &a, hipStream_t st) {
     return hipGetLastError();
 }
 bool dsum_wave_supported(int nbin) { return nbin >= 256 && nbin <= 2048 && is_pow2(nbin); }
-// k_dsum_wn for the other nbin <= 2048 (0: the block kernel k_dsum)
-#ifndef PPF_DSUM_WN
-#define PPF_DSUM_WN 1
-#endif
 
 template <int DT, int L2>
 static void launch_dsum_w(const DsumArgs &a, hipStream_t st) {
@@ -1707,14 +1628,10 @@ static void launch_dsum_w(const DsumArgs &a, hipStream_t st) {
                        lds, st, a);
 }
 
-#ifndef PPF_NUREF
-#define PPF_NUREF 1
-#endif
 hipError_t launch_dsum(const DsumArgs &a_in, hipStream_t st) {
     DsumArgs a = a_in;
     // many channels: nu_ref once per sub-int (the wave-per-row kernels read it)
-    if (PPF_NUREF && a.nuref && a.nchan >= 2048 && a.nbin <= 2048 &&
-        (dsum_wave_supported(a.nbin) || PPF_DSUM_WN)) {
+    if (a.nuref && a.nchan >= 2048 && a.nbin <= 2048) {
         hipLaunchKernelGGL(k_nu_ref, dim3((unsigned)a.nsub), dim3(64), 0, st, a);
     } else {
         a.nuref = nullptr;
@@ -1734,8 +1651,8 @@ hipError_t launch_dsum(const DsumArgs &a_in, hipStream_t st) {
         return hipGetLastError();
     }
     dim3 g((unsigned)((int64_t)a.nsub * a.nblkd)), b(kBlock);
-    if (PPF_DSUM_WN && a.nbin <= 2048 && a.cbd <= 128) {
-        // wave-per-row pass at any nbin (k_dsum_wn), NBMAX 1024 or 2048
+    if (a.nbin <= 2048 && a.cbd <= 128) {
+        // wave-per-row pass at the other nbin <= 2048 (k_dsum_wn), NBMAX 1024 or 2048
         const int nbm = a.nbin <= 1024 ? 1024 : 2048;
         const size_t row = (size_t)kWaves * nbm * (a.dtype == 0 ? 4 : 8);
         const size_t lds = row > (size_t)nbm * 8 ? row : (size_t)nbm * 8;

@@ -26,18 +26,6 @@
 
 namespace ppf {
 
-// Newton trust region also for the moment-expansion fits (phase / DM / GM
-// without scattering; C4: 1.04 instead of 2.34 data passes per fit);
-// 0 builds them with scipy's trust-ncg path only
-#ifndef PPF_NEWTON_MOM
-#define PPF_NEWTON_MOM 1
-#endif
-// channel-subset warm start of the Newton scattering fits (0: every
-// evaluation on every channel)
-#ifndef PPF_NEWTON_SUBSET
-#define PPF_NEWTON_SUBSET 1
-#endif
-
 // ===========================================================================
 // per-channel likelihood terms (pptoaslib.py:195-561)
 // stats: 0 C, 1 C', 2 C'', 3 Q1, 4 Q1', 5 Q2, 6 S, 7 S1, 8 S2a, 9 S2b
@@ -223,9 +211,6 @@ hipError_t launch_gflag(int nsub, int nchan, const uint8_t *needx, const int32_t
     return hipGetLastError();
 }
 
-#ifndef PPF_TRINIT_ZERO
-#define PPF_TRINIT_ZERO 0   // 1: k_tr_init zeroes the moment fits' stats slots
-#endif
 // ===========================================================================
 // k_tr_init: one wave per sub-integration (4 per workgroup)
 // ===========================================================================
@@ -284,14 +269,15 @@ __global__ __launch_bounds__(kBlock) void k_tr_init(SolveArgs a) {
         for (int i = 0; i < 5; ++i) { S.x[i] = x[i]; S.th[i] = x[i]; S.g[i] = 0.0; }
         S.f = 0.0;
         for (int i = 0; i < 15; ++i) S.H[i] = 0.0;
-        // scattering fits without bounds take the Newton trust region
-        // (tr_update_newton) unless the caller asked for scipy's path
-        S.newton = (a.newton && (scat || PPF_NEWTON_MOM) && !bnd) ? 1 : 0;
+        // fits without bounds take the Newton trust region (tr_update_newton)
+        // unless the caller asked for scipy's path; the moment-expansion
+        // fits (no scattering) too: C4 1.04 instead of 2.34 data passes per fit
+        S.newton = (a.newton && !bnd) ? 1 : 0;
         S.radius = S.newton ? kNewtonR0 : 1.0;   // scipy initial_trust_radius = 1
         // channel-subset warm start of the scattering fits (every sub-th
-        // group of 64 channels, at least two groups; PPF_NEWTON_SUBSET)
+        // group of 64 channels, at least two groups)
         int sub = 1;
-        if (PPF_NEWTON_SUBSET && S.newton && scat) {
+        if (S.newton && scat) {
             const int ng = (a.nchan + 63) / 64;
             while (sub * 2 <= kSubsetMaxStride && sub * 2 <= ng / 2) sub *= 2;
         }
@@ -349,19 +335,13 @@ __global__ __launch_bounds__(kBlock) void k_tr_init(SolveArgs a) {
         const double P = a.P[s];
         const double nuDM2 = pow(nu_fit[0], -2.0), nuGM4 = pow(nu_fit[1], -4.0);
         double *dp = a.dphi + (int64_t)s * a.nchan * 2;
-        double *st = a.stats + (int64_t)s * 2 * a.nchan * 10;
+        // S_n (stats slot 6) is stored with C, C', C'' by k_tr_mom, and (round
+        // 6) the scattering slots' zeros with them: zeroing both stats slots
+        // here wrote nsub x nchan x 160 B (840 MB, 0.3 ms at C2)
         for (int n = lane; n < a.nchan; n += 64) {
             const double nu = fr[n];
             dp[2 * n + 0] = kDconst * (pow(nu, -2.0) - nuDM2) / P;
             dp[2 * n + 1] = kDconst * kDconst * (pow(nu, -4.0) - nuGM4) / P;
-            // S_n (slot 6) is stored with C, C', C'' by k_tr_mom, and (round
-            // 6) the scattering slots' zeros with them: zeroing both slots
-            // here wrote nsub x nchan x 160 B (840 MB, 0.3 ms at C2)
-            if (PPF_TRINIT_ZERO)
-                for (int q = 0; q < 2; ++q) {
-                    double *d = st + ((int64_t)q * a.nchan + n) * 10;
-                    for (int j = 0; j < 10; ++j) d[j] = 0.0;
-                }
         }
     }
 }
@@ -377,17 +357,8 @@ __global__ __launch_bounds__(kBlock) void k_tr_init(SolveArgs a) {
 // ===========================================================================
 constexpr int kPassChans = kBlock;             // channels per workgroup
 
-#ifndef PPF_PASS_WPE
-#define PPF_PASS_WPE 3
-#endif
-#ifndef PPF_PASS_SPLIT
-#define PPF_PASS_SPLIT 1
-#endif
-#ifndef PPF_PASS_NT
-#define PPF_PASS_NT PPF_NT
-#endif
 template <bool SCAT>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_PASS_WPE))) void k_pass(SolveArgs a) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) void k_pass(SolveArgs a) {
     __shared__ double red[kWaves * 21];
     const int nblk = (a.nchan + kPassChans - 1) / kPassChans;
     // channel-block-major order: the workgroups resident together share one
@@ -434,7 +405,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_PASS
     // split its harmonics (split: workgroup-uniform), so a subset pass is not
     // one wave's serial harmonic loop per 256 channels while the other three
     // idle (C5: 16 of 256 groups per sub-int)
-    const bool split = PPF_PASS_SPLIT && S.sub >= kWaves;
+    const bool split = S.sub >= kWaves;
     const int n = blk * kPassChans + (split ? lane : (int)threadIdx.x);
     const bool in_sub = S.sub <= 1 || ((n >> 6) % S.sub) == 0;
     const bool use_n = in_sub && n < a.nchan && (!mask || mask[n]);
@@ -477,13 +448,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_PASS
         // harmonics in groups of KB: the next group's loads are issued before
         // the current group is summed (software pipeline, one memory wait per
         // group)
-#ifndef PPF_PASS_KB
-// harmonics per load group.  Round 6: 3 instead of 4 -- at three waves per
-// SIMD the 4-harmonic body spilled 40 B (168 VGPRs), the 3-harmonic one
-// fits in 154: C3 +0.8 %, C5 +2 % (profiles/r06/ab_kb_status.txt)
-#define PPF_PASS_KB 3
-#endif
-        constexpr int KB = PPF_PASS_KB;
+        // harmonics per load group.  Round 6: 3 instead of 4 -- at three
+        // waves per SIMD the 4-harmonic body spilled 40 B (168 VGPRs), the
+        // 3-harmonic one fits in 154: C3 +0.8 %, C5 +2 %
+        // (profiles/r06/ab_kb_status.txt)
+        constexpr int KB = 3;
         // two buffers, loads one group ahead of the sums.  The loop is
         // unrolled by two so each buffer keeps its registers (rotating them
         // with moves would make each iteration wait for all its loads).
@@ -496,12 +465,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_PASS
 #pragma unroll
             for (int u = 0; u < KB; ++u) {
                 const int k = min(kb + u, kend - 1);
-#if PPF_PASS_NT
                 // X streamed past the L2, which keeps |M|^2 (ld_stream)
                 xo[u] = ld_stream(Xc + k * xs);
-#else
-                xo[u] = Xc[k * xs];
-#endif
                 if (SCAT) po[u] = Pc[k * xs];
             }
         };
@@ -1020,12 +985,8 @@ __device__ __forceinline__ double tree_sum64(const double *p, int nblk, int stri
 // sub-int, follows.  It pays where there are many narrow sub-ints (C3, 10k
 // x 512 channels: 68.4-70.2 vs 71.3-71.7 ms per step) and not for a few wide
 // ones (C5, 500 x 16384: 87.5-88.2 vs 83.6-85.3 ms; 8 waves on the chip and
-// 64 block partials per lane), tools/g33.sh.  PPF_TRSTEP_LANE: 1 = by shape
-// (nsub >= 2048 and nchan <= 2048; default), 2 = always (the whole GPU suite
-// passed so), 0 = never.
-#ifndef PPF_TRSTEP_LANE
-#define PPF_TRSTEP_LANE 1
-#endif
+// 64 block partials per lane), so launch_tr_step picks it by shape: nsub >=
+// 2048 and nchan <= 2048.
 template <bool BOX>
 __global__ __launch_bounds__(64) void k_tr_step_l(SolveArgs a) {
     extern __shared__ __attribute__((aligned(16))) double tsl[];
@@ -1099,13 +1060,10 @@ constexpr double kX24 = 2.3;
 // 16 moments (mom16): x^14 / 14! < 1.6e-13 for |x| <= 0.73, with x = 2 pi h_n
 // Delta and h_n the centre of the channel band's harmonics (k_moments)
 constexpr double kX16 = 0.73;
-// fewer of the 16 (k_tr_mom, PPF_TRMOM_ADAPT): x^10 / 10! and x^6 / 6! <
+// fewer of the 16 (k_tr_mom): x^10 / 10! and x^6 / 6! <
 // 1.6e-13 for |x| <= 0.2368 (12 moments) and 0.0220 (8)
 constexpr double kX12 = 0.2368;
 constexpr double kX8 = 0.0220;
-#ifndef PPF_TRMOM_ADAPT
-#define PPF_TRMOM_ADAPT 1
-#endif
 constexpr int kMomChans = 64;                    // channels per k_moments workgroup
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
@@ -1113,9 +1071,6 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 // MFMA f64 16x16x4: A = Y (16 channels x 4 harmonics; one wave = 16
 // channels), B = u^m (4 harmonics x 16 moments), two B tiles (m < 16, m >=
 // 16) and separate real / imaginary A.  The harmonic sum is the MFMA K loop.
-#ifndef PPF_MOM_WPE
-#define PPF_MOM_WPE 3
-#endif
 // (measured, C2 per 10k sub-ints, same call: KU = 8 6.12 vs 5.76 ms; the
 // loop unrolled by two over two buffers, so that no batch waits for loads it
 // has just issued, 5.77 at KU = 4 and 5.91 at KU = 2: no latency to hide.
@@ -1126,20 +1081,14 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 // not kept.  The same one-round-trip prologue for k_pass, and unconditional
 // loads in the scattering-gate and k_tr_init channel loops, measured within
 // the noise at C3 / C5 (profiles/r05/ab_ps1_status.txt, ab_gt1_status.txt))
-#ifndef PPF_MOM_KU
-#define PPF_MOM_KU 4
-#endif
-// PPF_MOM_ILP (round 6, measured and not kept): the batch's phasors from
-// its base phasor and two accumulator pairs -- k_moments 5.83 vs 5.72-5.76
-// ms per 10k at C2 (profiles/r06/ab_r6a_status.txt): the kernel is not
-// bound by its dependency chains, and the 164 VGPRs cost a wave per SIMD
-#ifndef PPF_MOM_ILP
-#define PPF_MOM_ILP 0
-#endif
+// Round 6, measured and removed: the batch's phasors from its base phasor
+// and two accumulator pairs -- k_moments 5.83 vs 5.72-5.76 ms per 10k at C2
+// (profiles/r06/ab_r6a_status.txt): the kernel is not bound by its
+// dependency chains, and the 164 VGPRs cost a wave per SIMD
 // M16: the call's moment count (a.mom16: 16 on the moments-from-X path, 32
 // otherwise), a template argument so the MFMA loop carries no branch
 template <bool M16>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_MOM_WPE))) void k_moments(SolveArgs a) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) void k_moments(SolveArgs a) {
     const int nblk = (a.nchan + kMomChans - 1) / kMomChans;
     const int s = blockIdx.x / nblk, blk = blockIdx.x % nblk;
     const TRState &S = a.state[s];
@@ -1191,22 +1140,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_MOM_
     double2 E = cmk(1.0, 0.0);
     // batches of 4 K-steps (16 harmonics), software-pipelined: the next
     // batch's loads are in flight while this one's MFMAs run
-    constexpr int KU = PPF_MOM_KU;
-#if PPF_MOM_ILP
-    // Round 6: no serial chains through a batch.  The K-step phasors are
-    // Eb W4^t from the batch's base phasor Eb (one product each, all
-    // independent; Eb itself advances by W4^KU once per batch), and the
-    // m < 16 contraction runs on two accumulator pairs (even / odd K-steps,
-    // summed at the end), so consecutive MFMAs do not wait for each other:
-    // the kernel waited on instruction dependencies 63 % of its wave cycles
-    // (profiles/r05/sq_c2_r5a.txt) at half the HBM rate
-    double2 Wt[KU];
-    Wt[0] = cmk(1.0, 0.0);
-#pragma unroll
-    for (int t = 1; t < KU; ++t) Wt[t] = cmul(Wt[t - 1], W4);
-    const double2 WB = cmul(Wt[KU - 1], W4);
-    f64x4 dre0b = dre0, dim0b = dre0;
-#endif
+    constexpr int KU = 4;
     double2 xa[KU], xb[KU];
     // The loads are unconditional (clamped to a valid harmonic; values past
     // the cutoff or of a masked channel are replaced by 0 after the load):
@@ -1252,24 +1186,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_MOM_
     };
     auto keep = [&](int k) { return valid && k < kend; };
     auto mm = [&](const double2 (&xv)[KU], int kb, auto tl) {
-#if PPF_MOM_ILP
-        // base phasor of the batch (k = kb + kk), re-seeded exactly every
-        // 64 harmonics (kb is a multiple of 4 KU)
-        if ((kb & 63) == 0) E = cexp2pi((double)(kb + kk) * phin);
-        else E = cmul(E, WB);
-#endif
 #pragma unroll
         for (int t = 0; t < KU; ++t) {
             const int k = kb + 4 * t + kk;
-#if PPF_MOM_ILP
-            const double2 Et = t == 0 ? E : cmul(E, Wt[t]);
-#else
             // phasor by recurrence, re-seeded exactly every 64 harmonics
             // (kb is a multiple of 16: only t = 0 can re-seed)
             if (t == 0 && (kb & 63) == 0) E = cexp2pi((double)k * phin);
             else E = cmul(E, W4);
             const double2 Et = E;
-#endif
             double2 xt;
             if constexpr (decltype(tl)::value) xt = opt(xv, t);
             else xt = xv[t];
@@ -1279,17 +1203,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_MOM_
             const double u2 = u * u, u4 = u2 * u2, u8 = u4 * u4, u16 = u8 * u8;
             const double uj = ((ci & 1) ? u : 1.0) * ((ci & 2) ? u2 : 1.0) *
                               ((ci & 4) ? u4 : 1.0) * ((ci & 8) ? u8 : 1.0);
-#if PPF_MOM_ILP
-            // (32 moments: dre1 / dim1 already make four chains)
-            if (m16 && (t & 1)) {
-                dre0b = __builtin_amdgcn_mfma_f64_16x16x4f64(y.x, uj, dre0b, 0, 0, 0);
-                dim0b = __builtin_amdgcn_mfma_f64_16x16x4f64(y.y, uj, dim0b, 0, 0, 0);
-            } else
-#endif
-            {
-                dre0 = __builtin_amdgcn_mfma_f64_16x16x4f64(y.x, uj, dre0, 0, 0, 0);
-                dim0 = __builtin_amdgcn_mfma_f64_16x16x4f64(y.y, uj, dim0, 0, 0, 0);
-            }
+            dre0 = __builtin_amdgcn_mfma_f64_16x16x4f64(y.x, uj, dre0, 0, 0, 0);
+            dim0 = __builtin_amdgcn_mfma_f64_16x16x4f64(y.y, uj, dim0, 0, 0, 0);
             if constexpr (!m16) {
                 const double ujh = uj * u16;
                 dre1 = __builtin_amdgcn_mfma_f64_16x16x4f64(y.x, ujh, dre1, 0, 0, 0);
@@ -1315,15 +1230,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPF_MOM_
     };
     if (tiled) run(std::true_type{});                  // (uniform)
     else run(std::false_type{});
-#if PPF_MOM_ILP
-    if constexpr (m16) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            dre0[r] += dre0b[r];
-            dim0[r] += dim0b[r];
-        }
-    }
-#endif
     // D[row][col]: col = lane & 15 = moment, row = (lane >> 4) + 4 r = channel
     double2 *M = a.mom + ((int64_t)s * 2 + q) * a.nchan * kMoments;
 #pragma unroll
@@ -1376,9 +1282,6 @@ __device__ __forceinline__ void taylor_seg(const double2 (&mu)[SZ], double x, do
     }
 }
 
-#ifndef PPF_TRMOM_WPE
-#define PPF_TRMOM_WPE 2
-#endif
 #ifdef PPF_TM_PROF
 // section cycle counters of k_tr_mom, thread 0 of each workgroup (profiling
 // builds only: tools/tprof.py)
@@ -1399,7 +1302,7 @@ __device__ unsigned long long g_tprof[8];
 // flight while the current half is summed), a fixed-order block reduction
 // of f, g, H and the scipy trust-ncg update on thread 0.
 template <int TB>
-__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(PPF_TRMOM_WPE))) void k_tr_mom(SolveArgs a) {
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(2))) void k_tr_mom(SolveArgs a) {
     __shared__ TRState L;
     __shared__ double red[kWaves * 10];
     __shared__ int cmdb;
@@ -1511,7 +1414,6 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(PPF_TRMOM_WP
             c_ok = mk[n];
         };
         const bool q4 = !m16 && xsel > kX24;   // uniform: all 32 moments needed
-#if PPF_TRMOM_ADAPT
         // mom16 (round 6): only the moments the step needs.  The second
         // derivative's series truncated after M moments errs by at most
         // x^(M-2) / (M-2)! of sum |Y| (|u| <= 1), so with x = max_n 2 pi h_n
@@ -1526,10 +1428,6 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(PPF_TRMOM_WP
 #pragma unroll
             for (int m = 0; m < 4; ++m) b[m] = p[m];
         };
-#else
-        constexpr int mq = 2;
-        auto ldq4 = [&](int, double2 (&)[KQ]) {};
-#endif
         ldq(0, 0, qa);
         ldc(0);
         for (int i = 0; i < nit; ++i) {
@@ -1571,7 +1469,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(PPF_TRMOM_WP
             const double C = F.x, Cp = -kTwoPi * K1.y, Cpp = -kTwoPi * kTwoPi * K2.x;
             double *sn = st + (int64_t)n * 10;
             sn[0] = C; sn[1] = Cp; sn[2] = Cpp; sn[6] = Sn;
-            if (!PPF_TRINIT_ZERO) sn[3] = sn[4] = sn[5] = sn[7] = sn[8] = sn[9] = 0.0;
+            sn[3] = sn[4] = sn[5] = sn[7] = sn[8] = sn[9] = 0.0;
             const double iS = 1.0 / Sn;
             const double dph[3] = {1.0, d1, d2};
             const double hn = -2.0 * (C * Cpp + Cp * Cp) * iS;
@@ -1599,11 +1497,7 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(PPF_TRMOM_WP
 #pragma unroll
             for (int e = 0; e < 6; ++e) o[6 + uidx(hi[e], hj[e])] = acc[4 + e];
             L.meval = qsel;
-#if PPF_NEWTON_MOM
             cmdb = L.newton ? tr_update_newton_n<3>(L, o, a.max_iter) : tr_update<3>(L, o, a.max_iter);
-#else
-            cmdb = tr_update<3>(L, o, a.max_iter);
-#endif
         }
         TP(4);
         __syncthreads();
@@ -1729,20 +1623,14 @@ __device__ __noinline__ void nz_solve(const double *c, int nzcase, int option, d
     *no_root_out = no_root ? 1 : 0;
 }
 
-#ifdef PPF_POSTFIT_WPE
-#define PPF_POSTFIT_ATTR __attribute__((amdgpu_waves_per_eu(PPF_POSTFIT_WPE)))
-#else
-#define PPF_POSTFIT_ATTR
-#endif
 // PB threads per sub-int.  64 (one wave) lets four sub-ints share a CU at
 // the kernel's one wave per SIMD, so the serial parts (the zero-covariance
 // root finding, the covariance inversion by thread 0) of four sub-ints
 // overlap instead of one: C2 264.0k -> 269.6k fits/s, C3 73.8-74.3 ->
 // 71.7-71.9 ms per step in one call (tools/g27.sh).  Wide sub-ints keep 256
 // (C5, 16384 channels in 500 sub-ints: 85.0-86.0 vs 86.2-86.7 ms with 64).
-// PPF_POSTFIT_PB forces one of them.
 template <int PB>
-__global__ __launch_bounds__(PB) PPF_POSTFIT_ATTR void k_postfit(SolveArgs a) {
+__global__ __launch_bounds__(PB) void k_postfit(SolveArgs a) {
     __shared__ double red[kWaves * 32];
     __shared__ double sh_Xinv[25];
     __shared__ double sh_misc[16];
@@ -2103,7 +1991,7 @@ hipError_t launch_pass(const SolveArgs &a, hipStream_t st) {
 
 hipError_t launch_tr_step(const SolveArgs &a, hipStream_t st) {
     const dim3 g((unsigned)((a.nsub + kWaves - 1) / kWaves));
-    const bool lane = PPF_TRSTEP_LANE == 2 || (PPF_TRSTEP_LANE == 1 && a.nsub >= 2048 && a.nchan <= 2048);
+    const bool lane = a.nsub >= 2048 && a.nchan <= 2048;   // many narrow sub-ints: k_tr_step_l
     if (lane) {
         const dim3 gl((unsigned)((a.nsub + 63) / 64));
         const size_t lds = 64 * sizeof(TRState);
@@ -2151,11 +2039,8 @@ hipError_t launch_tr_mom(const SolveArgs &a, hipStream_t st) {
     // updates overlap other workgroups' evaluation passes): C2 k_tr_mom 163
     // vs 171 ms per 120 calls, C4 332.8-338.6k vs 322.7-330.6k
     // archive-iterations/s in one call (profiles/r05/ab_tb1_status.txt)
-#ifdef PPF_TRMOM_TB
-    const int tb = PPF_TRMOM_TB;
-#else
+    // (the 64- and 256-thread instantiations are still compiled, not launched)
     const int tb = 128;
-#endif
     if (tb == 64) hipLaunchKernelGGL(k_tr_mom<64>, dim3((unsigned)a.nsub), dim3(64), 0, st, a);
     else if (tb == 128) hipLaunchKernelGGL(k_tr_mom<128>, dim3((unsigned)a.nsub), dim3(128), 0, st, a);
     else hipLaunchKernelGGL(k_tr_mom<256>, dim3((unsigned)a.nsub), dim3(256), 0, st, a);
@@ -2163,11 +2048,7 @@ hipError_t launch_tr_mom(const SolveArgs &a, hipStream_t st) {
 }
 
 hipError_t launch_postfit(const SolveArgs &a, hipStream_t st) {
-#ifdef PPF_POSTFIT_PB
-    const int pb = PPF_POSTFIT_PB;
-#else
     const int pb = a.nchan <= 2048 ? 64 : 256;
-#endif
     // (128 threads measured slower in round 5: C2 285.3-286.5k vs 287.6-288.2k, C3
     // 145.0-146.5k vs 147.7-148.1k, profiles/r05/ab_pf1_status.txt)
     if (pb == 64) hipLaunchKernelGGL(k_postfit<64>, dim3((unsigned)a.nsub), dim3(64), 0, st, a);

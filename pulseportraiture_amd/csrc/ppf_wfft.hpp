@@ -126,45 +126,31 @@ struct Plan {
     static constexpr int toff(int s) { return L(s) - L2; }
 };
 
-// Element idx -> LDS slot.  Default: the padding above.  PPF_LDS_XOR=1: slot
-// = idx ^ ((idx >> SH) & MK), a permutation inside aligned blocks, no padding.
-// Priced with MI355X_MICROARCH.md's LDS lane groups (tools/lds_conflicts.py),
-// the XOR map cuts the extra bank-conflict cycles of a 1024-point row from
-// 2.25 to 0.75 per ds_*_b128 (the padding moves lanes 16-31 of a
-// ds_read_b128 group one slot onto lanes 0-15's banks) and makes the
-// eight-channel write-out of k_xspec_w conflict-free.  Measured on MI355X
-// (89 GPU tests green with it): C3 unchanged, k_xmom_g 3% slower (31.8 vs
-// 30.8 ms; the kernels are f64-issue bound, not LDS bound), C5 7% slower (k_xspec_w<9> needs 136
-// VGPRs instead of 124: three waves per SIMD instead of four).  Kept off.
-#ifndef PPF_LDS_XOR
-#define PPF_LDS_XOR 0
-#endif
-template <int LOG2N>
-__host__ __device__ constexpr bool use_xor() { return PPF_LDS_XOR != 0; }
+// Element idx -> LDS slot: the padding above.  An XOR slot map (idx ^ ((idx
+// >> SH) & MK), no padding) has fewer bank conflicts on paper
+// (tools/lds_conflicts.py: 0.75 vs 2.25 extra cycles per ds_*_b128 at 1024
+// points) but measured slower on MI355X (the kernels are f64-issue bound, not
+// LDS bound: k_xmom_g 31.8 vs 30.8 ms, C5 7 % slower from 136 vs 124 VGPRs in
+// k_xspec_w<9>) and was removed.
 template <int LOG2N>
 struct Swz {
-    static constexpr int SH = LOG2N == 7 ? 2 : (LOG2N == 10 ? 4 : 3);
-    static constexpr int MK = LOG2N == 7 ? 3 : 7;
     // offsets that are multiples of FREE commute with the map
-    static constexpr int FREE = use_xor<LOG2N>() ? (MK + 1) << SH : 1 << Plan<LOG2N>::S;
+    static constexpr int FREE = 1 << Plan<LOG2N>::S;
 };
 template <int LOG2N>
 __device__ __forceinline__ constexpr int pad(int idx) {
-    if constexpr (use_xor<LOG2N>()) return idx ^ ((idx >> Swz<LOG2N>::SH) & Swz<LOG2N>::MK);
-    else return idx + (idx >> Plan<LOG2N>::S);
+    return idx + (idx >> Plan<LOG2N>::S);
 }
 // pad(a + C) given pad(a), for a compile-time C that is a multiple of FREE
 template <int LOG2N, int C>
 __device__ __forceinline__ int pad_add(int pa) {
     static_assert(C % Swz<LOG2N>::FREE == 0, "offset must commute with the slot map");
-    if constexpr (use_xor<LOG2N>()) return pa + C;
-    else return pa + C + (C >> Plan<LOG2N>::S);
+    return pa + C + (C >> Plan<LOG2N>::S);
 }
 // LDS slots of one wave buffer
 template <int LOG2N>
 __host__ __device__ constexpr int buf_slots() {
-    if constexpr (use_xor<LOG2N>()) return Plan<LOG2N>::N;
-    else return Plan<LOG2N>::N + (Plan<LOG2N>::N >> Plan<LOG2N>::S);
+    return Plan<LOG2N>::N + (Plan<LOG2N>::N >> Plan<LOG2N>::S);
 }
 // slot of element lane + C, C a compile-time multiple of 64: one of two
 // lane bases (lb[0] = pad(lane), lb[1] = pad(lane + 64) - 64) plus a constant
@@ -231,7 +217,7 @@ __device__ __forceinline__ void stage(double2 *buf, const double2 *__restrict__ 
         if constexpr (L % Swz<LOG2N>::FREE == 0) {
             const int ob = pad<LOG2N>(o);
 #pragma unroll
-            for (int q = 0; q < rad; ++q) buf[ob + q * L + (use_xor<LOG2N>() ? 0 : (q * L) >> P::S)] = v[b][q];
+            for (int q = 0; q < rad; ++q) buf[ob + q * L + ((q * L) >> P::S)] = v[b][q];
         } else {
 #pragma unroll
             for (int q = 0; q < rad; ++q) buf[pad<LOG2N>(o + q * L)] = v[b][q];
@@ -256,143 +242,13 @@ __device__ __forceinline__ void fft_row(double2 (&x)[Plan<LOG2N>::R], double2 *b
     constexpr int R = P::R;
     dft<R>(x);
     wave_sync();
-    // stage 0 output: o = lane R + q (L = 1, k = 0).  Padding: pad(lane R +
-    // q) = pad(lane R) + q (q < R <= 2^S).  XOR map: the lane's R outputs are
-    // permuted inside their block, slot = lane R + (q ^ f_lane) when R <=
-    // 2^SH, else computed per element
-    if constexpr (use_xor<LOG2N>()) {
+    // stage 0 output: o = lane R + q (L = 1, k = 0): pad(lane R + q) =
+    // pad(lane R) + q (q < R <= 2^S)
+    const int ob = pad<LOG2N>(lane * R);
 #pragma unroll
-        for (int q = 0; q < R; ++q) buf[pad<LOG2N>(lane * R + q)] = x[q];
-    } else {
-        const int ob = pad<LOG2N>(lane * R);
-#pragma unroll
-        for (int q = 0; q < R; ++q) buf[ob + q] = x[q];
-    }
+    for (int q = 0; q < R; ++q) buf[ob + q] = x[q];
     wave_sync();
     stages_from<LOG2N, 1>(buf, T, lane);
-}
-
-// ---------------------------------------------------------------------------
-// Half-buffer variant (round-4 prototype, k_noise_h): the same stages and
-// arithmetic as fft_row, but each exchange goes through a buffer of doubles
-// (the padded slot map of the complex buffer, 8 B per slot) in two sweeps,
-// real parts then imaginary parts.  Half the LDS per wave (8.7 KB at 1024
-// points instead of 17.4 KB), so the LDS no longer caps a CU at two waves
-// per SIMD; the results are bit-identical to fft_row (only the exchange
-// differs).  hb: the wave's buffer_slots<LOG2N>() doubles.
-template <int LOG2N, int ST, int B, int Q, int PART>
-__device__ __forceinline__ void hstage_read_q(const double *hb, const int (&lb)[2],
-                                              double2 (&v)[Plan<LOG2N>::N / Plan<LOG2N>::radix(ST) / 64][Plan<LOG2N>::radix(ST)]) {
-    using P = Plan<LOG2N>;
-    constexpr int rad = P::radix(ST), NB = P::N / rad;
-    if constexpr (Q < rad) {
-        const double t = hb[lane_slot<LOG2N, 64 * B + Q * NB>(lb)];
-        if constexpr (PART == 0) v[B][Q].x = t;
-        else v[B][Q].y = t;
-        hstage_read_q<LOG2N, ST, B, Q + 1, PART>(hb, lb, v);
-    }
-}
-template <int LOG2N, int ST, int B, int PART>
-__device__ __forceinline__ void hstage_read(const double *hb, const int (&lb)[2],
-                                            double2 (&v)[Plan<LOG2N>::N / Plan<LOG2N>::radix(ST) / 64][Plan<LOG2N>::radix(ST)]) {
-    using P = Plan<LOG2N>;
-    constexpr int rad = P::radix(ST), NB = P::N / rad, BPL = NB / 64;
-    if constexpr (B < BPL) {
-        hstage_read_q<LOG2N, ST, B, 0, PART>(hb, lb, v);
-        hstage_read<LOG2N, ST, B + 1, PART>(hb, lb, v);
-    }
-}
-// write the stage outputs v (PART of each) to their slots
-template <int LOG2N, int ST, int PART>
-__device__ __forceinline__ void hstage_write(double *hb, int lane,
-                                             const double2 (&v)[Plan<LOG2N>::N / Plan<LOG2N>::radix(ST) / 64][Plan<LOG2N>::radix(ST)]) {
-    using P = Plan<LOG2N>;
-    constexpr int N = P::N, rad = P::radix(ST), L = P::L(ST);
-    constexpr int NB = N / rad, BPL = NB / 64;
-#pragma unroll
-    for (int b = 0; b < BPL; ++b) {
-        const int j = lane + 64 * b, k = j & (L - 1);
-        const int o = (j - k) * rad + k;
-#pragma unroll
-        for (int q = 0; q < rad; ++q) {
-            const double t = PART == 0 ? v[b][q].x : v[b][q].y;
-            if constexpr (L % Swz<LOG2N>::FREE == 0)
-                hb[pad<LOG2N>(o) + q * L + (use_xor<LOG2N>() ? 0 : (q * L) >> P::S)] = t;
-            else
-                hb[pad<LOG2N>(o + q * L)] = t;
-        }
-    }
-}
-// stage ST >= 1 whose inputs are the previous stage's outputs vp (still in
-// registers): exchange them through hb (two sweeps), twiddle, DFT; the
-// outputs stay in v
-template <int LOG2N, int ST, int PST>
-__device__ __forceinline__ void hstage(double *hb, const double2 *__restrict__ T, int lane,
-                                       const double2 (&vp)[Plan<LOG2N>::N / Plan<LOG2N>::radix(PST) / 64][Plan<LOG2N>::radix(PST)],
-                                       double2 (&v)[Plan<LOG2N>::N / Plan<LOG2N>::radix(ST) / 64][Plan<LOG2N>::radix(ST)]) {
-    using P = Plan<LOG2N>;
-    constexpr int N = P::N, rad = P::radix(ST), L = P::L(ST);
-    constexpr int NB = N / rad, BPL = NB / 64, TS = N / (rad * L);
-    const int lb[2] = {pad<LOG2N>(lane), pad<LOG2N>(lane + 64) - 64};
-    hstage_write<LOG2N, PST, 0>(hb, lane, vp);
-    wave_sync();
-    hstage_read<LOG2N, ST, 0, 0>(hb, lb, v);
-    wave_sync();
-    hstage_write<LOG2N, PST, 1>(hb, lane, vp);
-    wave_sync();
-    hstage_read<LOG2N, ST, 0, 1>(hb, lb, v);
-    wave_sync();
-#pragma unroll
-    for (int b = 0; b < BPL; ++b) {
-        const int j = lane + 64 * b, k = j & (L - 1);
-        const double2 w1 = T[k * TS];
-        double2 wq = w1;
-        v[b][1] = cmul(v[b][1], w1);
-#pragma unroll
-        for (int q = 2; q < rad; ++q) {
-            wq = cmul(wq, w1);
-            v[b][q] = cmul(v[b][q], wq);
-        }
-        dft<rad>(v[b]);
-    }
-}
-// the whole transform from registers x (stage-0 inputs, as fft_row) to the
-// last stage's outputs in registers (vl: [N / radix(NST-1) / 64][radix]),
-// written nowhere: the caller reads them out through hb (hwrite_last)
-template <int LOG2N, int ST>
-struct HBlk {
-    using P = Plan<LOG2N>;
-    using T = double2[P::N / P::radix(ST) / 64][P::radix(ST)];
-};
-template <int LOG2N, int ST>
-__device__ __forceinline__ void hstages_from(double *hb, const double2 *__restrict__ T, int lane,
-                                             const typename HBlk<LOG2N, ST - 1>::T &vp,
-                                             typename HBlk<LOG2N, Plan<LOG2N>::NST - 1>::T &vl) {
-    if constexpr (ST == Plan<LOG2N>::NST - 1) {
-        hstage<LOG2N, ST, ST - 1>(hb, T, lane, vp, vl);
-    } else {
-        typename HBlk<LOG2N, ST>::T v;
-        hstage<LOG2N, ST, ST - 1>(hb, T, lane, vp, v);
-        hstages_from<LOG2N, ST + 1>(hb, T, lane, v, vl);
-    }
-}
-template <int LOG2N>
-__device__ __forceinline__ void fft_row_h(double2 (&x)[Plan<LOG2N>::R], double *hb,
-                                          const double2 *__restrict__ T, int lane,
-                                          typename HBlk<LOG2N, Plan<LOG2N>::NST - 1>::T &vl) {
-    using P = Plan<LOG2N>;
-    static_assert(P::NST >= 2, "half-buffer FFT: at least two stages");
-    dft<P::R>(x);
-    typename HBlk<LOG2N, 0>::T v0;
-#pragma unroll
-    for (int q = 0; q < P::R; ++q) v0[0][q] = x[q];
-    hstages_from<LOG2N, 1>(hb, T, lane, v0, vl);
-}
-// the last stage's outputs, PART (0: re, 1: im), to their natural-order slots
-template <int LOG2N, int PART>
-__device__ __forceinline__ void hwrite_last(double *hb, int lane,
-                                            const typename HBlk<LOG2N, Plan<LOG2N>::NST - 1>::T &vl) {
-    hstage_write<LOG2N, Plan<LOG2N>::NST - 1, PART>(hb, lane, vl);
 }
 
 }  // namespace wfft

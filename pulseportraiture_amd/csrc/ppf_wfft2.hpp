@@ -42,14 +42,7 @@ namespace wf2 {
 // scheduling fences between the sections (keeps the compiler from hoisting
 // a later section's twiddle arithmetic into an earlier one, which holds
 // dozens of extra VGPRs)
-#ifndef PPF_WF2_CUT
-#define PPF_WF2_CUT 1
-#endif
-#if PPF_WF2_CUT
 #define WF2_CUT() __builtin_amdgcn_sched_barrier(0)
-#else
-#define WF2_CUT()
-#endif
 
 constexpr int kN = 1024;
 constexpr int kXS = 65;                 // exchange row stride (complex slots)
@@ -143,22 +136,15 @@ __device__ __forceinline__ void dft16_group(double2 (&y)[16]) {
         dft16_group<LEN, I + LEN>(y);
     }
 }
-#ifndef PPF_WF2_FDFT
-#define PPF_WF2_FDFT 1
-#endif
 __device__ __forceinline__ void dft16(double2 (&x)[16]) {
-    if constexpr (PPF_WF2_FDFT == 0) {
-        wfft::dft<16>(x);
-    } else {
-        double2 y[16];
-        wfft::dft_perm<16, 0>(x, y);
-        dft16_group<2, 0>(y);
-        dft16_group<4, 0>(y);
-        dft16_group<8, 0>(y);
-        dft16_group<16, 0>(y);
+    double2 y[16];
+    wfft::dft_perm<16, 0>(x, y);
+    dft16_group<2, 0>(y);
+    dft16_group<4, 0>(y);
+    dft16_group<8, 0>(y);
+    dft16_group<16, 0>(y);
 #pragma unroll
-        for (int i = 0; i < 16; ++i) x[i] = y[i];
-    }
+    for (int i = 0; i < 16; ++i) x[i] = y[i];
 }
 
 // Sections A-C.  x: the row as above; xb: the wave's kXSlots exchange slots.

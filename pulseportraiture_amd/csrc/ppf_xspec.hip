@@ -49,35 +49,15 @@ constexpr int kXW = 8;                 // waves per k_align_part_w workgroup
 // write-out barrier holds 4 waves, not 8; C3 k_xspec_w 27.7 vs 29.2 ms),
 // 8 below (C5, 512-point rows: 29.8 vs 37.0 ms)
 template <int LOG2N>
-__host__ __device__ constexpr int xsw() {
-#ifdef PPF_XSPEC_WAVES
-    return PPF_XSPEC_WAVES;
-#else
-    return LOG2N == 10 ? 4 : 8;
-#endif
-}
+__host__ __device__ constexpr int xsw() { return LOG2N == 10 ? 4 : 8; }
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 // row elements as native vectors: arrays of HIP_vector_type structs carried
 // across the row loop are not promoted to VGPRs
 typedef float vf2 __attribute__((ext_vector_type(2)));
 typedef double vd2 __attribute__((ext_vector_type(2)));
 typedef float vf4 __attribute__((ext_vector_type(4)));
-#ifndef PPF_SCHED_CUT
-#define PPF_SCHED_CUT 1
-#endif
-#if PPF_SCHED_CUT
+// scheduling fence: nothing is moved across it
 #define SCHED_CUT() __builtin_amdgcn_sched_barrier(0)
-#else
-#define SCHED_CUT()
-#endif
-#ifndef PPF_XM_CUT
-#define PPF_XM_CUT 0
-#endif
-#if PPF_XM_CUT
-#define XM_CUT() __builtin_amdgcn_sched_barrier(0)
-#else
-#define XM_CUT()
-#endif
 
 // XCD-aware block -> (sub-int, channel block): blocks b and b+8 share an
 // XCD, so each XCD keeps only its channel blocks' model rows in its L2.
@@ -118,24 +98,19 @@ __device__ __forceinline__ void rfft_pair(const double2 *buf, int k, double2 w, 
 // ===========================================================================
 // k_xspec_w: cross spectrum X of the sub-ints that stream it
 // ===========================================================================
-// wave buffer + 2 side slots; with the XOR slot map the buffers start 4
-// slots apart mod 16, which makes the eight-channel write-out of k_xspec_w
-// conflict-free (tools/lds_conflicts.py)
 // largest FFT twiddle index + 1 used by wfft stages >= 1
 template <int LOG2N>
 __host__ __device__ constexpr int tw_slots() {
     using P = wfft::Plan<LOG2N>;
     return P::NST > 1 ? P::N / P::radix(P::NST - 1) : 1;
 }
-// Stage twiddles from an LDS copy (default) instead of the global table: the
+// The stage twiddles come from an LDS copy, not the global table: the
 // wave's next row is already in flight during the FFT, and vmcnt counts in
 // order, so a twiddle load issued after that prefetch would wait for it
 // (the s_waitcnt vmcnt(0) before every stage's first twiddle use).
-#ifndef PPF_TW_LDS
-#define PPF_TW_LDS 1
-#endif
+// wave buffer + 2 side slots
 template <int LOG2N>
-__host__ __device__ constexpr int xspec_slw() { return wfft::buf_slots<LOG2N>() + (wfft::use_xor<LOG2N>() ? 4 : 2); }
+__host__ __device__ constexpr int xspec_slw() { return wfft::buf_slots<LOG2N>() + 2; }
 
 // GS: the sub-ints with gflag set (k_gflag: every channel's harmonic cutoff
 // below NL = 64 guess_npl) also accumulate the GetTOAs guess spectrum
@@ -150,29 +125,18 @@ __host__ __device__ constexpr int xspec_slw() { return wfft::buf_slots<LOG2N>() 
 // err^2 = sum_n w_n^2 errs_FT,n^2 / W^2.
 // minimum waves per SIMD: at 1024 points the LDS admits two 4-wave
 // workgroups per CU (two waves per SIMD), and the fused-guess variant must
-// keep that register budget (<= 256)
-// PPF_GS9: the fused guess at 512 points as well (1: capped at four waves
-// per SIMD, spilling; 2: uncapped, two waves per SIMD; 0, default: those
-// shapes take k_dsum_w).  Measured (round 5, C5 per 500 sub-ints, one call):
-// C5's model reaches harmonic ~430 of 513, above the NL = 192 guess
-// harmonics, so k_gflag sets no sub-int and the GS=1 variant only costs its
-// registers: k_xspec_w<9> 26.5 vs 22.0 ms, 90.1 vs 84.7 ms per step.
-#ifndef PPF_GS9
-#define PPF_GS9 0
-#endif
-template <int LOG2N, bool GS = false>
-__host__ __device__ constexpr int xspec_wpe() { return LOG2N == 10 ? 2 : (LOG2N == 9 && GS && PPF_GS9 == 1 ? 4 : 1); }
-// the fused guess runs at 1024 points (and 512 with PPF_GS9): below, its
-// extra registers cost a wave per SIMD or spill (those shapes take k_dsum)
-__host__ __device__ constexpr bool xspec_guess_fused(int log2N) { return log2N == 10 || (log2N == 9 && PPF_GS9 != 0); }
-bool xspec_guess_fused_n(int log2N) { return xspec_guess_fused(log2N); }
-// one post-pass over the transform (power sums and X together, X scaled at
-// the write-out); 0: the two-pass form (sums, then X scaled in the buffer)
-#ifndef PPF_XS_ONEPASS
-#define PPF_XS_ONEPASS 1
-#endif
+// keep that register budget (<= 256).
+// The fused guess runs at 1024 points only: below, its extra registers cost a
+// wave per SIMD or spill, and those shapes take k_dsum_w.  (At 512 points,
+// round 5, C5 per 500 sub-ints in one call: the model reaches harmonic ~430 of
+// 513, above the NL = 192 guess harmonics, so k_gflag sets no sub-int and the
+// variant only costs its registers: k_xspec_w<9> 26.5 vs 22.0 ms, 90.1 vs
+// 84.7 ms per step.  Removed.)
+bool xspec_guess_fused_n(int log2N) { return log2N == 10; }
+// One post-pass over the transform: power sums and X together, X scaled at
+// the write-out.
 template <int LOG2N, int DT, bool GS>
-__global__ __launch_bounds__(64 * xsw<LOG2N>()) __attribute__((amdgpu_waves_per_eu(xspec_wpe<LOG2N, GS>())))
+__global__ __launch_bounds__(64 * xsw<LOG2N>()) __attribute__((amdgpu_waves_per_eu(LOG2N == 10 ? 2 : 1)))
 void k_xspec_w(XspecArgs a) {
     constexpr int kXSW = xsw<LOG2N>();
     using P = wfft::Plan<LOG2N>;
@@ -186,14 +150,7 @@ void k_xspec_w(XspecArgs a) {
     // 4 ahead, C3 27.1 -> 25.5 ms); at 512 points k_xspec_w runs four waves
     // per SIMD at <= 128 VGPRs, which one pair ahead keeps (126; C5 29.2 ->
     // 28.6 ms), two would not (132)
-#ifndef PPF_XS_MPRE9
-#define PPF_XS_MPRE9 1
-#endif
-#ifdef PPF_XS_MPRE
-    constexpr int MD = PPF_XS_MPRE;
-#else
-    constexpr int MD = LOG2N == 10 ? 4 : (LOG2N == 9 ? (GS && PPF_GS9 == 1 ? 0 : PPF_XS_MPRE9) : 0);
-#endif
+    constexpr int MD = LOG2N == 10 ? 4 : (LOG2N == 9 ? 1 : 0);
     using RowT = typename std::conditional<DT == 0, vf2, vd2>::type;
     extern __shared__ __attribute__((aligned(16))) double2 lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -202,14 +159,10 @@ void k_xspec_w(XspecArgs a) {
     int s, cb;
     block_map(a.xcd_swizzle, a.nblk, s, cb, a.nsub);
     if (a.needx && !a.needx[s]) return;               // uniform: moment-mode sub-int (or no slot)
-#if PPF_TW_LDS
     double2 *twl = lds + kXSW * SL;
     for (int i = threadIdx.x; i < tw_slots<LOG2N>(); i += 64 * kXSW) twl[i] = a.T[i];
     __syncthreads();
     const double2 *tw = twl;
-#else
-    const double2 *tw = a.T;
-#endif
     // rounds: in round r wave w takes channel cb*CB + r*kXSW + w
     const int cbase = cb * a.cb, cend = min(a.nchan, cbase + a.cb);
     const int nround = (a.cb + kXSW - 1) / kXSW;
@@ -260,7 +213,7 @@ void k_xspec_w(XspecArgs a) {
         const double f = a.freqs[(int64_t)s * a.nchan + __builtin_amdgcn_readfirstlane(nn)];
         return g_Dg * (1.0 / (f * f) - g_nrm2);
     };
-    double2 *gacc = lds + kXSW * SL + (PPF_TW_LDS ? tw_slots<LOG2N>() : 0);
+    double2 *gacc = lds + kXSW * SL + tw_slots<LOG2N>();
     if constexpr (GS) {
         gon = a.gflag[s] != 0;                         // uniform
         if (gon) {
@@ -319,7 +272,6 @@ void k_xspec_w(XspecArgs a) {
                     Mq[i][1] = Mrow[N - lane - 64 * i];
                 }
             };
-#if PPF_XS_ONEPASS
             // ONE post-pass over the transform: each pair's D_k feeds the
             // power sums (noise, Sd) and leaves the UNSCALED D_k conj(M_k) in
             // the buffer; the row's 1/errs_FT^2 is known once the sums are
@@ -410,107 +362,6 @@ void k_xspec_w(XspecArgs a) {
                 chan[2] = pd * inv_e2;                                  // Sd_n
                 chan[3] = readlane_d(ch_mpow, n - cbase) * inv_e2;     // S_n at tau = 0
             }
-#else
-            preload_m();
-            // pass 1: power sums (noise, Sd); pass 2 recomputes D for X
-            double pn = 0.0, pd = 0.0;
-            {
-                double2 w = w_seed;
-#pragma unroll
-                for (int i = 0; i < NP; ++i) {
-                    const int klo = lane + 64 * i, khi = N - klo;
-                    double2 Dlo, Dhi;
-                    rfft_pair<LOG2N>(buf, klo, w, Dlo, Dhi);
-                    w = cmul(w, w_step);
-                    const double p0 = cabs2(Dlo), p1 = cabs2(Dhi);
-                    if (klo >= a.kc) pn += p0;
-                    if (khi >= a.kc) pn += p1;
-                    if (klo >= 1) pd += p0;
-                    pd += p1;
-                    SCHED_CUT();
-                }
-            }
-            double2 Dm = cmk(0.0, 0.0);
-            if (lane == 0) {
-                const double2 zm = buf[wfft::pad<LOG2N>(N / 2)];
-                Dm = cmk(zm.x, -zm.y);
-                const double p = cabs2(Dm);
-                if (N / 2 >= a.kc) pn += p;
-                pd += p;
-            }
-            pn = wave_sum(pn);
-            pd = wave_sum(pd);
-            double errs_FT;
-            if (a.errs) errs_FT = readlane_d(ch_err, n - cbase) * sqrtN;
-            else errs_FT = sqrt(pn / (double)(NH - a.kc) / (double)(2 * N)) * sqrtN;
-            const double inv_e2 = 1.0 / (errs_FT * errs_FT);
-
-            // guess phasor of this row: El = w e^{2 pi i k dphi} at k = lane
-            // + 64 i by recurrence (step e^{2 pi i 64 dphi}: lane 1's phasor
-            // squared six times)
-            double2 El = cmk(0.0, 0.0), Est = El;
-            if (GS && gon) {
-                const int r = n - cbase;
-                const double wn = g_wn(n), dg = g_dgn(n);
-                const double2 E1 = cexp2pi((double)lane * dg);
-                El = cscale(E1, wn);
-                Est = cmk(readlane_d(E1.x, 1), readlane_d(E1.y, 1));
-#pragma unroll
-                for (int q = 0; q < 6; ++q) Est = cmul(Est, Est);
-                g_w2e2 += wn * wn * errs_FT * errs_FT;
-            }
-            {
-                // in place: X_k -> pad(k), X_{N-k} -> pad(N-k); the pair
-                // (0, N) keeps X_N in pad(N/2) (read above as Dm).  (Skipping
-                // the pairs past the block's cutoff, and X_{N-k} when the
-                // cutoff is below N/2, measured slower: C3 k_xspec_w 27.8 ->
-                // 28.6 ms, C2 with MOM_X 27.3 -> 28.3 ms)
-                double2 w = w_seed;
-#pragma unroll
-                for (int i = 0; i < NP; ++i) {
-                    const int klo = lane + 64 * i, khi = N - klo;
-                    if (GS && gon && 64 * i >= NL) break;   // (uniform) beyond the cutoff
-                    double2 Dlo, Dhi;
-                    rfft_pair<LOG2N>(buf, klo, w, Dlo, Dhi);
-                    w = cmul(w, w_step);
-                    // (loading these before the next row's prefetch, so their
-                    // in-order wait skips it, was measured: the extra
-                    // registers cost occupancy, C5 29.7 -> 33.2 ms)
-                    double2 Mlo, Mhi;
-                    if constexpr (MD > 0) {
-                        Mlo = Mq[i % MD][0];
-                        Mhi = Mq[i % MD][1];
-                        if (i + MD < NP) {
-                            Mq[i % MD][0] = Mrow[klo + 64 * MD];
-                            Mq[i % MD][1] = Mrow[khi - 64 * MD];
-                        }
-                    } else {
-                        Mlo = Mrow[klo];
-                        Mhi = Mrow[khi];
-                    }
-                    buf[wfft::pad<LOG2N>(klo)] =
-                        (klo == 0) ? cmk(0.0, 0.0) : cscale(cmulc(Dlo, Mlo), inv_e2);
-                    if (GS && gon) {
-                        // X_{N-k} is past the cutoff: its slot takes the
-                        // row's guess term of harmonic k (k = 0: dropped)
-                        if (klo != 0) buf[wfft::pad<LOG2N>(khi)] = cmul(Dlo, El);
-                        El = cmul(El, Est);
-                    } else {
-                        buf[klo == 0 ? wfft::pad<LOG2N>(N / 2) : wfft::pad<LOG2N>(khi)] =
-                            cscale(cmulc(Dhi, Mhi), inv_e2);
-                    }
-                    SCHED_CUT();
-                }
-            }
-            if (lane == 0) {
-                buf[XNYQ] = cscale(cmulc(Dm, Mrow[N / 2]), inv_e2);
-                double *chan = a.chan + crow * 4;
-                chan[0] = errs_FT;
-                chan[1] = inv_e2;
-                chan[2] = pd * inv_e2;                                  // Sd_n
-                chan[3] = readlane_d(ch_mpow, n - cbase) * inv_e2;     // S_n at tau = 0
-            }
-#endif
         }
         __syncthreads();
         // write-out: thread t -> channel c = t % 8 of the round, harmonics
@@ -521,17 +372,11 @@ void k_xspec_w(XspecArgs a) {
             if (nc < cend) {
                 const bool ok = !mask || mask[nc];
                 const double2 *b = lds + c * SL;
-#if PPF_XS_ONEPASS
                 const double ie2 = ok ? reinterpret_cast<const double *>(b + XIE2)[0] : 0.0;
-#endif
                 for (int k = threadIdx.x / kXSW; k < kw; k += 64) {
                     const int slot = k == N ? wfft::pad<LOG2N>(N / 2)
                                             : (k == N / 2 ? XNYQ : wfft::pad<LOG2N>(k));
-#if PPF_XS_ONEPASS
                     st_stream(Xs + (int64_t)k * a.nchan + nc, ok ? cscale(b[slot], ie2) : cmk(0.0, 0.0));
-#else
-                    st_stream(Xs + (int64_t)k * a.nchan + nc, ok ? b[slot] : cmk(0.0, 0.0));
-#endif
                 }
             }
         }
@@ -604,14 +449,6 @@ __host__ __device__ constexpr int xmom_slw() {
 //   FFT twiddles live in LDS, and the per-channel inputs (dphi, errs, mask)
 //   are read once per block into lane registers and broadcast by readlane.
 // ===========================================================================
-#ifndef PPF_G_CUT
-#define PPF_G_CUT 1
-#endif
-#if PPF_G_CUT
-#define G_CUT() __builtin_amdgcn_sched_barrier(0)
-#else
-#define G_CUT()
-#endif
 #ifdef PPF_XM_PROF
 // section cycle counters of k_xmom_g (profiling builds only)
 __device__ unsigned long long g_xprof[8];
@@ -805,12 +642,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void k
                 x[qq] = cmk((double)row[j2], (double)row[j2 + 1]);
             }
             wfft::wave_sync();
-#ifndef G_NOFFT
             wfft::fft_row<LOG2N>(x, buf, tw, lane);
             XP(1);
-#else
-            for (int qq = 0; qq < R; ++qq) buf[wfft::pad<LOG2N>(lane + 64 * qq)] = x[qq];
-#endif
             double2 Dm = cmk(0.0, 0.0);
             if (lane == 0) {
                 const double2 zm = buf[wfft::pad<LOG2N>(N / 2)];
@@ -855,7 +688,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void k
 #pragma unroll
             for (int i = 0; i < NP; ++i) {
                 pair(Mr, i, w);
-                G_CUT();
+                SCHED_CUT();
             }
             if (lane == 0) buf[SIDE] = cmulc(Dm, Mr[N / 2]);
             const double mpow = SH ? mrow[NH].x : Pwave[n];
@@ -902,7 +735,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void k
         // among several.
         int nb = N / 8;
         if constexpr (SH) nb = min(nb, (__builtin_amdgcn_readlane(ch_kc, n - cbase) + 3) >> 2);
-#ifndef G_NOMFMA
 #pragma unroll 4
         for (int t = 0; t < KPW / 4; ++t) {
             const int b = XW * t + wave;
@@ -918,7 +750,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void k
             d0 = __builtin_amdgcn_mfma_f64_16x16x4f64(abase[2 * se], bv, d0, 0, 0, 0);
             d1 = __builtin_amdgcn_mfma_f64_16x16x4f64(abase[2 * so], bv, d1, 0, 0, 0);
         }
-#endif
         XP(4);
         // output element tid: this wave's sub-int, moment om = 2 j + set,
         // Re/Im ori
@@ -1043,48 +874,19 @@ constexpr int kX2W = 4;
 constexpr int kX2SL = wf2::kXSlots + wf2::kSpSlots;       // 1072 slots per wave
 constexpr int kX2IE = 1041;                               // the row's 1/errs_FT^2 (.x)
 __device__ __forceinline__ int x2slot(int k) { return k + (k >> 6); }   // k <= 1024 -> <= 1040
-#ifndef PPF_X2_MD
-#define PPF_X2_MD 4
-#endif
-#ifndef PPF_XSPEC2
-#define PPF_XSPEC2 1
-#endif
-#ifndef PPF_X2_NT
-#define PPF_X2_NT (PPF_NT ? 3 : 0)   // nontemporal row loads (1), X stores (2): ld/st_stream
-#endif
-#ifndef PPF_X2_MEARLY
-#define PPF_X2_MEARLY 0
-#endif
-#ifndef PPF_X2_LATEPF
-#define PPF_X2_LATEPF 0
-#endif
-#ifndef PPF_X2_EW
-#define PPF_X2_EW 1
-#endif
-// PPF_X2_DIAG (timing-only builds, results wrong): 1 no X stores, 2 every
-// model load from the first model row (L2 hits), 4 no FFT (the row values go
-// straight to the post-pass)
-#ifndef PPF_X2_DIAG
-#define PPF_X2_DIAG 0
-#endif
-// TL guess sums: 1 = per-wave partials in registers, no barrier in the round
-// loop; 0 = the round's two barriers kept for the guess add only (the X
-// stores still go out whole lines, by the row's own wave, before the first)
-#ifndef PPF_X2_GREG
-#define PPF_X2_GREG 1
-#endif
 
 template <int DT, bool GS, bool TL>
 __global__ __launch_bounds__(64 * kX2W) __attribute__((amdgpu_waves_per_eu(2)))
 void k_xspec_w2(XspecArgs a) {
     constexpr int N = 1024, NH = N + 1;
-    constexpr bool GR = TL && PPF_X2_GREG != 0;      // guess partials in registers
+    // TL guess sums: per-wave partials in registers, no barrier in the round loop
+    constexpr bool GR = TL;
     // GR with the guess: the per-lane constants of the transform and of
     // the post-pass, and the channels' guess phasors, in an LDS table behind
     // the wave buffers (one copy per workgroup, read back every row)
     // instead of 16 VGPRs held across the round loop
     constexpr bool LT = GR && GS;
-    constexpr int MD = PPF_X2_MD;
+    constexpr int MD = 4;                            // model values loaded ahead of the post-pass
     using RowT = typename std::conditional<DT == 0, vf2, vd2>::type;
     extern __shared__ __attribute__((aligned(16))) double2 lds[];
     const int lane0 = threadIdx.x & 63;
@@ -1129,15 +931,8 @@ void k_xspec_w2(XspecArgs a) {
 #pragma unroll 1
         for (int h = lane0; h < kwp; h += 64) {
             const double2 v = (ok && h < kw) ? cscale(b[x2slot(h)], ie2) : cmk(0.0, 0.0);
-#if PPF_X2_DIAG & 1
-            if (ie2 == 12345.0)            // (timing-only build: no X stores)
-#endif
-#if PPF_X2_NT & 2
             __builtin_nontemporal_store(vd2{v.x, v.y},
                                         reinterpret_cast<vd2 *>(Xn + (int64_t)(h >> 3) * a.nchan * kXTile));
-#else
-            Xn[(int64_t)(h >> 3) * a.nchan * kXTile] = v;
-#endif
         }
     };
     const int mlane = (cbase + lane0 < cend && (!mask || mask[cbase + lane0])) ? 1 : 0;
@@ -1212,15 +1007,8 @@ void k_xspec_w2(XspecArgs a) {
     auto fetch = [&](int n) {
         const RowT *src = rows + ((int64_t)s * a.nchan + n) * N;
 #pragma unroll
-        for (int q = 0; q < 16; ++q) {
-#if PPF_X2_NT & 1
-            zr[q] = __builtin_nontemporal_load(src + lane0 + 64 * q);
-#else
-            zr[q] = src[lane0 + 64 * q];
-#endif
-        }
+        for (int q = 0; q < 16; ++q) zr[q] = __builtin_nontemporal_load(src + lane0 + 64 * q);
     };
-#if PPF_X2_EW
     // Round 6: the next row's load is unconditional (a row past the block,
     // or a masked one, is replaced by the block's last row: a valid address
     // whose values are ignored), so the row registers carry no phi between
@@ -1238,14 +1026,9 @@ void k_xspec_w2(XspecArgs a) {
     int n = cbase + wave;
     fetch_c(n);
     rows_ready();
-#else
-    int n = cbase + wave;
-    if (usable(n)) fetch(n);
-#endif
     XP_INIT();
     for (int r = 0; r < nround; ++r, n += kX2W) {
         const bool live = usable(n);
-#if PPF_X2_EW
         if (n < cend && !live && lane0 < 4) a.chan[((int64_t)s * a.nchan + n) * 4 + lane0] = 0.0;
         double2 x[16];
 #pragma unroll
@@ -1266,13 +1049,9 @@ void k_xspec_w2(XspecArgs a) {
         const int kA = wf2::pair_k0(lane);
         const int hl0 = lo ? kA : N - kA, hstep = lo ? 64 : -64;
         const double2 *Mrow = a.Mft + ((int64_t)mi * a.nchan + (n < cend ? n : cend - 1)) * NH;
-#if PPF_X2_DIAG & 2
-        Mrow = a.Mft;       // (timing-only build: every model load from the first row, L2 hits)
-#endif
-        // the first MD slots' model values: PPF_X2_MEARLY issues them here,
-        // before the next row's prefetch, so that the post-pass's wait for
-        // them (vmcnt is in order) does not include the prefetch; else
-        // after the FFT.  The loads are unconditional (hl < N/2 is always a
+        // the first MD slots' model values, issued after the FFT (issued
+        // here, before the next row's prefetch: 24.2 vs 23.9 ms, round 6).
+        // The loads are unconditional (hl < N/2 is always a
         // valid index): under a lane-divergent branch the compiler cannot
         // count the loads in flight and waits for all of them (vmcnt(0),
         // the next row's prefetch included) at every slot.
@@ -1281,40 +1060,12 @@ void k_xspec_w2(XspecArgs a) {
 #pragma unroll
             for (int i = 0; i < MD; ++i) Mq[i] = Mrow[(unsigned)(hl0 + hstep * i)];
         };
-        if (PPF_X2_MEARLY && live) mpre();
-        __builtin_amdgcn_sched_barrier(0);
+        SCHED_CUT();
         fetch_c(n + kX2W);                       // next row in flight during this FFT
-#else
-        if (n < cend && !live) {
-            if (lane0 < 4) a.chan[((int64_t)s * a.nchan + n) * 4 + lane0] = 0.0;
-            if (usable(n + kX2W)) fetch(n + kX2W);
-        }
-#endif
         if (live) {
             const int64_t crow = (int64_t)s * a.nchan + n;
-#if !PPF_X2_EW
-            double2 x[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) x[q] = cmk((double)zr[q].x, (double)zr[q].y);
-#endif
             const int rr = n - cbase;
-#if !PPF_X2_EW
-            int lane = lane0;
-            asm volatile("" : "+v"(lane));
-            const bool lo = lane <= 32;
-            const int kA = wf2::pair_k0(lane);
-            const int hl0 = lo ? kA : N - kA, hstep = lo ? 64 : -64;
-            const double2 *Mrow = a.Mft + ((int64_t)mi * a.nchan + n) * NH;
-            double2 Mq[MD > 0 ? MD : 1];
-            auto mpre = [&]() {
-#pragma unroll
-                for (int i = 0; i < MD; ++i) Mq[i] = Mrow[(unsigned)(hl0 + hstep * i)];
-            };
-            if (PPF_X2_MEARLY) mpre();
-            if (!PPF_X2_LATEPF && usable(n + kX2W)) fetch(n + kX2W);   // next row in flight during this FFT
-#endif
             XP(0);
-#if !(PPF_X2_DIAG & 4)
             if constexpr (LT) {
                 wf2::Seeds sdl;
                 sdl.w1 = ltab[lane];
@@ -1323,11 +1074,9 @@ void k_xspec_w2(XspecArgs a) {
             } else {
                 wf2::fft1024(x, buf, lane, sd);
             }
-#endif
             XP(1);
-            if (PPF_X2_EW) __builtin_amdgcn_sched_barrier(0);
-            if (!PPF_X2_MEARLY) mpre();
-            if (!PPF_X2_EW && PPF_X2_LATEPF && usable(n + kX2W)) fetch(n + kX2W);
+            SCHED_CUT();
+            mpre();
             double2 zm = cmk(0.0, 0.0);
             wf2::pairs(x, buf + wf2::kXSlots, lane, zm);
             XP(2);
@@ -1455,9 +1204,7 @@ void k_xspec_w2(XspecArgs a) {
                 chan[3] = mpow * inv_e2;                                // S_n at tau = 0
             }
             if constexpr (TL) {
-#if PPF_X2_EW
                 rows_ready();
-#endif
                 XP(4);
                 // (a wave's LDS operations are ordered: the staged X of
                 // every lane is there, and read before the next row's
@@ -1468,17 +1215,13 @@ void k_xspec_w2(XspecArgs a) {
                 XP(5);
             }
         } else if constexpr (TL) {
-#if PPF_X2_EW
             rows_ready();
-#endif
             if (n < cend) store_tiles(n, buf, 0.0, false);    // a zapped channel's tiles: zeros
         }
         if constexpr (GR) continue;
         if (TL && !(GS && gon)) continue;         // (uniform) no guess terms to add: no barrier
         if constexpr (!TL) {
-#if PPF_X2_EW
             rows_ready();
-#endif
             XP(4);
         }
         __syncthreads();
@@ -1493,17 +1236,8 @@ void k_xspec_w2(XspecArgs a) {
                 const double2 *b = lds + c * kX2SL;
                 const double ie2 = ok ? reinterpret_cast<const double *>(b + kX2IE)[0] : 0.0;
                 for (int k = threadIdx.x / kX2W; k < kw; k += 64) {
-#if PPF_X2_DIAG & 1
-                    if (ie2 == 12345.0)            // (timing-only build: no X stores)
-#endif
-                    {
-#if PPF_X2_NT & 2
                     const double2 v = ok ? cscale(b[x2slot(k)], ie2) : cmk(0.0, 0.0);
                     __builtin_nontemporal_store(vd2{v.x, v.y}, reinterpret_cast<vd2 *>(Xs + (int64_t)k * a.nchan + nc));
-#else
-                    Xs[(int64_t)k * a.nchan + nc] = ok ? cscale(b[x2slot(k)], ie2) : cmk(0.0, 0.0);
-#endif
-                    }
                 }
             }
         }
@@ -1656,9 +1390,6 @@ __device__ __forceinline__ void wmr_stage_g(double2 *buf, int N, int L, int R, c
 // (the LDS of a workgroup -- four row buffers and the twiddles -- admits
 // three of them per CU at NMAX 512 and two at 1024, so the register budget
 // is three / two waves per SIMD)
-#ifndef PPF_WM_PRE
-#define PPF_WM_PRE 1
-#endif
 // ODD: odd nbin (<= 1023), the row as NF = nbin complex points with zero
 // imaginary parts (rfft_len), X_k = Z_k for k <= nbin / 2: no pair post-pass.
 template <int DT, int NMAX, bool ODD>
@@ -1697,7 +1428,6 @@ void k_xspec_wm(XspecArgs a) {
     const double ch_mpow = nl < cend ? a.Mpow[(int64_t)mi * a.nchan + nl] : 0.0;
     const double ch_err = (a.errs && nl < cend) ? a.errs[(int64_t)s * a.nchan + nl] : 0.0;
     const bool two0 = !ODD && (__builtin_ctz((unsigned)N) & 1) != 0;
-#if PPF_WM_PRE
     // the wave's next row in registers while this one is transformed
     // (unconditional loads of a valid row: the prefetch stays in VGPRs)
     using ET = typename std::conditional<DT == 0, float, double>::type;
@@ -1713,11 +1443,9 @@ void k_xspec_wm(XspecArgs a) {
         }
     };
     fetch(min(cbase + wave, cend - 1));
-#endif
     for (int r = 0, n = cbase + wave; r < nround; ++r, n += kWmW) {
         const bool live = usable(n);
         if (n < cend && !live && lane < 4) a.chan[((int64_t)s * a.nchan + n) * 4 + lane] = 0.0;
-#if PPF_WM_PRE
         if (live) {
 #pragma unroll
             for (int i = 0; i < PJ; ++i) {
@@ -1730,22 +1458,8 @@ void k_xspec_wm(XspecArgs a) {
             }
         }
         fetch(min(n + kWmW, cend - 1));
-#endif
         if (live) {
             const int64_t crow = (int64_t)s * a.nchan + n;
-#if !PPF_WM_PRE
-            static_assert(!ODD, "odd nbin needs PPF_WM_PRE");
-            if (DT == 0) {
-                const float2 *src = reinterpret_cast<const float2 *>(a.data) + crow * (int64_t)N;
-                for (int j = lane; j < N; j += 64) {
-                    const float2 v = src[j];
-                    buf[j] = cmk((double)v.x, (double)v.y);
-                }
-            } else {
-                const double2 *src = reinterpret_cast<const double2 *>(a.data) + crow * (int64_t)N;
-                for (int j = lane; j < N; j += 64) buf[j] = src[j];
-            }
-#endif
             wfft::wave_sync();
             // the stages in fft_radices' order (one 2 when the power of two
             // is odd, 4s, then the odd primes ascending), wave-uniform
@@ -2043,20 +1757,17 @@ hipError_t launch_xspec_wm(const XspecArgs &a, hipStream_t st) {
 static bool use_xspec2() {
     static const bool on = [] {
         const char *e = getenv("PPF_XSPEC2");
-        return e ? atoi(e) != 0 : (PPF_XSPEC2 != 0);
+        return e ? atoi(e) != 0 : true;
     }();
     return on;
 }
 // tiled X slots for the moment-mode sub-ints of k_xspec_w2 unless PPF_XTILE=0
 // (environment, read once): then every slot is harmonic-major and written
 // by the round's write-out, as before round 7
-#ifndef PPF_XTILE
-#define PPF_XTILE 1
-#endif
 bool xspec_tiled(int log2N) {
     static const bool on = [] {
         const char *e = getenv("PPF_XTILE");
-        return e ? atoi(e) != 0 : (PPF_XTILE != 0);
+        return e ? atoi(e) != 0 : true;
     }();
     return on && log2N == 10 && use_xspec2();
 }
@@ -2076,7 +1787,7 @@ static void launch_w(const XspecArgs &a, hipStream_t st) {
             if (a.xtile) {
                 if (a.gflag)
                     hipLaunchKernelGGL((k_xspec_w2<DT, true, true>), g, b,
-                                       lds + (size_t)(PPF_X2_GREG ? 256 : guess_slots(10)) * sizeof(double2), st, a);
+                                       lds + (size_t)256 * sizeof(double2), st, a);   // the [4][64] lane table
                 else hipLaunchKernelGGL((k_xspec_w2<DT, false, true>), g, b, lds, st, a);
             }
             if (a.gflag)
@@ -2086,11 +1797,10 @@ static void launch_w(const XspecArgs &a, hipStream_t st) {
             return;
         }
     }
-    const size_t lds = ((size_t)xsw<L2>() * xspec_slw<L2>() + (PPF_TW_LDS ? tw_slots<L2>() : 0)) *
-                       sizeof(double2);
+    const size_t lds = ((size_t)xsw<L2>() * xspec_slw<L2>() + tw_slots<L2>()) * sizeof(double2);
     dim3 g((unsigned)((int64_t)a.nsub * a.nblk)), b(64 * xsw<L2>());
-    if (a.gflag && xspec_guess_fused(L2))
-        hipLaunchKernelGGL((k_xspec_w<L2, DT, xspec_guess_fused(L2)>), g, b,
+    if (a.gflag && L2 == 10)                          // the fused guess (xspec_guess_fused_n)
+        hipLaunchKernelGGL((k_xspec_w<L2, DT, L2 == 10>), g, b,
                            lds + (size_t)guess_slots(L2) * sizeof(double2), st, a);
     else hipLaunchKernelGGL((k_xspec_w<L2, DT, false>), g, b, lds, st, a);
 }
@@ -2170,117 +1880,8 @@ __global__ __launch_bounds__(64 * kNoiseW) void k_noise_w(NoiseArgs a, int64_t n
     }
 }
 
-// k_noise_h: k_noise_w on the half-buffer FFT (wfft::fft_row_h) without the
-// next-row prefetch: 8.7 KB of LDS and fewer VGPRs per wave at 1024 points,
-// so more waves per SIMD; bit-identical results (round-4 prototype of the
-// wave-FFT restructure; PPF_NOISE_HALF=1 selects it).
-#ifndef PPF_NOISE_HALF
-#define PPF_NOISE_HALF 0
-#endif
-#ifndef PPF_NOISE_HALF_WPE
-#define PPF_NOISE_HALF_WPE 3
-#endif
-template <int LOG2N, int DT>
-__global__ __launch_bounds__(64 * kNoiseW) __attribute__((amdgpu_waves_per_eu(PPF_NOISE_HALF_WPE)))
-void k_noise_h(NoiseArgs a, int64_t nrows) {
-    using P = wfft::Plan<LOG2N>;
-    constexpr int N = P::N, R = P::R, NP = N / 128;
-    constexpr int SL = wfft::buf_slots<LOG2N>();
-    using RowT = typename std::conditional<DT == 0, vf2, vd2>::type;
-    extern __shared__ __attribute__((aligned(16))) double2 lds[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double2 *tw = lds;
-    double *hb = reinterpret_cast<double *>(lds + tw_slots<LOG2N>()) + wave * SL;
-    for (int i = threadIdx.x; i < tw_slots<LOG2N>(); i += 64 * kNoiseW) tw[i] = a.T[i];
-    __syncthreads();
-    const double2 w_seed = a.T2[lane], w_step = a.T2[64];
-    const RowT *rows = reinterpret_cast<const RowT *>(a.in);
-    const int64_t nw = (int64_t)gridDim.x * kNoiseW;
-    // the first PF of the next row's R loads per lane are in flight during
-    // this row's transform (PPF_NOISE_HALF_PF; 0: none)
-#ifndef PPF_NOISE_HALF_PF
-#define PPF_NOISE_HALF_PF 0
-#endif
-    constexpr int PF = PPF_NOISE_HALF_PF < R ? PPF_NOISE_HALF_PF : R;
-    RowT zp[PF > 0 ? PF : 1];
-    int64_t row = (int64_t)blockIdx.x * kNoiseW + wave;
-    if (PF > 0 && row < nrows) {
-#pragma unroll
-        for (int q = 0; q < PF; ++q) zp[q] = rows[row * N + lane + 64 * q];
-    }
-    for (; row < nrows; row += nw) {
-        double2 x[R];
-        const RowT *src = rows + row * N;
-#pragma unroll
-        for (int q = 0; q < R; ++q) {
-            const RowT z = q < PF ? zp[q % (PF > 0 ? PF : 1)] : src[lane + 64 * q];
-            x[q] = cmk((double)z.x, (double)z.y);
-        }
-        if (PF > 0 && row + nw < nrows) {
-#pragma unroll
-            for (int q = 0; q < PF; ++q) zp[q] = rows[(row + nw) * N + lane + 64 * q];
-        }
-        typename wfft::HBlk<LOG2N, P::NST - 1>::T vl;
-        wfft::fft_row_h<LOG2N>(x, hb, tw, lane, vl);
-        // the (k, N - k) pairs: real parts, then imaginary parts
-        double zr[2 * NP + 1], zi[2 * NP + 1];
-        wfft::hwrite_last<LOG2N, 0>(hb, lane, vl);
-        wfft::wave_sync();
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const int k = lane + 64 * i;
-            zr[2 * i] = hb[wfft::pad<LOG2N>(k)];
-            zr[2 * i + 1] = hb[k == 0 ? 0 : wfft::pad<LOG2N>(N - k)];
-        }
-        zr[2 * NP] = hb[wfft::pad<LOG2N>(N / 2)];
-        wfft::wave_sync();
-        wfft::hwrite_last<LOG2N, 1>(hb, lane, vl);
-        wfft::wave_sync();
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const int k = lane + 64 * i;
-            zi[2 * i] = hb[wfft::pad<LOG2N>(k)];
-            zi[2 * i + 1] = hb[k == 0 ? 0 : wfft::pad<LOG2N>(N - k)];
-        }
-        zi[2 * NP] = hb[wfft::pad<LOG2N>(N / 2)];
-        wfft::wave_sync();
-        double pn = 0.0;
-        double2 w = w_seed;
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const int klo = lane + 64 * i, khi = N - klo;
-            // rfft_pair on register copies of the two bins
-            const double2 zk = cmk(zr[2 * i], zi[2 * i]), zn = cmk(zr[2 * i + 1], zi[2 * i + 1]);
-            const double2 e = cmk(0.5 * (zk.x + zn.x), 0.5 * (zk.y - zn.y));
-            const double2 o = cmk(0.5 * (zk.x - zn.x), 0.5 * (zk.y + zn.y));
-            const double2 wo = cmul(w, o);
-            const double2 Dlo = cmk(e.x + wo.y, e.y - wo.x);
-            const double2 Dhi = cmk(e.x - wo.y, -(e.y + wo.x));
-            w = cmul(w, w_step);
-            if (klo >= a.kc) pn += cabs2(Dlo);
-            if (khi >= a.kc) pn += cabs2(Dhi);
-        }
-        if (lane == 0 && N / 2 >= a.kc) pn += cabs2(cmk(zr[2 * NP], zi[2 * NP]));
-        pn = wave_sum(pn);
-        if (lane == 0) a.out[row] = sqrt(pn / (double)a.nbin / (double)(N + 1 - a.kc));
-    }
-}
-
-template <int LOG2N, int DT>
-static void launch_nh(const NoiseArgs &a, int64_t nrows, hipStream_t st) {
-    const size_t lds = (size_t)tw_slots<LOG2N>() * sizeof(double2) +
-                       (size_t)kNoiseW * wfft::buf_slots<LOG2N>() * sizeof(double);
-    const int64_t want = (nrows + kNoiseW - 1) / kNoiseW;
-    const unsigned grid = (unsigned)std::min<int64_t>(want, 256 * 24);
-    hipLaunchKernelGGL((k_noise_h<LOG2N, DT>), dim3(grid), dim3(64 * kNoiseW), lds, st, a, nrows);
-}
-
 template <int LOG2N, int DT>
 static void launch_nw(const NoiseArgs &a, int64_t nrows, hipStream_t st) {
-    if (PPF_NOISE_HALF && LOG2N == 10) {
-        launch_nh<LOG2N, DT>(a, nrows, st);
-        return;
-    }
     const size_t lds = ((size_t)kNoiseW * wfft::buf_slots<LOG2N>() + tw_slots<LOG2N>()) * sizeof(double2);
     // two to four workgroups per CU by LDS; a few rows per wave
     const int64_t want = (nrows + kNoiseW - 1) / kNoiseW;
@@ -2330,14 +1931,10 @@ __global__ __launch_bounds__(64 * kXW) void k_align_part_w(AlignArgs a) {
     const int s0 = g * per, s1 = min(a.nsub, s0 + per);
     const double2 w_seed = a.T2[lane], w_step = a.T2[64];
     const RowT *rows = reinterpret_cast<const RowT *>(a.in);
-#if PPF_TW_LDS
     double2 *twl = lds + kXW * SL;
     for (int i = threadIdx.x; i < tw_slots<LOG2N>(); i += 64 * kXW) twl[i] = a.T[i];
     __syncthreads();
     const double2 *tw = twl;
-#else
-    const double2 *tw = a.T;
-#endif
     double2 Alo[NP], Ahi[NP], Am = cmk(0.0, 0.0);
 #pragma unroll
     for (int i = 0; i < NP; ++i) Alo[i] = Ahi[i] = cmk(0.0, 0.0);
@@ -2416,7 +2013,7 @@ __global__ __launch_bounds__(64 * kXW) void k_align_part_w(AlignArgs a) {
 
 template <int L2, int DT>
 static void launch_align_w_t(const AlignArgs &a, hipStream_t st) {
-    const size_t lds = ((size_t)kXW * xspec_slw<L2>() + (PPF_TW_LDS ? tw_slots<L2>() : 0)) * sizeof(double2);
+    const size_t lds = ((size_t)kXW * xspec_slw<L2>() + tw_slots<L2>()) * sizeof(double2);
     hipLaunchKernelGGL((k_align_part_w<L2, DT>), dim3((unsigned)((int64_t)a.ngroup * a.nchan)),
                        dim3(64 * kXW), lds, st, a);
 }
