@@ -204,13 +204,14 @@ int cz_tables(ppf_ctx *ctx, const ppf::CzPlan &c, hipStream_t st, const double2 
 
 struct FitLayout {
     size_t M, X, chan, stats, x0, gP, gw, nuref, Msum, gpart, gwx, gflag, state, partials, active, mom, dphi,
-        mres, hcen, Mpow, MP, KC, needx, xslot, xtile, rclist, Bt, total;
+        mres, hcen, Mpow, MP, KC, needx, xslot, xtile, cls, rec, hmlist, nglist, rclist, Bt, total;
     // rows past the LDS transforms (round 6): their rFFTs (data spectra,
     // long-transform chirp tables and work rows, rows per chunk)
     int lng;
     size_t spec, lchirp, lA, lY, gprof, gspec, gsh;
     int64_t lrows;
     int nblk, cb, cbd, nblkd;
+    int cbx, nblkx;   // the spectrum pass's own channel block (ppf::xspec_own_cb), else cb, nblk
     int fused;    // phase+DM fits on the fused moment pass (k_xmom_g), X only for scattering fits
     int momx;     // wave shapes, PPF_OPT_MOM_X: every fit's moments from X (k_xspec_w + k_moments)
     int xcap;     // X slots
@@ -264,6 +265,9 @@ FitLayout fit_layout(const ppf_fit_desc *d) {
     L.cb = d->nchan < 32 ? d->nchan : 32;
     L.nblk = (d->nchan + L.cb - 1) / L.cb;
     L.fused = ppf::xspec_wave_supported(rfft_log2(d->nbin), L.cb) ? 1 : 0;
+    L.cbx = L.cb;
+    if (L.fused && ppf::xspec_own_cb(rfft_log2(d->nbin)) > 0) L.cbx = ppf::xspec_own_cb(rfft_log2(d->nbin));
+    L.nblkx = (d->nchan + L.cbx - 1) / L.cbx;
     // moments from X: on request, or by default where the GetTOAs guess is
     // fused into the spectrum pass (1024-point rows): there the X pass
     // replaces both the guess pass (k_dsum) and k_xmom_g's re-FFT
@@ -298,6 +302,10 @@ FitLayout fit_layout(const ppf_fit_desc *d) {
     L.needx = o; o += align256(nsub);
     L.xslot = o; o += align256(sizeof(int32_t) * nsub);
     L.xtile = o; o += L.tiled ? align256(nsub) : 0;
+    L.cls = o;   o += align256(sizeof(int32_t) * nsub);
+    L.rec = o;   o += align256(sizeof(double) * nsub * ppf::kRecN);
+    L.hmlist = o; o += align256(sizeof(int32_t) * nsub);
+    L.nglist = o; o += align256(sizeof(int32_t) * nsub);
     L.rclist = o; o += align256(sizeof(int32_t) * nsub);
     L.Bt = o;    o += align256(sizeof(double) * (nharm - 1) / 2 * 16);
     if (d->guess) {
@@ -305,10 +313,10 @@ FitLayout fit_layout(const ppf_fit_desc *d) {
         L.gw = o; o += align256(sizeof(double) * nsub * (size_t)L.nblkd * 2);
         L.nuref = o; o += align256(sizeof(double) * nsub);
         L.Msum = o; o += align256(sizeof(double2) * (size_t)(d->nmodel > 0 ? d->nmodel : 1) * nharm);
-        if (L.fused) {   // guess spectrum fused into k_xspec_w (k_gflag)
+        if (L.fused) {   // guess spectrum fused into k_xspec_w (k_classify: gflag)
             const size_t ng = (size_t)ppf::guess_slots(rfft_log2(d->nbin));
-            L.gpart = o; o += align256(sizeof(double2) * nsub * (size_t)L.nblk * ng);
-            L.gwx = o;   o += align256(sizeof(double) * nsub * (size_t)L.nblk * 3);
+            L.gpart = o; o += align256(sizeof(double2) * nsub * (size_t)L.nblkx * ng);
+            L.gwx = o;   o += align256(sizeof(double) * nsub * (size_t)L.nblkx * 3);
             L.gflag = o; o += align256(nsub);
         }
     }
@@ -635,31 +643,41 @@ int ppf_fit_batch(ppf_ctx *ctx, const ppf_fit_desc *d, void *stream) {
     uint8_t *needx = (uint8_t *)(ws + L.needx);
     int32_t *xslot = (int32_t *)(ws + L.xslot);
     uint8_t *xtile = L.tiled ? (uint8_t *)(ws + L.xtile) : nullptr;
-    if ((e = ppf::launch_classify(d->nsub, d->fit_flags, d->init, d->log10_tau, L.fused && !L.momx, L.xcap,
-                                  needx, xslot, xtile, st)) != hipSuccess)
-        return hip_fail(ctx, e, "k_classify");
     // fused guess: the sub-ints k_xspec_w streams whose mean-model cutoff
     // fits its guess harmonics accumulate the guess spectrum there
     uint8_t *gflag = nullptr;
-    if (d->guess && L.fused && ppf::xspec_guess_fused_n(rfft_log2(d->nbin))) {
-        gflag = (uint8_t *)(ws + L.gflag);
-        const int klim = 64 * ppf::guess_npl(rfft_log2(d->nbin));
-        if ((e = ppf::launch_gflag(d->nsub, d->nchan, needx, (const int32_t *)(ws + L.KC),
-                                   d->model_index, klim, gflag, st)) != hipSuccess)
-            return hip_fail(ctx, e, "k_gflag");
-    }
+    if (d->guess && L.fused && ppf::xspec_guess_fused_n(rfft_log2(d->nbin))) gflag = (uint8_t *)(ws + L.gflag);
+    // the words behind active: [4], [5] k_tr_init's kind counts, [8]
+    // k_classify's arrival ticket, [9], [10] its list counts
+    unsigned *kinds = (unsigned *)(ws + L.active + 16);
+    if ((e = hipMemsetAsync(kinds, 0, 8 * sizeof(unsigned), st)) != hipSuccess)
+        return hip_fail(ctx, e, "hipMemsetAsync");
+    ppf::ClassifyArgs ca{};
+    ca.nsub = d->nsub; ca.nchan = d->nchan; ca.log10_tau = d->log10_tau;
+    ca.fused = (L.fused && !L.momx) ? 1 : 0; ca.xcap = L.xcap;
+    ca.fit_flags = d->fit_flags; ca.init = d->init; ca.freqs = d->freqs; ca.P = d->P;
+    ca.nu_fits = d->nu_fits; ca.mask = d->chan_mask; ca.model_index = d->model_index;
+    ca.KC = (const int32_t *)(ws + L.KC);
+    ca.klim = gflag ? 64 * ppf::guess_npl(rfft_log2(d->nbin)) : -1;
+    ca.guess_DM = d->guess ? d->guess_DM : nullptr; ca.guess_ref = d->guess ? d->guess_ref : 0;
+    ca.needx = needx; ca.xslot = xslot; ca.xtile = xtile; ca.gflag = gflag;
+    ca.cls = (int32_t *)(ws + L.cls); ca.rec = (double *)(ws + L.rec);
+    ca.hm_list = (int32_t *)(ws + L.hmlist); ca.ng_list = (int32_t *)(ws + L.nglist);
+    ca.counts = kinds + 4;
+    if ((e = ppf::launch_classify(ca, st)) != hipSuccess) return hip_fail(ctx, e, "k_classify");
     mark(1);
 
     ppf::XspecArgs xa{};
     xa.nsub = d->nsub; xa.nchan = d->nchan; xa.nbin = d->nbin; xa.log2N = rfft_log2(d->nbin);
-    xa.kc = kc; xa.nblk = L.nblk; xa.cb = L.cb; xa.dtype = d->data_dtype;
+    xa.kc = kc; xa.nblk = L.nblkx; xa.cb = L.cbx; xa.dtype = d->data_dtype;
     // k_xspec_w: channel-block-major (mode 2) when the model spectra
     // outgrow the L2s, sub-int-major otherwise; k_xmom_g stages its model
     // row in LDS per workgroup and keeps mode 1
     constexpr long long kOrder2Bytes = 32ll << 20;
     const long long model_bytes = (long long)d->nchan * (d->nbin / 2 + 1) * 16;
     const int xcd1 = (L.nblk % 8 == 0) ? 1 : 0;
-    xa.xcd_swizzle = (xcd1 && model_bytes > kOrder2Bytes) ? 2 : xcd1;
+    const int xcdx = (L.nblkx % 8 == 0) ? 1 : 0;
+    xa.xcd_swizzle = (xcdx && model_bytes > kOrder2Bytes) ? 2 : xcdx;
     xa.data = d->data; xa.Mft = Mft; xa.model_index = d->model_index; xa.mask = d->chan_mask;
     xa.errs = d->errs; xa.freqs = d->freqs; xa.P = d->P; xa.T = T; xa.T2 = T2;
     xa.X = (double2 *)(ws + L.X); xa.chan = (double *)(ws + L.chan);
@@ -668,6 +686,15 @@ int ppf_fit_batch(ppf_ctx *ctx, const ppf_fit_desc *d, void *stream) {
     xa.xtile = xtile;
     xa.xnh = L.xnh;
     xa.gflag = gflag;
+    xa.cls = ca.cls;
+    xa.rec = ca.rec;
+    // the caller expects no streaming fit (C2's pipeline): the launches
+    // whose sub-ints are then few or none stride over k_classify's lists
+    const bool bounded = (d->options & PPF_OPT_NO_X) != 0;
+    if (bounded && xtile) {
+        xa.list = ca.hm_list;
+        xa.nlist = ca.counts + 1;
+    }
     if (gflag) {
         xa.gpart = (double2 *)(ws + L.gpart);
         xa.gw = (double *)(ws + L.gwx);
@@ -716,6 +743,10 @@ int ppf_fit_batch(ppf_ctx *ctx, const ppf_fit_desc *d, void *stream) {
         da.gP = (double *)(ws + L.gP); da.gw = (double *)(ws + L.gw);
         da.nuref = (double *)(ws + L.nuref);
         da.gflag = gflag;
+        if (bounded && gflag) {
+            da.list = ca.ng_list;
+            da.nlist = ca.counts + 2;
+        }
         mark(7);
         if ((e = ppf::launch_dsum(da, st)) != hipSuccess) return hip_fail(ctx, e, "k_dsum");
         mark(8);
@@ -735,7 +766,7 @@ int ppf_fit_batch(ppf_ctx *ctx, const ppf_fit_desc *d, void *stream) {
         ga.gflag = gflag;
         ga.gpart = xa.gpart;
         ga.gwx = xa.gw;
-        ga.nblk = L.nblk;
+        ga.nblk = L.nblkx;
         if (L.lng) {
             // the profiles' rFFTs on the long transforms (same plan as the rows)
             double *prof = (double *)(ws + L.gprof);
@@ -775,13 +806,12 @@ int ppf_fit_batch(ppf_ctx *ctx, const ppf_fit_desc *d, void *stream) {
     sa.active = (unsigned *)(ws + L.active);
     sa.rc_count = sa.active + 1;             // reset together with active
     sa.rc_list = (int32_t *)(ws + L.rclist);
-    sa.kinds = (unsigned *)(ws + L.active + 16);
+    sa.kinds = kinds;
+    sa.rec = ca.rec;
     if (!ctx->host_active) {
         e = hipHostMalloc((void **)&ctx->host_active, 4 * sizeof(unsigned));
         if (e != hipSuccess) return hip_fail(ctx, e, "hipHostMalloc");
     }
-    if ((e = hipMemsetAsync(sa.kinds, 0, 2 * sizeof(unsigned), st)) != hipSuccess)
-        return hip_fail(ctx, e, "hipMemsetAsync");
     sa.moments = use_moments;
     sa.mom = (double2 *)(ws + L.mom);
     sa.dphi = (double *)(ws + L.dphi);

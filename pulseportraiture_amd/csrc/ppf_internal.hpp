@@ -42,14 +42,27 @@ struct XspecArgs {
     const uint8_t *xtile;        // [nsub] or null
     int xnh;
     // GetTOAs guess spectrum fused into the wave pass (gflag[s] set, see
-    // k_gflag): sum_n w_n D_nk exp(2 pi i k dphi_n(DM_guess)) of the block's
+    // k_classify): sum_n w_n D_nk exp(2 pi i k dphi_n(DM_guess)) of the block's
     // rows for the harmonics guess_pairs() covers, per (sub-int, block)
     const uint8_t *gflag;        // [nsub] or null (no fused guess)
     double2 *gpart;              // [nsub][nblk][guess_slots(log2N)]
     double *gw;                  // [nsub][nblk][3] (sum w, count, sum w^2 errs_FT^2)
     const double *guess_weights, *guess_DM, *nu_fits;
     int guess_ref;
+    // k_xspec_w2: what k_classify formed once per sub-int, read instead of
+    // the byte flags and of a frequency reduction per workgroup
+    const int32_t *cls;          // [nsub] kCls* bits
+    const double *rec;           // [nsub][kRecN] (kRec*)
+    // bounded launch of the harmonic-major instantiation (PPF_OPT_NO_X): the
+    // workgroups stride over list entries x blocks; null: the full grid
+    const int32_t *list;         // [*nlist] sub-ints with a harmonic-major slot
+    const unsigned *nlist;
 };
+
+// k_classify's per-sub-int class bits and record
+constexpr int kClsNeedX = 1, kClsTile = 2, kClsGflag = 4;
+// nu_ref^-2 of the guess, Dconst DM_guess / P, usable channels, their mean frequency
+constexpr int kRecNuRefM2 = 0, kRecDg = 1, kRecCnt = 2, kRecNuMean = 3, kRecN = 4;
 
 // Fused guess harmonics of an N = 2^log2N point wave FFT: k < 64 guess_npl
 // (the FFTFIT sums stop at the mean model's cutoff; a sub-int whose cutoff
@@ -70,6 +83,10 @@ struct DsumArgs {
     const uint8_t *gflag;        // [nsub]: 1 = fused into k_xspec_w (skip), or null
     double *nuref;               // [nsub] nu_ref^-2 per sub-int (k_nu_ref), or null:
                                  // every workgroup reduces the frequencies itself
+    // bounded launch of k_dsum_w (fused guess with PPF_OPT_NO_X): the
+    // workgroups stride over list entries x blocks; null: the full grid
+    const int32_t *list;         // [*nlist] sub-ints without gflag
+    const unsigned *nlist;
 };
 
 // k_xmom: fused re-FFT + cross spectrum + Taylor moments (no X in HBM)
@@ -177,6 +194,7 @@ struct SolveArgs {
     int xnh;                     // harmonics per channel of an X slot (XspecArgs::xnh)
     unsigned *rc_count;          // sub-ints k_tr_mom sent back for a new moment centre
     int32_t *rc_list;            // [nsub] their indices (slot order of the atomic)
+    const double *rec;           // [nsub][kRecN] (k_classify): usable channels, mean frequency
 };
 
 struct RotateArgs {
@@ -390,24 +408,45 @@ hipError_t launch_twiddles(int N, double2 *T, double2 *T2, hipStream_t st);
 hipError_t launch_rfft_rows(const RfftArgs &a, int64_t nrows, hipStream_t st);
 hipError_t launch_xspec(const XspecArgs &a, hipStream_t st);
 hipError_t launch_guess(const GuessArgs &a, hipStream_t st);
-hipError_t launch_gflag(int nsub, int nchan, const uint8_t *needx, const int32_t *KC,
-                        const int32_t *model_index, int klim, uint8_t *gflag, hipStream_t st);
 hipError_t launch_dsum(const DsumArgs &a, hipStream_t st);
 bool xspec_wave_supported(int log2N, int cb);
+// channels per workgroup of the spectrum pass where it has a block size of
+// its own (k_xspec_w2: 64), else 0: the layout's
+int xspec_own_cb(int log2N);
 // wave-per-row mixed-radix spectrum pass (k_xspec_wm): nbin / 2 not a power
 // of two, <= 1024 (prime factors above 7 on the generic-radix stage)
 bool xspec_wm_supported(int nbin);
-// the spectrum pass accumulates the GetTOAs guess at this FFT size (k_gflag)
+// the spectrum pass accumulates the GetTOAs guess at this FFT size (k_classify: gflag)
 bool xspec_guess_fused_n(int log2N);
 hipError_t launch_xspec_wm(const XspecArgs &a, hipStream_t st);
 hipError_t launch_xspec_wave(const XspecArgs &a, hipStream_t st);
 hipError_t launch_xmom(const XmomArgs &a, bool full, hipStream_t st);
 hipError_t launch_btab(int N, double *Bt, hipStream_t st);
-// xtile (or null): 1 for the sub-ints whose X slot is tiled (the moment-mode
-// ones: no scattering), 0 for those k_pass streams
-hipError_t launch_classify(int nsub, const int32_t *fit_flags, const double *init, int log10_tau,
-                           int fused, int xcap, uint8_t *needx, int32_t *xslot, uint8_t *xtile,
-                           hipStream_t st);
+// k_classify: per sub-int, which stream the cross spectrum and in which slot,
+// whether the guess rides in the spectrum pass, and the scalars every later
+// kernel would otherwise reduce from the frequency list again
+struct ClassifyArgs {
+    int nsub, nchan, log10_tau, fused, xcap;
+    const int32_t *fit_flags;
+    const double *init, *freqs, *P, *nu_fits;
+    const uint8_t *mask;
+    const int32_t *model_index;
+    const int32_t *KC;           // [nmodel][nchan]
+    int klim;                    // gflag: max_n KC <= klim; < 0: no fused guess (gflag null)
+    const double *guess_DM;      // or null (no guess)
+    int guess_ref;
+    uint8_t *needx;              // [nsub]
+    int32_t *xslot;              // [nsub]
+    uint8_t *xtile;              // [nsub] or null: 1 = tiled slot (moment mode), 0 = k_pass streams it
+    uint8_t *gflag;              // [nsub] or null
+    int32_t *cls;                // [nsub] kCls* bits
+    double *rec;                 // [nsub][kRecN]
+    // the sub-ints with a harmonic-major slot (needx, not tiled) and those
+    // without gflag, in sub-int order, with their counts
+    int32_t *hm_list, *ng_list;
+    unsigned *counts;            // [0] arrival ticket (zero on entry), [1] hm, [2] ng
+};
+hipError_t launch_classify(const ClassifyArgs &a, hipStream_t st);
 // k_xspec_w2 writes the moment-mode sub-ints' X tiled (X[k/8][n][k%8]) for
 // k_moments: 1024-point rows on k_xspec_w2, unless PPF_XTILE=0 (environment,
 // read once) selects the harmonic-major slots and the round's write-out

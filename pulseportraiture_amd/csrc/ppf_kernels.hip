@@ -681,7 +681,7 @@ __global__ __launch_bounds__(64) void k_nu_ref(DsumArgs a) {
 template <int DT, int LOG2NB>
 // (capped at four waves per SIMD -- 128 VGPRs, nine spills -- it measured
 // 8.2 vs 7.1 ms per 10,000 C2 sub-ints)
-__global__ __launch_bounds__(kBlock) void k_dsum_w(DsumArgs a) {
+__device__ __forceinline__ void dsum_w_block(const DsumArgs &a, const int s, const int blk) {
     using ElT = typename std::conditional<DT == 0, float, double>::type;
     // native vector types: arrays of HIP_vector_type structs carried across
     // the row loop are not promoted to VGPRs (they land in scratch)
@@ -693,7 +693,6 @@ __global__ __launch_bounds__(kBlock) void k_dsum_w(DsumArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dlds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     ElT *xs = reinterpret_cast<ElT *>(dlds) + wave * NB;
-    const int s = blockIdx.x / a.nblkd, blk = blockIdx.x % a.nblkd;
     if (a.gflag && a.gflag[s]) return;        // guess fused into k_xspec_w
     const uint8_t *mask = a.mask ? a.mask + (int64_t)s * a.nchan : nullptr;
     const double *fr = a.freqs + (int64_t)s * a.nchan;
@@ -785,6 +784,25 @@ __global__ __launch_bounds__(kBlock) void k_dsum_w(DsumArgs a) {
         for (int w2 = 0; w2 < kWaves; ++w2) { s0 += wred[w2 * 2]; s1 += wred[w2 * 2 + 1]; }
         a.gw[((int64_t)s * a.nblkd + blk) * 2 + 0] = s0;
         a.gw[((int64_t)s * a.nblkd + blk) * 2 + 1] = s1;
+    }
+}
+
+template <int DT, int LOG2NB>
+__global__ __launch_bounds__(kBlock) void k_dsum_w(DsumArgs a) {
+    dsum_w_block<DT, LOG2NB>(a, blockIdx.x / a.nblkd, blockIdx.x % a.nblkd);
+}
+
+// The sub-ints of DsumArgs::list only (a call that expects the guess of
+// every sub-int fused into the spectrum pass): a grid of a few workgroups
+// per CU strides over list entries x blocks, each processed as by k_dsum_w;
+// an empty list costs one short launch.
+constexpr int kDsumListGrid = 1024;
+template <int DT, int LOG2NB>
+__global__ __launch_bounds__(kBlock) void k_dsum_w_list(DsumArgs a) {
+    const int64_t items = (int64_t)*a.nlist * a.nblkd;
+    for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+        dsum_w_block<DT, LOG2NB>(a, a.list[it / a.nblkd], (int)(it % a.nblkd));
+        __syncthreads();      // the block's LDS reads are done before the next one's writes
     }
 }
 
@@ -1624,8 +1642,11 @@ static void launch_dsum_w(const DsumArgs &a, hipStream_t st) {
     constexpr int NB = 1 << L2;
     const size_t row = (size_t)kWaves * NB * (DT == 0 ? 4 : 8);
     const size_t lds = row > (size_t)NB * 8 ? row : (size_t)NB * 8;
-    hipLaunchKernelGGL((k_dsum_w<DT, L2>), dim3((unsigned)((int64_t)a.nsub * a.nblkd)), dim3(kBlock),
-                       lds, st, a);
+    if (a.list)
+        hipLaunchKernelGGL((k_dsum_w_list<DT, L2>), dim3(kDsumListGrid), dim3(kBlock), lds, st, a);
+    else
+        hipLaunchKernelGGL((k_dsum_w<DT, L2>), dim3((unsigned)((int64_t)a.nsub * a.nblkd)), dim3(kBlock),
+                           lds, st, a);
 }
 
 hipError_t launch_dsum(const DsumArgs &a_in, hipStream_t st) {

@@ -140,75 +140,137 @@ __device__ void wave_gates(const double *lnr, const uint8_t *mask, int nchan, do
     g_alpha = s2 != 0.0;
 }
 
-// k_classify: which sub-ints need the cross spectrum X in HBM (scattering
-// fits, which k_pass streams; every fit when the moments are taken from X,
-// i.e. off the fused k_xmom_g path), and X's slot for each of them: the
-// slots are the order of those sub-ints (one workgroup, a running
-// exclusive scan), so the workspace holds X only for the sub-ints that use
-// it.  Past the caller's xcap: slot -2, and k_tr_init fails the fit with
-// PPF_ST_NOSPACE.  Same scattering test as k_tr_init's `scat`.
+// k_classify: everything later kernels need to know about a sub-int as a
+// whole, formed once and in one launch: the routing flags, and the
+// frequency sums that k_xspec_w2 (per workgroup) and k_tr_init would
+// otherwise reduce again.
+//
+// Part 1, one wave per sub-int: the usable channels' count and mean
+// frequency (k_tr_init's fixed-order sum, lane l: channels l + 64 j, then
+// wave_sum), nu_ref^-2 and Dconst DM_guess / P of the GetTOAs guess
+// (nu_ref_m2 of ppf_kernels.hip, the same arithmetic: the same bits), whether
+// the sub-int's model has no harmonic above the fused guess range (max_n
+// KC[model][n] <= klim: the FFTFIT sums of k_guess stop at that cutoff), and
+// the scattering test (k_tr_init's `scat`).
+//
+// Part 2, the workgroup that arrives last, over all sub-ints in order: which
+// sub-ints need the cross spectrum X in HBM (scattering fits, which k_pass
+// streams; every fit when the moments are taken from X, i.e. off the fused
+// k_xmom_g path), and X's slot for each of them: the slots are the order of
+// those sub-ints (a running exclusive scan), so the workspace holds X only
+// for the sub-ints that use it.  Past the caller's xcap: slot -2, and
+// k_tr_init fails the fit with PPF_ST_NOSPACE.  gflag: the sub-ints whose
+// GetTOAs guess spectrum k_xspec_w accumulates (ppf_xspec.hip, GS): those it
+// streams (needx) with the model test of part 1; the others take k_dsum.
+// The same scan compacts the two lists the bounded launches stride over
+// (sub-int order: nothing depends on timing).
+//
+// Hand-over between the parts: every storing wave waits for its stores, one
+// lane per workgroup releases at agent scope and takes a ticket; the last
+// one acquires (its CU's L1 holds no line written elsewhere after that)
+// before the workgroup's other waves pass the barrier.
 constexpr int kClassifyBlock = 1024;
-__global__ __launch_bounds__(kClassifyBlock) void k_classify(int nsub, const int32_t *fit_flags,
-                                                             const double *init, int log10_tau,
-                                                             int fused, int xcap, uint8_t *needx,
-                                                             int32_t *xslot, uint8_t *xtile) {
-    __shared__ int wtot[kClassifyBlock / 64];
+constexpr int kClsOk = 8;     // part 1 -> part 2: the model passes the fused-guess test
+__global__ __launch_bounds__(kClassifyBlock) void k_classify(ClassifyArgs a) {
+    constexpr int NW = kClassifyBlock / 64;
+    __shared__ int wtot[3][NW];
+    __shared__ int is_last;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int base_slot = 0;
-    for (int s0 = 0; s0 < nsub; s0 += kClassifyBlock) {
+    {
+        const int s = blockIdx.x * NW + wave;
+        if (s < a.nsub) {
+            const double *fr = a.freqs + (int64_t)s * a.nchan;
+            const uint8_t *mask = a.mask ? a.mask + (int64_t)s * a.nchan : nullptr;
+            double sf = 0.0, cnt = 0.0;
+            for (int n = lane; n < a.nchan; n += 64)
+                if (!mask || mask[n]) { sf += fr[n]; cnt += 1.0; }
+            sf = wave_sum(sf); cnt = wave_sum(cnt);
+            double mx = 0.0;
+            if (a.klim >= 0) {
+                const int64_t m = a.model_index ? a.model_index[s] : 0;
+                for (int n = lane; n < a.nchan; n += 64) mx = fmax(mx, (double)a.KC[m * a.nchan + n]);
+                mx = wave_max(mx);
+            }
+            if (lane == 0) {
+                const double mu = sf / cnt;
+                double nu_ref_m2 = 1.0 / (mu * mu);
+                if (a.guess_ref) {                   // ppalign: dedisperse at nu_fit
+                    const double nf = a.nu_fits[(int64_t)s * 3];
+                    if (nf == nf) nu_ref_m2 = 1.0 / (nf * nf);
+                }
+                double *rec = a.rec + (int64_t)s * kRecN;
+                rec[kRecNuRefM2] = nu_ref_m2;
+                rec[kRecDg] = a.guess_DM ? kDconst * a.guess_DM[s] / a.P[s] : 0.0;
+                rec[kRecCnt] = cnt;
+                rec[kRecNuMean] = mu;
+                const double x3 = a.init[(int64_t)s * 5 + 3];
+                const double tau0 = a.log10_tau ? pow(10.0, x3) : x3;
+                const bool scat =
+                    a.fit_flags[(int64_t)s * 5 + 3] || a.fit_flags[(int64_t)s * 5 + 4] || tau0 != 0.0;
+                a.cls[s] = ((!a.fused || scat) ? kClsNeedX : 0) |
+                           (scat ? 0 : kClsTile) |     // moment mode: k_moments reads the slot
+                           ((a.klim >= 0 && mx <= (double)a.klim) ? kClsOk : 0);
+            }
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned t = __hip_atomic_fetch_add(a.counts, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        is_last = t == gridDim.x - 1 ? 1 : 0;
+        if (is_last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+    }
+    __syncthreads();
+    if (!is_last) return;
+    int base[3] = {0, 0, 0};             // running counts: X slots, hm_list, ng_list
+    for (int s0 = 0; s0 < a.nsub; s0 += kClassifyBlock) {
         const int s = s0 + tid;
-        int need = 0, tile = 0;
-        if (s < nsub) {
-            const double x3 = init[(int64_t)s * 5 + 3];
-            const double tau0 = log10_tau ? pow(10.0, x3) : x3;
-            const bool scat =
-                fit_flags[(int64_t)s * 5 + 3] || fit_flags[(int64_t)s * 5 + 4] || tau0 != 0.0;
-            need = (!fused || scat) ? 1 : 0;
-            tile = scat ? 0 : 1;             // moment mode: k_moments reads the slot
-        }
-        const unsigned long long bal = __ballot(need);
-        const int below = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wtot[wave] = __popcll(bal);
+        const int pre = s < a.nsub ? a.cls[s] : 0;
+        const int need = pre & kClsNeedX ? 1 : 0;
+        unsigned long long bal = __ballot(need);
+        const int slot_w = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) wtot[0][wave] = __popcll(bal);
         __syncthreads();
-        int off = base_slot;
-        for (int w = 0; w < wave; ++w) off += wtot[w];
-        int chunk = 0;
-        for (int w = 0; w < kClassifyBlock / 64; ++w) chunk += wtot[w];
-        if (s < nsub) {
-            const int slot = off + below;
-            needx[s] = (need && slot < xcap) ? 1 : 0;
-            xslot[s] = need ? (slot < xcap ? slot : -2) : -1;
-            if (xtile) xtile[s] = (uint8_t)tile;
+        int slot = base[0] + slot_w;
+        for (int w = 0; w < wave; ++w) slot += wtot[0][w];
+        for (int w = 0; w < NW; ++w) base[0] += wtot[0][w];
+        const int nx = (need && slot < a.xcap) ? 1 : 0;
+        const int tile = (a.xtile && (pre & kClsTile)) ? 1 : 0;
+        const int gf = (a.gflag && nx && (pre & kClsOk)) ? 1 : 0;
+        const int in[2] = {(s < a.nsub && nx && !tile) ? 1 : 0,          // a harmonic-major slot
+                           (s < a.nsub && a.gflag && !gf) ? 1 : 0};     // the guess through k_dsum
+        int pos[2];
+        for (int j = 0; j < 2; ++j) {
+            bal = __ballot(in[j]);
+            pos[j] = __popcll(bal & ((1ull << lane) - 1ull));
+            if (lane == 0) wtot[1 + j][wave] = __popcll(bal);
         }
-        base_slot += chunk;
+        __syncthreads();
+        for (int j = 0; j < 2; ++j) {
+            pos[j] += base[1 + j];
+            for (int w = 0; w < wave; ++w) pos[j] += wtot[1 + j][w];
+            for (int w = 0; w < NW; ++w) base[1 + j] += wtot[1 + j][w];
+        }
+        if (s < a.nsub) {
+            a.needx[s] = (uint8_t)nx;
+            a.xslot[s] = need ? (nx ? slot : -2) : -1;
+            if (a.xtile) a.xtile[s] = (pre & kClsTile) ? 1 : 0;
+            if (a.gflag) a.gflag[s] = (uint8_t)gf;
+            a.cls[s] = (nx ? kClsNeedX : 0) | (tile ? kClsTile : 0) | (gf ? kClsGflag : 0);
+            if (in[0]) a.hm_list[pos[0]] = s;
+            if (in[1]) a.ng_list[pos[1]] = s;
+        }
         __syncthreads();
     }
-}
-
-// k_gflag: the sub-ints whose GetTOAs guess spectrum k_xspec_w accumulates
-// (ppf_xspec.hip, GS): those it streams (needx) whose mean model has no
-// harmonic above the fused range (max_n KC[model][n] <= klim, the FFTFIT sums
-// of k_guess stop at that cutoff); the others take k_dsum.
-__global__ __launch_bounds__(kBlock) void k_gflag(int nsub, int nchan, const uint8_t *needx,
-                                                  const int32_t *KC, const int32_t *model_index,
-                                                  int klim, uint8_t *gflag) {
-    const int s = blockIdx.x * kBlock + threadIdx.x;
-    if (s >= nsub) return;
-    int ok = 0;
-    if (!needx || needx[s]) {
-        const int64_t m = model_index ? model_index[s] : 0;
-        int mx = 0;
-        for (int n = 0; n < nchan; ++n) mx = max(mx, KC[m * nchan + n]);
-        ok = mx <= klim ? 1 : 0;
+    if (tid == 0) {
+        a.counts[1] = (unsigned)base[1];
+        a.counts[2] = (unsigned)base[2];
     }
-    gflag[s] = (uint8_t)ok;
-}
-
-hipError_t launch_gflag(int nsub, int nchan, const uint8_t *needx, const int32_t *KC,
-                        const int32_t *model_index, int klim, uint8_t *gflag, hipStream_t st) {
-    hipLaunchKernelGGL(k_gflag, dim3((unsigned)((nsub + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                       nsub, nchan, needx, KC, model_index, klim, gflag);
-    return hipGetLastError();
 }
 
 // ===========================================================================
@@ -221,10 +283,8 @@ __global__ __launch_bounds__(kBlock) void k_tr_init(SolveArgs a) {
     const double *fr = a.freqs + (int64_t)s * a.nchan;
     const uint8_t *mask = a.mask ? a.mask + (int64_t)s * a.nchan : nullptr;
     // (runs before the spectrum kernels: nothing here reads chan[])
-    double sf = 0.0, cnt = 0.0;
-    for (int n = lane; n < a.nchan; n += 64)
-        if (!mask || mask[n]) { sf += fr[n]; cnt += 1.0; }
-    sf = wave_sum(sf); cnt = wave_sum(cnt);
+    // the usable channels' count and mean frequency: k_classify's record
+    const double cnt = a.rec[(int64_t)s * kRecN + kRecCnt];
     TRState &S = a.state[s];
     int flagmask = 0, nf = 0;
     for (int i = 0; i < 5; ++i)
@@ -249,7 +309,7 @@ __global__ __launch_bounds__(kBlock) void k_tr_init(SolveArgs a) {
     }
     const double tau0 = a.log10_tau ? pow(10.0, x[3]) : x[3];
     const int scat = ((flagmask & 0x18) || tau0 != 0.0) ? 1 : 0;
-    const double nu_mean = sf / cnt;
+    const double nu_mean = a.rec[(int64_t)s * kRecN + kRecNuMean];
     double nu_fit[3];
     for (int i = 0; i < 3; ++i) {
         nu_fit[i] = a.nu_fits[(int64_t)s * 3 + i];
@@ -1962,11 +2022,9 @@ __global__ __launch_bounds__(PB) void k_postfit(SolveArgs a) {
 // ===========================================================================
 // launchers
 // ===========================================================================
-hipError_t launch_classify(int nsub, const int32_t *fit_flags, const double *init, int log10_tau,
-                           int fused, int xcap, uint8_t *needx, int32_t *xslot, uint8_t *xtile,
-                           hipStream_t st) {
-    hipLaunchKernelGGL(k_classify, dim3(1), dim3(kClassifyBlock), 0, st, nsub, fit_flags, init,
-                       log10_tau, fused, xcap, needx, xslot, xtile);
+hipError_t launch_classify(const ClassifyArgs &a, hipStream_t st) {
+    constexpr int NW = kClassifyBlock / 64;
+    hipLaunchKernelGGL(k_classify, dim3((unsigned)((a.nsub + NW - 1) / NW)), dim3(kClassifyBlock), 0, st, a);
     return hipGetLastError();
 }
 

@@ -112,7 +112,7 @@ __host__ __device__ constexpr int tw_slots() {
 template <int LOG2N>
 __host__ __device__ constexpr int xspec_slw() { return wfft::buf_slots<LOG2N>() + 2; }
 
-// GS: the sub-ints with gflag set (k_gflag: every channel's harmonic cutoff
+// GS: the sub-ints with gflag set (k_classify: every channel's harmonic cutoff
 // below NL = 64 guess_npl) also accumulate the GetTOAs guess spectrum
 // (pptoas.py:461-464 in the Fourier domain, as rotate_data does it):
 // G_k = sum_n w_n D_nk exp(2 pi i k dphi_n), dphi_n = Dconst DM_guess / P
@@ -129,7 +129,7 @@ __host__ __device__ constexpr int xspec_slw() { return wfft::buf_slots<LOG2N>() 
 // The fused guess runs at 1024 points only: below, its extra registers cost a
 // wave per SIMD or spill, and those shapes take k_dsum_w.  (At 512 points,
 // round 5, C5 per 500 sub-ints in one call: the model reaches harmonic ~430 of
-// 513, above the NL = 192 guess harmonics, so k_gflag sets no sub-int and the
+// 513, above the NL = 192 guess harmonics, so k_classify sets no sub-int and the
 // variant only costs its registers: k_xspec_w<9> 26.5 vs 22.0 ms, 90.1 vs
 // 84.7 ms per step.  Removed.)
 bool xspec_guess_fused_n(int log2N) { return log2N == 10; }
@@ -875,9 +875,9 @@ constexpr int kX2SL = wf2::kXSlots + wf2::kSpSlots;       // 1072 slots per wave
 constexpr int kX2IE = 1041;                               // the row's 1/errs_FT^2 (.x)
 __device__ __forceinline__ int x2slot(int k) { return k + (k >> 6); }   // k <= 1024 -> <= 1040
 
+// One workgroup's block: channels [cb a.cb, (cb + 1) a.cb) of sub-int s.
 template <int DT, bool GS, bool TL>
-__global__ __launch_bounds__(64 * kX2W) __attribute__((amdgpu_waves_per_eu(2)))
-void k_xspec_w2(XspecArgs a) {
+__device__ __forceinline__ void xspec_w2_block(const XspecArgs &a, const int s, const int cb) {
     constexpr int N = 1024, NH = N + 1;
     // TL guess sums: per-wave partials in registers, no barrier in the round loop
     constexpr bool GR = TL;
@@ -895,114 +895,9 @@ void k_xspec_w2(XspecArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     double2 *buf = lds + wave * kX2SL;
 
-    int s, cb;
-    block_map(a.xcd_swizzle, a.nblk, s, cb, a.nsub);
-    if (a.needx && !a.needx[s]) return;               // uniform: moment-mode sub-int (or no slot)
-    if (a.xtile ? (a.xtile[s] != 0) != TL : TL) return;   // uniform: the other instantiation's slot layout
     const int cbase = cb * a.cb, cend = min(a.nchan, cbase + a.cb);
-    const int nround = (a.cb + kX2W - 1) / kX2W;
-    const int mi = a.model_index ? a.model_index[s] : 0;
-    const uint8_t *mask = a.mask ? a.mask + (int64_t)s * a.nchan : nullptr;
-    const double sqrtN = sqrt((double)N);
+    const int nround = (cend - cbase + kX2W - 1) / kX2W;
     const RowT *rows = reinterpret_cast<const RowT *>(a.data);
-    const wf2::Seeds sd = wf2::make_seeds(lane0);
-    // post-pass twiddle e^{-i pi k / N} of the lane's first pair, step
-    // e^{-i pi 64 / N}
-    double2 wA0, wstep;
-    {
-        double sn, cs;
-        sincospi(-(double)wf2::pair_k0(lane0) / (double)N, &sn, &cs);
-        wA0 = cmk(cs, sn);
-        sincospi(-64.0 / (double)N, &sn, &cs);
-        wstep = cmk(cs, sn);
-    }
-    double2 *Xs = a.X + (int64_t)(a.xslot ? a.xslot[s] : s) * a.xnh * a.nchan;
-    int kw = NH;
-    if (a.KC) {
-        const int nn = (cbase & ~63) + lane0;
-        kw = (int)wave_max(nn < a.nchan ? (double)a.KC[(int64_t)mi * a.nchan + nn] : 1.0);
-    }
-    // TL: the wave's own channel n, harmonics below kw rounded up to whole
-    // tiles (zeros past kw, and for a masked channel), lane l: harmonics l +
-    // 64 j -- per store instruction 8 tiles, each one whole 128-byte line
-    auto store_tiles = [&](int n, const double2 *b, double ie2, bool ok) {
-        const int kwp = (kw + kXTile - 1) & ~(kXTile - 1);
-        double2 *Xn = Xs + (int64_t)n * kXTile + (lane0 & (kXTile - 1));
-#pragma unroll 1
-        for (int h = lane0; h < kwp; h += 64) {
-            const double2 v = (ok && h < kw) ? cscale(b[x2slot(h)], ie2) : cmk(0.0, 0.0);
-            __builtin_nontemporal_store(vd2{v.x, v.y},
-                                        reinterpret_cast<vd2 *>(Xn + (int64_t)(h >> 3) * a.nchan * kXTile));
-        }
-    };
-    const int mlane = (cbase + lane0 < cend && (!mask || mask[cbase + lane0])) ? 1 : 0;
-    auto usable = [&](int n) {
-        return n < cend && __builtin_amdgcn_readlane(mlane, n - cbase) != 0;
-    };
-    constexpr int NL = 64 * guess_npl(10);
-    bool gon = false;
-    double g_Dg = 0.0, g_nrm2 = 0.0, g_w2e2 = 0.0;
-    double2 *gacc = lds + kX2W * kX2SL;
-    if constexpr (GS) {
-        gon = a.gflag[s] != 0;                         // uniform
-        if (gon) {
-            if constexpr (!GR)
-                for (int t = threadIdx.x; t < NL; t += 64 * kX2W) gacc[t] = cmk(0.0, 0.0);
-            const double *fr = a.freqs + (int64_t)s * a.nchan;
-            double v0 = 0.0, v1 = 0.0;
-            for (int nn = lane0; nn < a.nchan; nn += 64)
-                if (!mask || mask[nn]) { v0 += fr[nn]; v1 += 1.0; }
-            v0 = wave_sum(v0);
-            v1 = wave_sum(v1);
-            const double mu = v0 / v1;
-            double nu_ref_m2 = 1.0 / (mu * mu);
-            if (a.guess_ref) {
-                const double nf = a.nu_fits[(int64_t)s * 3];
-                if (nf == nf) nu_ref_m2 = 1.0 / (nf * nf);
-            }
-            g_Dg = readlane_d(kDconst * a.guess_DM[s] / a.P[s], 0);
-            g_nrm2 = readlane_d(nu_ref_m2, 0);
-            if constexpr (!GR) __syncthreads();
-        }
-    }
-    // GR: the wave's guess partials, slot i of every row it transforms (the
-    // slot's harmonic hl is fixed per lane; only 1 <= hl < NL is written out
-    // at the end -- 7 of the 8 slots of a lane, the eighth sums unused terms)
-    double2 gr[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) gr[i] = cmk(0.0, 0.0);
-    // the block's per-channel scalars in lane registers (lane l: channel
-    // cbase + l): a global load of them inside the round loop would wait,
-    // vmcnt being in order, for the next row's prefetch
-    const int nl = cbase + lane0;
-    const bool lin = nl < cend;
-    const double ch_mpow = lin ? a.Mpow[(int64_t)mi * a.nchan + nl] : 0.0;
-    const double ch_err = (a.errs && lin) ? a.errs[(int64_t)s * a.nchan + nl] : 0.0;
-    double ch_wn = 0.0, ch_dg = 0.0;
-    if (GS && gon && lin) {
-        ch_wn = a.guess_weights[(int64_t)s * a.nchan + nl];
-        const double f = a.freqs[(int64_t)s * a.nchan + nl];
-        ch_dg = g_Dg * (1.0 / (f * f) - g_nrm2);
-    }
-    // GR: the channel's unit phasor e^{2 pi i dphi_n} once, here: the row's
-    // phasors are its powers (below).  A cexp2pi per row keeps sincospi's
-    // polynomial constants in VGPRs across the whole round loop, which with
-    // the 32 registers of gr spilled 27 of them to scratch, reloaded one
-    // by one behind vmcnt(0) in every row
-    double2 ch_e1 = cmk(1.0, 0.0);
-    if constexpr (GR) {
-        if (GS && gon) ch_e1 = cexp2pi(ch_dg);
-    }
-    double2 *ltab = lds + kX2W * kX2SL;              // [4][64]: w1, v1, wA0, e1
-    if constexpr (LT) {
-        if (wave == 0) {
-            ltab[lane0] = sd.w1;
-            ltab[64 + lane0] = sd.v1;
-            ltab[128 + lane0] = wA0;
-            ltab[192 + lane0] = ch_e1;
-        }
-        __syncthreads();
-    }
     RowT zr[16];
     auto fetch = [&](int n) {
         const RowT *src = rows + ((int64_t)s * a.nchan + n) * N;
@@ -1024,7 +919,121 @@ void k_xspec_w2(XspecArgs a) {
         for (int q = 0; q < 16; ++q) asm volatile("" ::"v"(zr[q].x), "v"(zr[q].y));
     };
     int n = cbase + wave;
-    fetch_c(n);
+    // TL (the launch whose every workgroup has rows at C2): the first row's
+    // loads before anything else -- they need only s, cbase and the wave --
+    // so that the whole prologue below runs under their latency.  The
+    // sub-int's class and scalars come by scalar loads (k_classify's cls and
+    // rec), which do not queue behind them.
+    if constexpr (TL) fetch_c(n);
+    const int cls = a.cls[s];
+    const int mi = a.model_index ? a.model_index[s] : 0;
+    const int xsl = a.xslot ? a.xslot[s] : s;
+    double g_Dg = 0.0, g_nrm2 = 0.0, g_w2e2 = 0.0;
+    if constexpr (GS) {
+        g_Dg = readfirst_d(a.rec[(int64_t)s * kRecN + kRecDg]);
+        g_nrm2 = readfirst_d(a.rec[(int64_t)s * kRecN + kRecNuRefM2]);
+    }
+    if (a.needx && !(cls & kClsNeedX)) return;         // uniform: moment-mode sub-int (or no slot)
+    if (((cls & kClsTile) != 0) != TL) return;         // uniform: the other instantiation's slot layout
+    const bool gon = GS && (cls & kClsGflag) != 0;     // uniform
+    const uint8_t *mask = a.mask ? a.mask + (int64_t)s * a.nchan : nullptr;
+    // the block's per-channel scalars in lane registers (lane l: channel
+    // cbase + l): a global load of them inside the round loop would wait,
+    // vmcnt being in order, for the next row's prefetch.  All of them are
+    // loaded unconditionally (a lane past the block takes its last channel
+    // and drops the value) and together: one round trip
+    const int nl = cbase + lane0;
+    const bool lin = nl < cend;
+    const int nlc = lin ? nl : cend - 1;
+    const int64_t scn = (int64_t)s * a.nchan + nlc;
+    const int nkw = (cbase & ~63) + lane0;
+    int ld_kc = a.KC ? a.KC[(int64_t)mi * a.nchan + (nkw < a.nchan ? nkw : a.nchan - 1)] : 0;
+    int ld_mask = mask ? mask[nlc] : 1;
+    double ld_mpow = a.Mpow[(int64_t)mi * a.nchan + nlc];
+    double ld_err = a.errs ? a.errs[scn] : 0.0;
+    double ld_wn = 0.0, ld_f = 1.0;
+    if constexpr (GS) {
+        ld_wn = a.guess_weights[scn];
+        ld_f = a.freqs[scn];
+    }
+    const double sqrtN = sqrt((double)N);
+    const wf2::Seeds sd = wf2::make_seeds(lane0);
+    // post-pass twiddle e^{-i pi k / N} of the lane's first pair, step
+    // e^{-i pi 64 / N}
+    double2 wA0, wstep;
+    {
+        double sn, cs;
+        sincospi(-(double)wf2::pair_k0(lane0) / (double)N, &sn, &cs);
+        wA0 = cmk(cs, sn);
+        sincospi(-64.0 / (double)N, &sn, &cs);
+        wstep = cmk(cs, sn);
+    }
+    // (the first use of the loaded values, behind the lane constants above:
+    // converted or compared where it was loaded, under its pointer's null
+    // test, each value was waited for on its own -- vmcnt(0), a round trip
+    // each behind the row in flight)
+    asm volatile("" : "+v"(ld_kc), "+v"(ld_mask), "+v"(ld_mpow), "+v"(ld_err), "+v"(ld_wn), "+v"(ld_f));
+    double2 *Xs = a.X + (int64_t)xsl * a.xnh * a.nchan;
+    int kw = NH;
+    if (a.KC) kw = (int)wave_max(nkw < a.nchan ? (double)ld_kc : 1.0);
+    // TL: the wave's own channel n, harmonics below kw rounded up to whole
+    // tiles (zeros past kw, and for a masked channel), lane l: harmonics l +
+    // 64 j -- per store instruction 8 tiles, each one whole 128-byte line
+    auto store_tiles = [&](int n, const double2 *b, double ie2, bool ok) {
+        const int kwp = (kw + kXTile - 1) & ~(kXTile - 1);
+        double2 *Xn = Xs + (int64_t)n * kXTile + (lane0 & (kXTile - 1));
+#pragma unroll 1
+        for (int h = lane0; h < kwp; h += 64) {
+            const double2 v = (ok && h < kw) ? cscale(b[x2slot(h)], ie2) : cmk(0.0, 0.0);
+            __builtin_nontemporal_store(vd2{v.x, v.y},
+                                        reinterpret_cast<vd2 *>(Xn + (int64_t)(h >> 3) * a.nchan * kXTile));
+        }
+    };
+    const int mlane = (lin && ld_mask) ? 1 : 0;
+    auto usable = [&](int n) {
+        return n < cend && __builtin_amdgcn_readlane(mlane, n - cbase) != 0;
+    };
+    constexpr int NL = 64 * guess_npl(10);
+    double2 *gacc = lds + kX2W * kX2SL;
+    if constexpr (GS && !GR) {
+        if (gon) {
+            for (int t = threadIdx.x; t < NL; t += 64 * kX2W) gacc[t] = cmk(0.0, 0.0);
+            __syncthreads();
+        }
+    }
+    // GR: the wave's guess partials, slot i of every row it transforms (the
+    // slot's harmonic hl is fixed per lane; only 1 <= hl < NL is written out
+    // at the end -- 7 of the 8 slots of a lane, the eighth sums unused terms)
+    double2 gr[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) gr[i] = cmk(0.0, 0.0);
+    const double ch_mpow = lin ? ld_mpow : 0.0;
+    const double ch_err = (a.errs && lin) ? ld_err : 0.0;
+    double ch_wn = 0.0, ch_dg = 0.0;
+    if (GS && gon && lin) {
+        ch_wn = ld_wn;
+        ch_dg = g_Dg * (1.0 / (ld_f * ld_f) - g_nrm2);
+    }
+    // GR: the channel's unit phasor e^{2 pi i dphi_n} once, here: the row's
+    // phasors are its powers (below).  A cexp2pi per row keeps sincospi's
+    // polynomial constants in VGPRs across the whole round loop, which with
+    // the 32 registers of gr spilled 27 of them to scratch, reloaded one
+    // by one behind vmcnt(0) in every row
+    double2 ch_e1 = cmk(1.0, 0.0);
+    if constexpr (GR) {
+        if (GS && gon) ch_e1 = cexp2pi(ch_dg);
+    }
+    double2 *ltab = lds + kX2W * kX2SL;              // [4][64]: w1, v1, wA0, e1
+    if constexpr (LT) {
+        if (wave == 0) {
+            ltab[lane0] = sd.w1;
+            ltab[64 + lane0] = sd.v1;
+            ltab[128 + lane0] = wA0;
+            ltab[192 + lane0] = ch_e1;
+        }
+        __syncthreads();
+    }
+    if constexpr (!TL) fetch_c(n);
     rows_ready();
     XP_INIT();
     for (int r = 0; r < nround; ++r, n += kX2W) {
@@ -1266,7 +1275,7 @@ void k_xspec_w2(XspecArgs a) {
             // (the staged guess terms are doubled: exact factor 1/2)
             if constexpr (!GR)
                 for (int t = threadIdx.x; t < NL; t += 64 * kX2W) gp[t] = cscale(gacc[t], 0.5);
-            const double gwl = mlane ? a.guess_weights[(int64_t)s * a.nchan + cbase + lane0] : 0.0;
+            const double gwl = mlane ? ch_wn : 0.0;      // (gon: the lane's guess weight)
             const double wsum = wave_sum(gwl), cnt = wave_sum(mlane ? 1.0 : 0.0);
             if constexpr (GR) {
                 // the wave's partials into its own buffer, slot hl (1 <= hl
@@ -1305,6 +1314,30 @@ void k_xspec_w2(XspecArgs a) {
                 o[2] = acc;
             }
         }
+    }
+}
+
+template <int DT, bool GS, bool TL>
+__global__ __launch_bounds__(64 * kX2W) __attribute__((amdgpu_waves_per_eu(2)))
+void k_xspec_w2(XspecArgs a) {
+    int s, cb;
+    block_map(a.xcd_swizzle, a.nblk, s, cb, a.nsub);
+    xspec_w2_block<DT, GS, TL>(a, s, cb);
+}
+
+// The harmonic-major slots of a call that expects few or none of them
+// (XspecArgs::list): a grid of a few workgroups per CU strides over list
+// entries x blocks, each processed exactly as k_xspec_w2<DT, GS, false> does
+// it; an empty list costs one short launch instead of nsub x nblk workgroups
+// that read a flag and leave.
+constexpr int kX2ListGrid = 512;
+template <int DT, bool GS>
+__global__ __launch_bounds__(64 * kX2W) __attribute__((amdgpu_waves_per_eu(2)))
+void k_xspec_w2_list(XspecArgs a) {
+    const int64_t items = (int64_t)*a.nlist * a.nblk;
+    for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+        xspec_w2_block<DT, GS, false>(a, a.list[it / a.nblk], (int)(it % a.nblk));
+        __syncthreads();      // the block's LDS reads are done before the next one's writes
     }
 }
 
@@ -1790,10 +1823,16 @@ static void launch_w(const XspecArgs &a, hipStream_t st) {
                                        lds + (size_t)256 * sizeof(double2), st, a);   // the [4][64] lane table
                 else hipLaunchKernelGGL((k_xspec_w2<DT, false, true>), g, b, lds, st, a);
             }
-            if (a.gflag)
-                hipLaunchKernelGGL((k_xspec_w2<DT, true, false>), g, b,
-                                   lds + (size_t)guess_slots(10) * sizeof(double2), st, a);
-            else hipLaunchKernelGGL((k_xspec_w2<DT, false, false>), g, b, lds, st, a);
+            // (bounded where the caller expects no such sub-int: a.list)
+            const dim3 gh = a.list ? dim3(kX2ListGrid) : g;
+            if (a.gflag) {
+                const size_t ldg = lds + (size_t)guess_slots(10) * sizeof(double2);
+                if (a.list) hipLaunchKernelGGL((k_xspec_w2_list<DT, true>), gh, b, ldg, st, a);
+                else hipLaunchKernelGGL((k_xspec_w2<DT, true, false>), gh, b, ldg, st, a);
+            } else {
+                if (a.list) hipLaunchKernelGGL((k_xspec_w2_list<DT, false>), gh, b, lds, st, a);
+                else hipLaunchKernelGGL((k_xspec_w2<DT, false, false>), gh, b, lds, st, a);
+            }
             return;
         }
     }
@@ -1804,6 +1843,11 @@ static void launch_w(const XspecArgs &a, hipStream_t st) {
                            lds + (size_t)guess_slots(L2) * sizeof(double2), st, a);
     else hipLaunchKernelGGL((k_xspec_w<L2, DT, false>), g, b, lds, st, a);
 }
+
+// k_xspec_w2 takes 64 channels per workgroup (its lane registers hold one
+// channel's scalars per lane; round 9: half the workgroups, prologues and
+// guess partials of the layout's 32)
+int xspec_own_cb(int log2N) { return (log2N == 10 && use_xspec2()) ? 64 : 0; }
 
 bool xspec_wave_supported(int log2N, int cb) {
     return log2N >= 7 && log2N <= 10 && cb % xsw<7>() == 0 && cb % xsw<10>() == 0 && cb % kXW == 0;
