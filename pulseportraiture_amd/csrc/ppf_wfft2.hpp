@@ -212,21 +212,64 @@ __device__ __forceinline__ void fft1024(double2 (&x)[16], double2 *xb, int lane,
 }
 
 // kappa held by a lane, and the harmonic of x[m] (the header's layout)
-__device__ __forceinline__ int lane_kappa(int lane) {
+constexpr __host__ __device__ int lane_kappa(int lane) {
     return lane < 32 ? lane : (lane == 32 ? 32 : 96 - lane);
 }
-__device__ __forceinline__ int out_index(int lane, int m) {
-    const int kap = lane_kappa(lane);
-    return lane < 32 ? kap + 64 * m : kap + 64 * (15 - m);
+constexpr __host__ __device__ int out_index(int lane, int m) {
+    return lane < 32 ? lane_kappa(lane) + 64 * m : lane_kappa(lane) + 64 * (15 - m);
 }
 
-// D: the real post-pass operands.  After pairs(): for slot i < 8 every lane
-// holds A[i] = Z[kA + 64 i] and B[i] = Z[N - kA - 64 i], kA = pair_k0(lane)
-// (lane 0: slot 0 is the pair (0, N) -> Z0 twice).  Lane 0 also returns
-// Z[N/2] in zm.  sp: the wave's kSpSlots side slots.
-__device__ __forceinline__ int pair_k0(int lane) {
-    return lane == 32 ? 32 : (lane & 31) + (lane >= 32 ? 512 : 0);
+// D: the real post-pass operands.  pairs() swaps x[i] of the lanes >= 32 with
+// x[15 - i] of the lanes < 32 (i < 8), after which slot i of EVERY lane holds
+// one pair (hl, N - hl) of the band 64 i <= hl <= 64 i + 63:
+//   hl = pair_hl(lane, i) = 64 i + lane_kappa(lane)
+//   lanes < 32  (pair_lo):  x[i] = Z[hl],     x[15 - i] = Z[N - hl]
+//   lanes >= 32:            x[i] = Z[N - hl], x[15 - i] = Z[hl]
+// so what a slot needs (X below the cutoff, the noise sum above its own, the
+// guess terms) is the same for the whole wave and can be skipped by a scalar
+// branch.  Lanes 0 and 32 (kappa = -kappa mod 64) hold both halves of their
+// pairs themselves: lane 0 (Z[64 i], Z[N - 64 i]) = its x[i] and x[(16 - i) &
+// 15] (slot 0: the pair (0, N) -> Z0 twice), lane 32 (Z[32 + 64 i], Z[N - 32
+// - 64 i]) = its x[15 - i] and x[i]; they take them back from the 32-slot
+// side buffer sp.  Lane 0 also returns Z[N/2] in zm.
+constexpr __host__ __device__ bool pair_lo(int lane) { return lane < 32; }
+constexpr __host__ __device__ int pair_hl(int lane, int i) { return 64 * i + lane_kappa(lane); }
+// harmonic of x[i] after pairs(): the twiddle e^{-i pi k / N} of the slot
+constexpr __host__ __device__ int pair_k(int lane, int i) {
+    return pair_lo(lane) ? pair_hl(lane, i) : kN - pair_hl(lane, i);
 }
+// the harmonics pairs() leaves in x[i] and x[15 - i], from what it moves:
+// (lane, register) of the transform's output that ends there, through
+// out_index
+constexpr __host__ __device__ int pair_src_a(int lane, int i) {
+    return lane == 0    ? out_index(0, i)
+           : lane == 32 ? out_index(32, i)                 // sp[16 + i]
+           : lane < 32  ? out_index(lane, i)               // kept
+                        : out_index(lane - 32, 15 - i);    // swapped in
+}
+constexpr __host__ __device__ int pair_src_b(int lane, int i) {
+    return lane == 0    ? out_index(0, (16 - i) & 15)      // sp[(16 - i) & 15]
+           : lane == 32 ? out_index(32, 15 - i)
+           : lane < 32  ? out_index(lane + 32, i)          // swapped in
+                        : out_index(lane, 15 - i);         // kept
+}
+constexpr __host__ __device__ bool pairs_ok() {
+    for (int i = 0; i < 8; ++i) {
+        bool seen[64] = {};
+        for (int lane = 0; lane < 64; ++lane) {
+            const int hl = pair_hl(lane, i);
+            const int za = pair_src_a(lane, i), zb = pair_src_b(lane, i);
+            if (hl < 64 * i || hl > 64 * i + 63 || seen[hl - 64 * i]) return false;    // the band, once
+            seen[hl - 64 * i] = true;
+            if ((za + zb) % kN != 0) return false;                                      // (hl, N - hl)
+            if ((pair_lo(lane) ? za : zb) != hl) return false;                          // which one is Z[hl]
+            if (pair_k(lane, i) % kN != za) return false;
+        }
+    }
+    return out_index(0, 8) == kN / 2;                                                   // zm
+}
+static_assert(pairs_ok(), "wf2::pairs: slot i of every lane is one pair (hl, N - hl) of band i");
+
 __device__ __forceinline__ void pairs(double2 (&x)[16], double2 *sp, int lane, double2 &zm) {
     const bool special = (lane & 31) == 0;
     if (special) {
@@ -235,16 +278,15 @@ __device__ __forceinline__ void pairs(double2 (&x)[16], double2 *sp, int lane, d
         for (int m = 0; m < 16; ++m) sp[b + m] = x[m];
     }
 #pragma unroll
-    for (int i = 0; i < 8; ++i) pswap<true>(x[i], x[i + 8]);
+    for (int i = 0; i < 8; ++i) pswap<true>(x[i], x[15 - i]);
     wfft::wave_sync();
     if (special) {
-        // lane 0: pairs (64 i, N - 64 i) of its own registers; lane 32:
-        // (32 + 64 i, N - 32 - 64 i), its registers reversed
+        // pair_src_a / pair_src_b of lanes 0 and 32, from their own registers
         const bool l0 = lane == 0;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            x[i] = sp[l0 ? i : 31 - i];
-            x[i + 8] = sp[l0 ? ((16 - i) & 15) : 16 + i];
+            x[i] = sp[l0 ? i : 16 + i];
+            x[15 - i] = sp[l0 ? ((16 - i) & 15) : 31 - i];
         }
         if (l0) zm = sp[8];
     }

@@ -843,7 +843,7 @@ __global__ __launch_bounds__(256) void k_model_sum(const double2 *Mft, int nchan
 //   - one LDS exchange inside the FFT instead of three, no natural-order
 //     write-back: the real post-pass takes each pair (Z_k, Z_{N-k}) from
 //     registers after a v_permlane32_swap (wf2::pairs);
-//   - each lane's slot i holds the harmonics k = kA + 64 i and N - k; the
+//   - each lane's slot i holds the harmonics hl = 64 i + kappa and N - hl; the
 //     lower one (< N/2) is what X and the guess need below their cutoffs,
 //     so one model load, one D conj(M) and one LDS store per slot (two only
 //     when the group's cutoff passes N/2);
@@ -858,7 +858,12 @@ __global__ __launch_bounds__(256) void k_model_sum(const double2 *Mft, int nchan
 // channel's 8 consecutive harmonics in one 128-byte line, so the wave that
 // transformed a row also stores it: after wave_sum has given 1/sigma~^2 it
 // reads its staged X back in harmonic order (lane l: harmonic l + 64 j) and
-// each store instruction writes 8 whole lines.  No workgroup barrier in
+// each store instruction writes 8 whole lines.  Round 10: slot i of
+// wf2::pairs is the band [64 i, 64 i + 63] in every lane, i.e. those 8
+// lines, so a row whose group cutoff is <= N/2 keeps its X in the registers
+// the slots free and stores it from them, one store per band below the
+// cutoff -- no staging, no read-back; a higher cutoff (the high harmonics
+// and D_{N/2} are stored too) keeps the staged path.  No workgroup barrier in
 // the round loop; the fused guess terms are summed in registers per wave
 // (the lane that holds harmonic hl in slot i is the same for every row) and
 // the four waves' partials in wave order once, after the last round.  The
@@ -958,12 +963,13 @@ __device__ __forceinline__ void xspec_w2_block(const XspecArgs &a, const int s, 
     }
     const double sqrtN = sqrt((double)N);
     const wf2::Seeds sd = wf2::make_seeds(lane0);
-    // post-pass twiddle e^{-i pi k / N} of the lane's first pair, step
-    // e^{-i pi 64 / N}
+    // post-pass twiddle e^{-i pi k / N} of the harmonic k in the lane's
+    // x[0] (wf2::pair_k: hl of the lanes < 32, N - hl of the others), step
+    // e^{-i pi 64 / N} (lanes >= 32: its conjugate, k falling with the slot)
     double2 wA0, wstep;
     {
         double sn, cs;
-        sincospi(-(double)wf2::pair_k0(lane0) / (double)N, &sn, &cs);
+        sincospi(-(double)wf2::pair_k(lane0, 0) / (double)N, &sn, &cs);
         wA0 = cmk(cs, sn);
         sincospi(-64.0 / (double)N, &sn, &cs);
         wstep = cmk(cs, sn);
@@ -976,6 +982,10 @@ __device__ __forceinline__ void xspec_w2_block(const XspecArgs &a, const int s, 
     double2 *Xs = a.X + (int64_t)xsl * a.xnh * a.nchan;
     int kw = NH;
     if (a.KC) kw = (int)wave_max(nkw < a.nchan ? (double)ld_kc : 1.0);
+    // RX (round 10): a tiled row whose group cutoff stays below N/2 keeps
+    // its X in registers and stores it from them (uniform)
+    constexpr bool RX = TL;
+    const bool rx = kw <= N / 2;
     // TL: the wave's own channel n, harmonics below kw rounded up to whole
     // tiles (zeros past kw, and for a masked channel), lane l: harmonics l +
     // 64 j -- per store instruction 8 tiles, each one whole 128-byte line
@@ -1002,11 +1012,12 @@ __device__ __forceinline__ void xspec_w2_block(const XspecArgs &a, const int s, 
         }
     }
     // GR: the wave's guess partials, slot i of every row it transforms (the
-    // slot's harmonic hl is fixed per lane; only 1 <= hl < NL is written out
-    // at the end -- 7 of the 8 slots of a lane, the eighth sums unused terms)
-    double2 gr[8];
+    // slot's harmonic hl is fixed per lane; hl < NL = 64 x 7: slots 0 .. 6)
+    constexpr int NG = NL / 64;
+    static_assert(NL == 64 * NG && NG < 8, "whole bands of guess harmonics");
+    double2 gr[NG];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) gr[i] = cmk(0.0, 0.0);
+    for (int i = 0; i < NG; ++i) gr[i] = cmk(0.0, 0.0);
     const double ch_mpow = lin ? ld_mpow : 0.0;
     const double ch_err = (a.errs && lin) ? ld_err : 0.0;
     double ch_wn = 0.0, ch_dg = 0.0;
@@ -1048,26 +1059,25 @@ __device__ __forceinline__ void xspec_w2_block(const XspecArgs &a, const int s, 
             // then took other registers and a copy per row)
             asm volatile("" : "+v"(x[q].x), "+v"(x[q].y));
         }
-        // slot i: harmonics k = kA + 64 i and N - k; hl = the lower one
-        // (lanes <= 32: k, the others: N - k), D of it in Dl.  Per-lane
+        // slot i: harmonics hl = 64 i + kap and N - hl (wf2::pairs: the band
+        // [64 i, 64 i + 63] in every lane), D of hl in Dl.  Per-lane
         // indices re-derived every row from an opaque lane (hoisted out of
         // the round loop they would hold VGPRs for good)
         int lane = lane0;
         asm volatile("" : "+v"(lane));
-        const bool lo = lane <= 32;
-        const int kA = wf2::pair_k0(lane);
-        const int hl0 = lo ? kA : N - kA, hstep = lo ? 64 : -64;
+        const bool lo = wf2::pair_lo(lane);
+        const int kap = wf2::lane_kappa(lane);
         const double2 *Mrow = a.Mft + ((int64_t)mi * a.nchan + (n < cend ? n : cend - 1)) * NH;
         // the first MD slots' model values, issued after the FFT (issued
         // here, before the next row's prefetch: 24.2 vs 23.9 ms, round 6).
-        // The loads are unconditional (hl < N/2 is always a
-        // valid index): under a lane-divergent branch the compiler cannot
+        // The loads are unconditional (hl < N/2 is always a valid index):
+        // under a branch, lane-divergent or scalar, the compiler does not
         // count the loads in flight and waits for all of them (vmcnt(0),
-        // the next row's prefetch included) at every slot.
+        // the next row's prefetch included).
         double2 Mq[MD > 0 ? MD : 1];
         auto mpre = [&]() {
 #pragma unroll
-            for (int i = 0; i < MD; ++i) Mq[i] = Mrow[(unsigned)(hl0 + hstep * i)];
+            for (int i = 0; i < MD; ++i) Mq[i] = Mrow[(unsigned)(kap + 64 * i)];
         };
         SCHED_CUT();
         fetch_c(n + kX2W);                       // next row in flight during this FFT
@@ -1089,67 +1099,75 @@ __device__ __forceinline__ void xspec_w2_block(const XspecArgs &a, const int s, 
             double2 zm = cmk(0.0, 0.0);
             wf2::pairs(x, buf + wf2::kXSlots, lane, zm);
             XP(2);
-            // guess phasor w_n e^{2 pi i hl dphi}, step e^{+-2 pi i 64 dphi}
+            // guess phasor w_n e^{2 pi i hl dphi}, step e^{2 pi i 64 dphi}
             double2 El = cmk(0.0, 0.0), Est = El;
             if constexpr (GR) {
                 if (GS && gon) {
-                    // hl0 = m (lanes <= 32) or 512 - m (the others), m = lane
-                    // mod 32 (lane 32: 32): e1^m by square and multiply over
-                    // the uniform e1^(2^b), e1^512 by four more squarings
+                    // slot 0: hl = kap < 64: e1^kap by square and multiply
+                    // over the uniform e1^(2^b)
                     const double2 b1 = LT ? ltab[192 + rr] : cmk(readlane_d(ch_e1.x, rr), readlane_d(ch_e1.y, rr));
                     const double2 b2 = cmul(b1, b1), b4 = cmul(b2, b2), b8 = cmul(b4, b4);
-                    const double2 b16 = cmul(b8, b8), b32 = cmul(b16, b16), b64 = cmul(b32, b32);
-                    const int m = lane == 32 ? 32 : (lane & 31);
-                    double2 pw = (m & 1) ? b1 : cmk(1.0, 0.0);
-                    if (m & 2) pw = cmul(pw, b2);
-                    if (m & 4) pw = cmul(pw, b4);
-                    if (m & 8) pw = cmul(pw, b8);
-                    if (m & 16) pw = cmul(pw, b16);
-                    if (m & 32) pw = b32;
-                    double2 E1 = pw;
-                    if (!lo) {
-                        const double2 b128 = cmul(b64, b64), b256 = cmul(b128, b128);
-                        E1 = cmulc(cmul(b256, b256), pw);
-                    }
-                    El = cscale(E1, readlane_d(ch_wn, rr));
-                    Est = lo ? b64 : cconj(b64);
+                    const double2 b16 = cmul(b8, b8), b32 = cmul(b16, b16);
+                    double2 pw = (kap & 1) ? b1 : cmk(1.0, 0.0);
+                    if (kap & 2) pw = cmul(pw, b2);
+                    if (kap & 4) pw = cmul(pw, b4);
+                    if (kap & 8) pw = cmul(pw, b8);
+                    if (kap & 16) pw = cmul(pw, b16);
+                    if (kap & 32) pw = cmul(pw, b32);
+                    El = cscale(pw, readlane_d(ch_wn, rr));
+                    Est = cmul(b32, b32);
                 }
             } else if (GS && gon) {
                 const double dg = readlane_d(ch_dg, rr);
-                const double2 E1 = cexp2pi((double)hl0 * dg);
+                const double2 E1 = cexp2pi((double)kap * dg);
                 El = cscale(E1, readlane_d(ch_wn, rr));
-                // step e^{2 pi i 64 dphi}: lane 1's phasor (hl0 = 1) squared
+                // step e^{2 pi i 64 dphi}: lane 1's phasor (hl = 1) squared
                 // six times
                 Est = cmk(readlane_d(E1.x, 1), readlane_d(E1.y, 1));
 #pragma unroll
                 for (int q = 0; q < 6; ++q) Est = cmul(Est, Est);
-                if (!lo) Est = cconj(Est);
             }
             // Per slot (the real-FFT post-pass in doubled form: the 0.5 of
             // e and o dropped, so Dl = 2 D_hl, v = the other harmonic's 2 D
             // up to conjugation; every product below is rescaled by an
-            // exact power of two):
+            // exact power of two), k = the harmonic in x[i] (wf2::pair_k):
             //   e = Z_k + conj Z_{N-k}, o = Z_k - conj Z_{N-k}, wo = w o
-            //   lanes <= 32 (sg = +1): 2 D_k = (e.x + wo.y, e.y - wo.x)
-            //   the others (sg = -1):  2 D_{N-k} = conj of (e.x - wo.y, e.y + wo.x)
+            //   lanes < 32 (sg = +1, k = hl): 2 D_k = (e.x + wo.y, e.y - wo.x)
+            //   the others (sg = -1, k = N - hl): 2 D_{N-k} = conj of (e.x - wo.y, e.y + wo.x)
             // u = e + sg (wo.y, -wo.x): Dl = (u.x, sg u.y) is 2 D_hl; v = e -
             // sg (...) has |v| = |2 D_{N - hl}|.
+            // The slot loop stays straight-line code: every lane of a slot
+            // computes everything under per-lane predicates, although since
+            // round 10 a slot is one band and what it needs is uniform --
+            // scalar branches per slot on the cutoffs measured slower
+            // (DESIGN.md round 10).  Two exceptions: the last band, which
+            // carries no guess term, is skipped when it lies past both
+            // cutoffs; and the high harmonic's X as before.
             const double sg = lo ? 1.0 : -1.0;
+            const double2 ws = cmk(wstep.x, sg * wstep.y);
             const int hcut = N - a.kc;            // N - hl >= kc  <=>  hl <= hcut
+            const bool gq = GS && gon;
             double pn = 0.0, pd = 0.0;
             double2 w = LT ? ltab[128 + lane] : wA0;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const double2 zk = x[i], zn = x[i + 8];
+                const double2 zk = x[i], zn = x[15 - i];
+                if (i >= NG && !(64 * i < kw || 64 * i <= hcut)) {
+                    // the last band past X's cutoff and the noise sum's
+                    // (uniform; kw > N/2 is not: 64 i < kw): only its part of
+                    // Sd, |u|^2 + |v|^2 = 4 (|Z_k|^2 + |Z_{N-k}|^2) (|w| = 1)
+                    pd = fma(4.0, fma(zk.x, zk.x, zk.y * zk.y) + fma(zn.x, zn.x, zn.y * zn.y), pd);
+                    continue;
+                }
                 const double ex = zk.x + zn.x, ey = zk.y - zn.y;
                 const double ox = zk.x - zn.x, oy = zk.y + zn.y;
                 const double wox = fma(w.x, ox, -w.y * oy), woy = fma(w.x, oy, w.y * ox);
-                w = cmul(w, wstep);
+                if (i < 7) w = cmul(w, ws);
                 const double ux = fma(sg, woy, ex), uy = fma(-sg, wox, ey);
                 const double vx = fma(-sg, woy, ex), vy = fma(sg, wox, ey);
                 const double2 Dl = cmk(ux, sg * uy);
                 const double ph = fma(vx, vx, vy * vy), pl = fma(ux, ux, uy * uy);
-                const int hl = hl0 + hstep * i;
+                const int hl = kap + 64 * i;
                 if (hl <= hcut) pn += ph;
                 // (lane 0, slot 0: pl = |2 D_0|^2, which Sd leaves out)
                 if (i == 0) pd += lane == 0 ? ph : pl + ph;
@@ -1157,31 +1175,43 @@ __device__ __forceinline__ void xspec_w2_block(const XspecArgs &a, const int s, 
                 double2 Ml;
                 if constexpr (MD > 0) {
                     Ml = Mq[i % MD];
-                    if (i + MD < 8) Mq[i % MD] = Mrow[(unsigned)(hl + hstep * MD)];
+                    if (i + MD < 8) Mq[i % MD] = Mrow[(unsigned)(hl + 64 * MD)];
                 } else {
                     Ml = Mrow[(unsigned)hl];
                 }
                 // 2 x the unscaled X of the low harmonic (the write-out
                 // applies 1/(2 sigma~^2)); k = 0 zeroed (F0_fact = 0)
-                // (k = 0 -- lane 0, slot 0 only -- is zeroed after the loop)
-                if (hl < kw) buf[x2slot(hl)] = cmulc(Dl, Ml);
-                if (GS && gon) {
+                // (k = 0 -- lane 0, slot 0 only -- is zeroed after the loop).
+                // RX: kept in x[i], the registers the slot frees; staged in
+                // LDS as well where the row goes through store_tiles (!rx,
+                // which has no fused guess: kw <= NL with it)
+                const double2 xv = cmulc(Dl, Ml);
+                if constexpr (RX) x[i] = xv;
+                else if (hl < kw) buf[x2slot(hl)] = xv;
+                if (gq) {
                     // 2 x the row's guess term of harmonic hl: GR into the
                     // wave's partial; else staged in the slot of N - hl
                     // (past X's cutoff: kw <= NL < N/2)
-                    if constexpr (GR) gr[i] = cadd(gr[i], cmul(Dl, El));
-                    else if (hl >= 1 && hl < NL) buf[x2slot(N - hl)] = cmul(Dl, El);
-                    El = cmul(El, Est);
+                    if (i < NG) {
+                        if constexpr (GR) gr[i] = cadd(gr[i], cmul(Dl, El));
+                        else if (hl >= 1) buf[x2slot(N - hl)] = cmul(Dl, El);
+                        El = cmul(El, Est);
+                    }
                 } else if (kw > N / 2) {
+                    if (RX && hl < kw) buf[x2slot(hl)] = xv;
                     // the group's cutoff passes N/2: the high harmonic too
                     // (2 D_{N - hl} = (vx, -sg vy))
                     const int hh = N - hl;
                     if (hh < kw) buf[x2slot(hh)] = cmulc(cmk(vx, -sg * vy), Mrow[(unsigned)hh]);
                 }
             }
+            // k = 0 (F0_fact = 0)
+            if (lane == 0) {
+                if constexpr (RX) x[0] = cmk(0.0, 0.0);
+                if (!(RX && rx)) buf[x2slot(0)] = cmk(0.0, 0.0);
+            }
             XP(3);
             if (lane == 0) {
-                buf[x2slot(0)] = cmk(0.0, 0.0);       // k = 0 (F0_fact = 0)
                 // D_{N/2} (pairs: zm = Z_{N/2}), doubled like the rest
                 const double2 Dm = cmk(2.0 * zm.x, -2.0 * zm.y);
                 const double p = cabs2(Dm);
@@ -1215,12 +1245,31 @@ __device__ __forceinline__ void xspec_w2_block(const XspecArgs &a, const int s, 
             if constexpr (TL) {
                 rows_ready();
                 XP(4);
-                // (a wave's LDS operations are ordered: the staged X of
-                // every lane is there, and read before the next row's
-                // exchange overwrites it)
-                wfft::wave_sync();
-                store_tiles(n, buf, 0.5 * inv_e2, true);
-                wfft::wave_sync();
+                if (rx) {
+                    // slot i is 64 consecutive harmonics = 8 whole tiles:
+                    // from the registers, one store per needed slot (the
+                    // tiles and values of store_tiles; h < kwp <= xnh)
+                    const double ie2 = 0.5 * inv_e2;
+                    const int kwp = (kw + kXTile - 1) & ~(kXTile - 1);
+                    double2 *Xn = Xs + (int64_t)n * kXTile + (kap & (kXTile - 1)) +
+                                  (int64_t)(kap >> 3) * a.nchan * kXTile;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        if (64 * i >= kw) break;
+                        const int h = kap + 64 * i;
+                        const double2 v = h < kw ? cscale(x[i], ie2) : cmk(0.0, 0.0);
+                        if (h < kwp)
+                            __builtin_nontemporal_store(
+                                vd2{v.x, v.y}, reinterpret_cast<vd2 *>(Xn + (int64_t)(8 * i) * a.nchan * kXTile));
+                    }
+                } else {
+                    // (a wave's LDS operations are ordered: the staged X of
+                    // every lane is there, and read before the next row's
+                    // exchange overwrites it)
+                    wfft::wave_sync();
+                    store_tiles(n, buf, 0.5 * inv_e2, true);
+                    wfft::wave_sync();
+                }
                 XP(5);
             }
         } else if constexpr (TL) {
@@ -1281,13 +1330,10 @@ __device__ __forceinline__ void xspec_w2_block(const XspecArgs &a, const int s, 
                 // the wave's partials into its own buffer, slot hl (1 <= hl
                 // < NL; slot 0 takes g_w2e2 below): every wave is past its
                 // last row's reads of it
-                const bool lo = lane0 <= 32;
-                const int kA = wf2::pair_k0(lane0);
-                const int hl0 = lo ? kA : N - kA, hstep = lo ? 64 : -64;
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int hl = hl0 + hstep * i;
-                    if (hl >= 1 && hl < NL) buf[hl] = gr[i];
+                for (int i = 0; i < NG; ++i) {
+                    const int hl = wf2::pair_hl(lane0, i);
+                    if (hl >= 1) buf[hl] = gr[i];
                 }
             }
             if (lane0 == 0) reinterpret_cast<double *>(buf)[0] = g_w2e2;

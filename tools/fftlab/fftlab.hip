@@ -103,7 +103,7 @@ __global__ __launch_bounds__(64 * WG) __attribute__((amdgpu_waves_per_eu(WPE))) 
     const wf2::Seeds sd = wf2::make_seeds(lane0);
     const double2 wstep = wpi(64);
     const double2 wseed_nat = wpi(lane0);
-    const double2 wseed_pair = wpi(wf2::pair_k0(lane0));
+    const double2 wseed_pair = wpi(wf2::pair_k(lane0, 0));
     const long long nw = (long long)gridDim.x * WG;
     long long row = (long long)blockIdx.x * WG + wave;
     vf2 zr[16];
@@ -143,14 +143,16 @@ __global__ __launch_bounds__(64 * WG) __attribute__((amdgpu_waves_per_eu(WPE))) 
             wf2::fft1024(x, buf, lane, sd);
             double2 zm = cmk(0.0, 0.0);
             wf2::pairs(x, buf + wf2::kXSlots, lane, zm);
-            const int k0 = wf2::pair_k0(lane);
+            // slot i: x[i] = Z[k], x[15 - i] = Z[N - k], k = pair_k(lane, i)
+            // (rising with i in the lanes < 32, falling in the others)
+            const double2 wst = wf2::pair_lo(lane) ? wstep : cmk(wstep.x, -wstep.y);
             double2 w = wseed_pair;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const int klo = k0 + 64 * i, khi = N - klo;
+                const int klo = wf2::pair_k(lane, i), khi = N - klo;
                 double2 Dlo, Dhi;
-                rpair(x[i], x[i + 8], w, Dlo, Dhi);
-                w = cmul(w, wstep);
+                rpair(x[i], x[15 - i], w, Dlo, Dhi);
+                w = cmul(w, wst);
                 const double p0 = cabs2(Dlo), p1 = cabs2(Dhi);
                 if (klo >= KC) pn += p0;
                 if (khi >= KC) pn += p1;
