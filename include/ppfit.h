@@ -79,6 +79,24 @@ enum ppf_status {
     PPF_ST_NOSPACE = 0x1000  /* the fit streams the cross spectrum but the
                                 workspace holds fewer X slots (x_subints)    */
 };
+/* Degenerate sub-integrations end alone; the rest of the batch is fitted as
+ * without them (tests/test_gpu_degenerate.py).
+ *   - PPF_ST_NOFIT (no fit flag set, or no usable channel) and PPF_ST_NOSPACE:
+ *     status holds exactly that value and the record is all zeros except
+ *     status and phi_guess (the initial phase the fit would have used; the
+ *     caller's init[0] where the guess stage had no channel to form one
+ *     from).  Every field is finite.  scales, scale_errs and channel_snrs of
+ *     the sub-int are written as 0; its covariance block is NOT written: a
+ *     caller that reads it must have zeroed the array (engine.fit_batch
+ *     does).
+ *   - The values of a masked channel (chan_mask == 0) -- its data row, errs,
+ *     guess_weights -- are never read into any result, whatever they hold
+ *     (NaN, Inf, stale numbers): the outputs are bitwise those of the same
+ *     call with ordinary values there.
+ *   - A non-finite sample, or a channel whose noise is zero (errs == 0, or
+ *     estimated from a row of zeros), in a USED channel ends that sub-int
+ *     with PPF_ST_NONFINITE set (the reference raises from SciPy's
+ *     finiteness check there); its parameter values are not meaningful. */
 
 /* ppf_fit_desc.options bits */
 enum ppf_option {

@@ -18,6 +18,7 @@ constexpr double kPi = 3.14159265358979323846;
 constexpr double kTwoPi = 6.28318530717958647692;
 constexpr double kDconst = 1.0 / 0.000241;   // pplib.py:64-67 (Dconst_trad)
 constexpr double kLn10 = 2.30258509299404568402;
+constexpr double kDblMax = 1.7976931348623157e308;   // x <= kDblMax: x is finite
 constexpr int kBlock = 256;                  // threads per workgroup (4 waves)
 constexpr int kWaves = kBlock / 64;
 constexpr int kMaxBfly = 4;                  // radix-4 butterflies / thread / pass
@@ -958,7 +959,10 @@ __host__ __device__ inline void balance_small(double (*a)[8], int n) {
             double r = 0.0, c = 0.0;
             for (int j = 0; j < n; ++j)
                 if (j != i) { c += fabs(a[j][i]); r += fabs(a[i][j]); }
-            if (c != 0.0 && r != 0.0) {
+            // a non-finite norm is not scaled: c = Inf beside a finite r would
+            // never leave "while (c > g)" (Inf / 4 = Inf).  Finite norms take
+            // the branch exactly as before
+            if (c != 0.0 && r != 0.0 && c <= kDblMax && r <= kDblMax) {
                 double g = r / radix, f = 1.0, s = c + r;
                 while (c < g) { f *= radix; c *= sqrdx; }
                 g = r * radix;

@@ -1702,7 +1702,11 @@ __global__ __launch_bounds__(PB) void k_postfit(SolveArgs a) {
         if (tid == 0) {
             for (int i = 0; i < 32; ++i) reinterpret_cast<double *>(res)[i] = 0.0;
             res->status = S.status;
-            res->phi_guess = S.phi_guess;
+            // a sub-int without a usable channel has no mean frequency (0 / 0)
+            // and k_guess's phase is NaN: the record then holds the caller's
+            // initial phase, so that every field of it is finite
+            const double pg = S.phi_guess;
+            res->phi_guess = fabs(pg) <= kDblMax ? pg : a.init[(int64_t)s * 5];
         }
         for (int n = tid; n < a.nchan; n += PB) {
             const int64_t o2 = (int64_t)s * a.nchan + n;

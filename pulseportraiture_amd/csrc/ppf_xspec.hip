@@ -1635,6 +1635,10 @@ void k_xspec_wm(XspecArgs a) {
 // F0_fact), slot 0 and slot NF, carry the rows' 1/errs_FT^2 for the
 // write-out, which stores 8 channels (128 B) per harmonic.
 // ===========================================================================
+__device__ __forceinline__ unsigned sample_bits(float v) { return __float_as_uint(v); }
+__device__ __forceinline__ unsigned long long sample_bits(double v) {
+    return (unsigned long long)__double_as_longlong(v);
+}
 template <int DT, int NMAX>
 __global__ __launch_bounds__(64 * kWmW) __attribute__((amdgpu_waves_per_eu(NMAX <= 512 ? 3 : 2)))
 void k_xspec_wo(XspecArgs a) {
@@ -1671,6 +1675,7 @@ void k_xspec_wo(XspecArgs a) {
     // the wave's next two rows in registers while these are transformed
     using ET = typename std::conditional<DT == 0, float, double>::type;
     constexpr int PJ = NMAX / 64;
+    using BT = typename std::conditional<DT == 0, unsigned, unsigned long long>::type;
     ET pa[PJ], pb[PJ];
     auto fetch = [&](ET (&p)[PJ], int m) {
         const ET *src = reinterpret_cast<const ET *>(a.data) + ((int64_t)s * a.nchan + m) * (int64_t)NF;
@@ -1687,12 +1692,26 @@ void k_xspec_wo(XspecArgs a) {
         const bool liveA = usable(nA), liveB = usable(nB), live = liveA || liveB;
         if (nA < cend && !liveA && lane < 4) a.chan[((int64_t)s * a.nchan + nA) * 4 + lane] = 0.0;
         if (nB < cend && !liveB && lane < 4) a.chan[((int64_t)s * a.nchan + nB) * 4 + lane] = 0.0;
+        // A row of zeros has a zero spectrum, but separated from its partner's
+        // in the shared transform it keeps that row's rounding residue (1e-16
+        // of it), which would become a finite noise estimate: such a row's
+        // power sums are set to the exact 0 the one-row kernels form, and the
+        // fit ends with PPF_ST_NONFINITE there as everywhere else.  (A row
+        // that holds anything, a NaN included, is left alone.)
+        bool zeroA = false, zeroB = false;
         if (live) {
+            // (the samples' bits OR-ed per lane, sign shifted out; the loads
+            // past NF repeat the row's last sample)
+            BT orA = 0, orB = 0;
 #pragma unroll
             for (int i = 0; i < PJ; ++i) {
                 const int t = lane + 64 * i;
                 if (t < NF) buf[t] = cmk(liveA ? (double)pa[i] : 0.0, liveB ? (double)pb[i] : 0.0);
+                orA |= sample_bits(pa[i]);
+                orB |= sample_bits(pb[i]);
             }
+            zeroA = __ballot((BT)(orA << 1) != 0) == 0;
+            zeroB = __ballot((BT)(orB << 1) != 0) == 0;
         }
         fetch(pa, min(nA + RW, cend - 1));
         fetch(pb, min(nB + RW, cend - 1));
@@ -1733,6 +1752,8 @@ void k_xspec_wo(XspecArgs a) {
             pdA = wave_sum(pdA);
             pnB = wave_sum(pnB);
             pdB = wave_sum(pdB);
+            if (zeroA) pnA = pdA = 0.0;
+            if (zeroB) pnB = pdB = 0.0;
             const int rA = nA - cbase, rB = min(nB - cbase, 63);
             double eA, eB;
             if (a.errs) {

@@ -287,24 +287,38 @@ def compare_row(label, tag, r, j, o, keep, P, log10_tau):
     return dev.max(), rel
 
 
-def device_fit(c, subs=None):
-    """engine.fit_batch on the case's batch (or on the sub-ints subs of it)
-    -> dict of numpy arrays."""
+def device_fit(c, subs=None, over=None):
+    """engine.fit_batch on the case's batch (or on the sub-ints subs of it,
+    which may repeat) -> dict of numpy arrays.  over: a dict that replaces,
+    for the len(subs) sub-ints of the call, any of data [n, nchan, nbin],
+    errs [n, nchan], guess_weights [n, nchan], mask [n, nchan] (True =
+    kept), flags ([5] or [n, 5]), solver and n_x (tests/degenerate.py);
+    what it does not name is the case's own."""
     from pulseportraiture_amd import engine
     b = inputs(c)
+    o = {} if over is None else over
     sl = np.arange(b["nsub"]) if subs is None else np.asarray(subs)
     n = len(sl)
-    data = b["data"][sl]
+    data = np.asarray(o["data"]) if "data" in o else b["data"][sl]
     data = data.astype(np.float32) if c["dtype"] == "f32" else data.copy()
+    keep = np.asarray(o["mask"]) if "mask" in o else b["keep"][sl]
+    errs = b["errs"]
+    if "errs" in o:
+        errs = np.array(o["errs"], dtype=float)
+    elif errs is not None:
+        errs = errs[sl].copy()
     kw = {}
     if c["guess"]:
-        kw = dict(guess=True, guess_weights=b["keep"][sl].astype(float),
+        gw = np.array(o["guess_weights"], dtype=float) \
+            if "guess_weights" in o else keep.astype(float)
+        kw = dict(guess=True, guess_weights=gw,
                   guess_DM=b["init"][sl, 1].copy(), guess_Ns=100)
     return engine.results_numpy(engine.fit_batch(
         data, b["model"], np.tile(b["freqs"], (n, 1)), np.full(n, b["P"]),
-        b["init"][sl].copy(), list(c["flags"]),
+        b["init"][sl].copy(),
+        np.array(o["flags"], dtype=np.int32) if "flags" in o else
+        list(c["flags"]),
         nu_fits=np.repeat(b["nu_fit"][sl][:, None], 3, axis=1),
-        nu_outs=np.full((n, 3), np.nan),
-        errs=None if b["errs"] is None else b["errs"][sl].copy(),
-        chan_mask=b["keep"][sl].astype(np.uint8), log10_tau=b["scat"],
-        mom_x=c["mom_x"], **kw))
+        nu_outs=np.full((n, 3), np.nan), errs=errs,
+        chan_mask=keep.astype(np.uint8), log10_tau=b["scat"],
+        mom_x=c["mom_x"], solver=o.get("solver"), n_x=o.get("n_x"), **kw))
