@@ -541,6 +541,42 @@ int ppf_gauss_portrait_batch(ppf_ctx *ctx, int32_t nport, int32_t nchan, int32_t
                              const double *scattering_index, const double *freqs,
                              const double *nu_ref, double *out, void *stream);
 
+/* Normal equations of the Gaussian-component portrait model (added within
+ * ABI 6): what a Levenberg-Marquardt fit of pplib.fit_gaussian_portrait
+ * (pplib.py:2005-2144) needs per iteration, for nfit independent fits.
+ * With m(p) the portrait ppf_gauss_portrait_batch builds for p (the same
+ * device code builds the rows, so m(p) has the same bits), fit f has the
+ * nfree + 1 columns over its nchan * nbin points
+ *     c_j     = ((m(p + delta_j e_j) - m(p)) / delta_j) * inv_errs,  j < nfree
+ *     c_nfree = (data - m(p)) * inv_errs
+ * and gram[f] = C C^T, [nfree + 1][nfree + 1] f64, symmetric, both triangles
+ * written: J^T J is the leading block, J^T r the last column, chi^2 the
+ * corner.  nfree = 0 gives chi^2 alone (an LM trial step).
+ * free_idx indexes the extended parameter vector: entries 0 .. npar - 1
+ * (npar = 2 + 6 * ngauss) are params, entry npar is the scattering index;
+ * strictly increasing.  free_idx [nfree] (int32) and delta [nfit][nfree] are
+ * HOST arrays, checked here and copied by the call; they must stay untouched
+ * until the stream has passed it.  Every other array is device memory:
+ * params, scattering_index, freqs, nu_ref and model_code as for
+ * ppf_gauss_portrait_batch; data [nfit][nchan][nbin] in in_dtype; inv_errs
+ * [nfit][nchan][nbin] f64 (1 / sigma per point; no masks: 0 drops a point).
+ * The contraction runs on the f64 MFMA over fixed chunks of the point axis,
+ * the partial tiles summed in a fixed order without atomics: the result is
+ * bitwise reproducible.
+ * PPF_EUNSUP: nbin odd or outside [32, 8192] (the LDS row transforms),
+ * nfree + 1 > 128.  PPF_EINVAL: bad model_code or in_dtype, free_idx out of
+ * range or not increasing, a zero or non-finite delta, a workspace smaller
+ * than ppf_gauss_lsq_workspace_bytes (0 for an unsupported shape), a NULL
+ * array or context.  All of this is checked on the host before any launch. */
+size_t ppf_gauss_lsq_workspace_bytes(int32_t nfit, int32_t nchan, int32_t nbin, int32_t nfree);
+int ppf_gauss_lsq_batch(ppf_ctx *ctx, int32_t nfit, int32_t nchan, int32_t nbin, int32_t ngauss,
+                        const char *model_code, const double *params,
+                        const double *scattering_index, const double *freqs,
+                        const double *nu_ref, int32_t nfree, const int32_t *free_idx,
+                        const double *delta, int32_t in_dtype, const void *data,
+                        const double *inv_errs, double *gram, void *workspace,
+                        size_t workspace_bytes, void *stream);
+
 /* Spline (PCA + B-spline) model portraits: pplib.gen_spline_portrait
  * (pplib.py:966-990) as called by pplib.read_spline_model (pplib.py:3060-3096)
  * from pptoas.GetTOAs.get_TOAs (pptoas.py:416-419) for make_spline_model

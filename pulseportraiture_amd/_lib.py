@@ -125,6 +125,13 @@ SIGNATURES = {
     "ppf_gauss_portrait_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32,
                                                 ctypes.c_char_p, _vp, _vp, _vp,
                                                 _vp, _vp, _vp]),
+    "ppf_gauss_lsq_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32,
+                                                        _i32]),
+    "ppf_gauss_lsq_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32,
+                                           ctypes.c_char_p, _vp, _vp, _vp,
+                                           _vp, _i32, _vp, _vp, _i32, _vp,
+                                           _vp, _vp, _vp, ctypes.c_size_t,
+                                           _vp]),
     "ppf_spline_portrait_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32,
                                                  _i32, _i32, _i32, _vp, _vp,
                                                  _vp, _vp, _vp, _vp, _vp]),

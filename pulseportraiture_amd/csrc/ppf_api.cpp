@@ -1555,6 +1555,100 @@ int ppf_gauss_portrait_batch(ppf_ctx *ctx, int32_t nport, int32_t nchan, int32_t
     return PPF_OK;
 }
 
+namespace {
+// workspace of ppf_gauss_lsq_batch: the model rows, the partial tiles and the
+// device copies of free_idx / delta
+struct GaussLsqLayout {
+    int ntile, npair, nseg;
+    size_t rows, part, fidx, delta, bytes;
+};
+bool gauss_lsq_layout(int64_t nfit, int64_t nchan, int64_t nbin, int64_t nfree, GaussLsqLayout &L) {
+    if (nfit < 0 || nchan < 1 || nfree < 0 || nfree + 1 > ppf::kGramMaxCol) return false;
+    if ((nbin & 1) || !nbin_supported((int)nbin) || nbin > 8192) return false;
+    L.ntile = (int)((nfree + 1 + 15) / 16);
+    L.npair = L.ntile * (L.ntile + 1) / 2;
+    L.nseg = (int)((nbin + ppf::kGramSeg - 1) / ppf::kGramSeg);
+    // one workgroup per row, one grid dimension per fit
+    if (nfit > 65535 || nfit * nchan * (nfree + 1) > 0x7fffffffLL || nchan * L.nseg > 0x7fffffffLL) return false;
+    size_t o = 0;
+    L.rows = o;  o += align256(sizeof(double) * (size_t)nfit * nchan * (nfree + 1) * nbin);
+    L.part = o;  o += align256(sizeof(double) * (size_t)nfit * nchan * L.nseg * L.npair * 256);
+    L.fidx = o;  o += align256(sizeof(int32_t) * (size_t)(nfree > 0 ? nfree : 1));
+    L.delta = o; o += align256(sizeof(double) * (size_t)(nfit * nfree > 0 ? nfit * nfree : 1));
+    L.bytes = o;
+    return true;
+}
+}  // namespace
+
+size_t ppf_gauss_lsq_workspace_bytes(int32_t nfit, int32_t nchan, int32_t nbin, int32_t nfree) {
+    GaussLsqLayout L;
+    return gauss_lsq_layout(nfit, nchan, nbin, nfree, L) ? L.bytes : 0;
+}
+
+int ppf_gauss_lsq_batch(ppf_ctx *ctx, int32_t nfit, int32_t nchan, int32_t nbin, int32_t ngauss,
+                        const char *model_code, const double *params, const double *scattering_index,
+                        const double *freqs, const double *nu_ref, int32_t nfree,
+                        const int32_t *free_idx, const double *delta, int32_t in_dtype,
+                        const void *data, const double *inv_errs, double *gram, void *workspace,
+                        size_t workspace_bytes, void *stream) {
+    // every argument check on the host, before the context or any launch
+    if ((nbin & 1) || nbin < 32 || nbin > 8192 || !nbin_supported(nbin))
+        return fail(ctx, PPF_EUNSUP, "nbin=%d: even lengths in [32, 8192] (the LDS row transforms)", nbin);
+    if (nfree >= ppf::kGramMaxCol)
+        return fail(ctx, PPF_EUNSUP, "nfree=%d: at most %d free parameters", nfree, ppf::kGramMaxCol - 1);
+    if (nfit < 0 || nchan < 1 || ngauss < 0 || nfree < 0)
+        return fail(ctx, PPF_EINVAL, "bad gauss_lsq shape");
+    if (in_dtype != PPF_F32 && in_dtype != PPF_F64) return fail(ctx, PPF_EINVAL, "in_dtype");
+    if (!model_code) return fail(ctx, PPF_EINVAL, "model_code is NULL");
+    ppf::GaussLsqArgs a{};
+    for (int i = 0; i < 3; ++i) {
+        const char c = model_code[i];
+        if (c != '0' && c != '1')
+            return fail(ctx, PPF_EINVAL, "model_code '%.3s': digit %d must be '0' or '1'", model_code, i);
+        a.code[i] = c - '0';
+    }
+    const int npar = 2 + 6 * ngauss;
+    if (nfree > 0 && (!free_idx || (nfit > 0 && !delta))) return fail(ctx, PPF_EINVAL, "free_idx / delta is NULL");
+    for (int j = 0; j < nfree; ++j) {
+        if (free_idx[j] < 0 || free_idx[j] > npar || (j > 0 && free_idx[j] <= free_idx[j - 1]))
+            return fail(ctx, PPF_EINVAL, "free_idx[%d] = %d: strictly increasing in [0, %d]", j, free_idx[j], npar);
+        for (int f = 0; f < nfit; ++f) {
+            const double d = delta[(size_t)f * nfree + j];
+            if (!(d != 0.0) || !std::isfinite(d))
+                return fail(ctx, PPF_EINVAL, "delta[%d][%d] = %g: a finite non-zero step", f, j, d);
+        }
+    }
+    GaussLsqLayout L;
+    if (!gauss_lsq_layout(nfit, nchan, nbin, nfree, L)) return fail(ctx, PPF_EUNSUP, "gauss_lsq shape too large");
+    if (nfit > 0 && (!workspace || workspace_bytes < L.bytes))
+        return fail(ctx, PPF_EINVAL, "workspace: %zu bytes given, %zu needed", workspace_bytes, L.bytes);
+    if (nfit > 0 && (!params || !scattering_index || !freqs || !nu_ref || !data || !inv_errs || !gram))
+        return fail(ctx, PPF_EINVAL, "null gauss_lsq argument");
+    if (!ctx) return PPF_EINVAL;
+    if (nfit == 0) return PPF_OK;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = twiddles(ctx, nbin, st, &a.T, &a.T2))) return rc;
+    char *ws = (char *)workspace;
+    if (nfree > 0) {
+        if ((e = hipMemcpyAsync(ws + L.fidx, free_idx, sizeof(int32_t) * nfree, hipMemcpyHostToDevice, st)) !=
+                hipSuccess ||
+            (e = hipMemcpyAsync(ws + L.delta, delta, sizeof(double) * (size_t)nfit * nfree,
+                                hipMemcpyHostToDevice, st)) != hipSuccess)
+            return hip_fail(ctx, e, "hipMemcpyAsync(free_idx, delta)");
+    }
+    a.nfit = nfit; a.nchan = nchan; a.nbin = nbin; a.ngauss = ngauss; a.npar = npar; a.nfree = nfree;
+    a.dtype = in_dtype; a.ntile = L.ntile; a.npair = L.npair; a.nseg = L.nseg;
+    a.params = params; a.scat_index = scattering_index; a.freqs = freqs; a.nu_ref = nu_ref;
+    a.free_idx = (const int32_t *)(ws + L.fidx); a.delta = (const double *)(ws + L.delta);
+    a.data = data; a.inv_errs = inv_errs;
+    a.rows = (double *)(ws + L.rows); a.part = (double *)(ws + L.part); a.gram = gram;
+    if ((e = ppf::launch_gauss_lsq(a, st)) != hipSuccess) return hip_fail(ctx, e, "k_gauss_rows / k_gauss_gram");
+    return PPF_OK;
+}
+
 int ppf_spline_portrait_batch(ppf_ctx *ctx, int32_t nport, int32_t nchan, int32_t nbin_model,
                               int32_t nbin, int32_t ncomp, int32_t nknots, int32_t degree,
                               const double *mean_prof, const double *eigvec, const double *knots,

@@ -383,6 +383,30 @@ struct GaussArgs {
 };
 hipError_t launch_gauss_port(const GaussArgs &a, hipStream_t st);
 
+// ppf_gauss_lsq_batch (ppf_gaussfit.hip): the Gram matrix of the
+// forward-difference Jacobian columns and the residual of the Gaussian
+// portrait model
+constexpr int kGramSeg = 1024;   // bins of one channel per Gram workgroup (one K chunk)
+constexpr int kGramMaxCol = 128; // nfree + 1 <= 8 tiles of 16
+struct GaussLsqArgs {
+    int nfit, nchan, nbin, ngauss, npar, nfree, dtype;
+    int ntile, npair, nseg;      // 16-row tiles of nfree + 1, upper-triangle pairs, chunks per channel
+    int code[3];
+    const double *params;        // [nfit][npar]
+    const double *scat_index;    // [nfit]
+    const double *freqs;         // [nfit][nchan]
+    const double *nu_ref;        // [nfit]
+    const int32_t *free_idx;     // [nfree] (device copy)
+    const double *delta;         // [nfit][nfree] (device copy)
+    const void *data;            // [nfit][nchan][nbin] in dtype
+    const double *inv_errs;      // [nfit][nchan][nbin]
+    const double2 *T, *T2;
+    double *rows;                // [nfit][nchan][nfree + 1][nbin]: m(p + delta_j e_j), last m(p)
+    double *part;                // [nfit][nchan * nseg][npair][256] partial tiles
+    double *gram;                // [nfit][nfree + 1][nfree + 1]
+};
+hipError_t launch_gauss_lsq(const GaussLsqArgs &a, hipStream_t st);
+
 // pplib.gen_spline_portrait (pplib.py:966-990): per (portrait, channel) row,
 // splev of the B-spline curve tck at the channel frequency (FITPACK splev /
 // fpbspl, ext = 0), the eigenvector expansion plus the mean profile, and

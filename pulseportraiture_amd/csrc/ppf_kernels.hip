@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "ppf_device.hpp"
+#include "ppf_gaussrow.hpp"
 #include "ppf_internal.hpp"
 
 namespace ppf {
@@ -1383,183 +1384,47 @@ __global__ __launch_bounds__(kBlock) void k_synth(SynthArgs a) {
 // A non-zero tau then convolves the row with the one-sided exponential
 // (rfft * 1/(1 + 2 pi i k tau_n) -> irfft, pplib.py:951-957, 4212-4260).
 // FP contraction is off so each product/sum rounds as NumPy's does.
+// The row itself is gp_build_row (ppf_gaussrow.hpp, shared with the
+// least-squares columns of ppf_gaussfit.hip); this kernel stores it.
 // ===========================================================================
-__device__ __forceinline__ double gp_evolve(double f, double nu_ref, double v, double e, int code) {
-#pragma clang fp contract(off)
-    if (code == 0) return exp((log(f) - log(nu_ref)) * e + 1.0 * log(v));   // power_law_evolution
-    return (f - nu_ref) * e + 1.0 * v;                                    // linear_evolution
-}
-
-__device__ __forceinline__ double gp_bin_center(int j, int nbin) {
-#pragma clang fp contract(off)
-    // np.linspace(1/(2 nbin), 1 - 1/(2 nbin), nbin) (get_bin_centers, pplib.py:694-707)
-    const double lo = 1.0 / (double)(nbin * 2), hi = 1.0 - 1.0 / (double)(nbin * 2);
-    if (j == nbin - 1) return hi;
-    const double step = (hi - lo) / (double)(nbin - 1);
-    return (double)j * step + lo;
-}
-
-// unnormalised retval of gaussian_profile at bin j (0 outside |z| < 20);
-// *xw receives the wrapped bin centre
-__device__ __forceinline__ double gp_raw(int j, int nbin, double mean, double sigma, double *xw) {
-#pragma clang fp contract(off)
-    double x = gp_bin_center(j, nbin);
-    if (mean < 0.5) { if (x > mean + 0.5) x = x - 1.0; }
-    else if (x < mean - 0.5) x = x + 1.0;
-    *xw = x;
-    const double z = (x - mean) / sigma;
-    if (!(fabs(z) < 20.0)) return 0.0;
-    return exp(-0.5 * (z * z)) / (sigma * 2.5066282746310002);   // sqrt(2 pi)
-}
-
-
 template <int KMAX, bool MX>
 __global__ __launch_bounds__(kBlock) void k_gauss_port(GaussArgs a) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) double2 lds[];
     __shared__ double red[kWaves * 2];
-    double *row = reinterpret_cast<double *>(lds);
     const int nbin = a.nbin, N = nbin >> 1;
     const int p = blockIdx.x / a.nchan, n = blockIdx.x % a.nchan;
     const double *prm = a.params + (int64_t)p * a.npar;
     const double f = a.freqs[(int64_t)p * a.nchan + n], nu_ref = a.nu_ref[p];
-    const double dc = prm[0];
-    for (int j = threadIdx.x; j < nbin; j += kBlock) row[j] = dc;   // zeros + DC
-    const double fwhm = 2.0 * sqrt(2.0 * log(2.0));
-    for (int g = 0; g < a.ngauss; ++g) {
-        const double *c = prm + 2 + 6 * g;
-        const double L = gp_evolve(f, nu_ref, c[0], c[1], a.code[0]);
-        const double W = gp_evolve(f, nu_ref, c[2], c[3], a.code[1]);
-        const double A = gp_evolve(f, nu_ref, c[4], c[5], a.code[2]);
-        if (!(W > 0.0)) {   // wid <= 0 (zeroout) or NaN: amp * zeros
-            for (int j = threadIdx.x; j < nbin; j += kBlock) row[j] = row[j] + A * 0.0;
-            continue;
-        }
-        const double sigma = W / fwhm;
-        double mean = fmod(L, 1.0);                  // Python/NumPy L % 1.0
-        if (mean != 0.0 && mean < 0.0) mean += 1.0;
-        // first argmax of the unnormalised profile
-        double lmax = -1.0, xw;
-        int lidx = nbin;
-        for (int j = threadIdx.x; j < nbin; j += kBlock) {
-            const double r = gp_raw(j, nbin, mean, sigma, &xw);
-            if (r > lmax) { lmax = r; lidx = j; }
-        }
-        double v[1] = {lmax};
-        block_max<1>(v, red);
-        const double gmax = v[0];
-        double vi[1] = {lmax == gmax ? -(double)lidx : -(double)nbin};
-        block_max<1>(vi, red);
-        const int imax = (int)(-vi[0]);
-        double fact = 1.0;                            // all-zero profile: returned as is
-        if (gmax != 0.0) {
-            double xi;
-            (void)gp_raw(imax, nbin, mean, sigma, &xi);
-            const double zz = (xi - L) / sigma;
-            fact = exp(-0.5 * (zz * zz)) / gmax;
-        }
-        for (int j = threadIdx.x; j < nbin; j += kBlock) {
-            const double r = gp_raw(j, nbin, mean, sigma, &xw);
-            row[j] = row[j] + A * (fact * r);
-        }
-    }
-    const double tau = prm[1];
+    double tau = prm[1];
     if (a.taus_out) {
         // long rows: tau_n for the convolution on the long transforms
         if (threadIdx.x == 0)
             a.taus_out[blockIdx.x] = tau != 0.0 ? tau / (double)nbin * pow(f / nu_ref, a.scat_index[p]) : 0.0;
-    } else if (tau != 0.0) {
-        // taus = (tau / nbin) * (freqs / nu_ref)**alpha; B_k = 1 / (1 + 2 pi i k tau_n)
-        const double tn = tau / (double)nbin * pow(f / nu_ref, a.scat_index[p]);
-        const bool odd = nbin & 1;
-        const int KH = odd ? N + 1 : N;
-        __syncthreads();
-        if (odd) {
-            // the real row (doubles) -> complex points in place: all reads first
-            double v[2 * KMAX];
-#pragma unroll
-            for (int i = 0; i < 2 * KMAX; ++i) {
-                const int j = threadIdx.x + i * kBlock;
-                if (j < nbin) v[i] = row[j];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 2 * KMAX; ++i) {
-                const int j = threadIdx.x + i * kBlock;
-                if (j < nbin) lds[j] = cmk(v[i], 0.0);
-            }
-            __syncthreads();
+        tau = 0.0;
+    }
+    const GpRow kind = gp_build_row<KMAX, MX, false>(lds, red, nbin, a.ngauss, a.code[0], a.code[1], a.code[2], prm,
+                                              -1, 0.0, tau, a.scat_index[p], f, nu_ref, a.T, a.T2, a.Te,
+                                              a.T2e);
+    if (kind == kGpPackedOdd) {
+        const double sc = 1.0 / (double)N;
+        double *o = a.out + (int64_t)blockIdx.x * nbin;
+        for (int j = threadIdx.x; j < N; j += kBlock) {
+            const double2 z = cscale(lds[j], sc);
+            o[2 * j] = z.x;
+            o[2 * j + 1] = z.y;
         }
-        lds_fft_n<MX>(lds, rfft_len(nbin), a.T, false);
-        double2 Xk[KMAX], Xn[KMAX];
-#pragma unroll
-        for (int i = 0; i < KMAX; ++i) {
-            const int k = threadIdx.x + i * kBlock;
-            if (k < KH) {
-                double2 X1 = rbin(lds, nbin, a.T2, k);
-                double2 X2 = odd ? cmk(0.0, 0.0) : rfft_bin(lds, N, a.T2, N - k);
-                if (tn != 0.0) {
-                    X1 = cmul(X1, scat_recip((2.0 * kPi * (double)k) * tn));
-                    if (!odd) X2 = cmul(X2, scat_recip((2.0 * kPi * (double)(N - k)) * tn));
-                }
-                if (k == 0) { X1.y = 0.0; X2.y = 0.0; }   // irfft keeps DC, Nyquist real parts
-                Xk[i] = X1;
-                Xn[i] = X2;
-            }
-        }
-        __syncthreads();
-        if (odd) {
-            // the reference's irfft takes no length (pplib.py:957): 2 N =
-            // nbin - 1 bins from X_0..X_N, X_N as the Nyquist term (its
-            // imaginary part dropped); the even-length packed inverse with
-            // the nbin - 1 twiddles, the row's last column zero
-#pragma unroll
-            for (int i = 0; i < KMAX; ++i) {
-                const int k = threadIdx.x + i * kBlock;
-                if (k < KH) lds[k] = Xk[i];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < KMAX; ++i) {
-                const int k = threadIdx.x + i * kBlock;
-                if (k < N) {
-                    Xk[i] = lds[k];
-                    Xn[i] = lds[N - k];
-                    if (k == 0) Xn[i].y = 0.0;
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < KMAX; ++i) {
-                const int k = threadIdx.x + i * kBlock;
-                if (k < N) lds[k] = irfft_prebin(Xk[i], Xn[i], a.T2e[k]);
-            }
-            __syncthreads();
-            lds_fft_n<MX>(lds, N, a.Te, true);
-            const double sc = 1.0 / (double)N;
-            double *o = a.out + (int64_t)blockIdx.x * nbin;
-            for (int j = threadIdx.x; j < N; j += kBlock) {
-                const double2 z = cscale(lds[j], sc);
-                o[2 * j] = z.x;
-                o[2 * j + 1] = z.y;
-            }
-            if (threadIdx.x == 0) o[nbin - 1] = 0.0;
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < KMAX; ++i) {
-            const int k = threadIdx.x + i * kBlock;
-            if (k < KH) lds[k] = irfft_prebin(Xk[i], Xn[i], a.T2[k]);
-        }
-        __syncthreads();
-        lds_fft_n<MX>(lds, rfft_len(nbin), a.T, true);
+        if (threadIdx.x == 0) o[nbin - 1] = 0.0;
+        return;
+    }
+    if (kind == kGpPacked) {
         const double sc = 1.0 / (double)N;
         double2 *o = reinterpret_cast<double2 *>(a.out) + (int64_t)blockIdx.x * N;
         for (int j = threadIdx.x; j < N; j += kBlock) o[j] = cscale(lds[j], sc);
         return;
     }
-    __syncthreads();
     if (nbin & 1) {
+        const double *row = reinterpret_cast<const double *>(lds);
         double *o = a.out + (int64_t)blockIdx.x * nbin;
         for (int j = threadIdx.x; j < nbin; j += kBlock) o[j] = row[j];
         return;

@@ -895,6 +895,116 @@ def gauss_portraits(model_code, params, scattering_index, freqs, nu_ref, nbin,
     return out
 
 
+def gauss_lsq(model_code, params, scattering_index, freqs, nu_ref, free_idx,
+              delta, data, inv_errs, dev=None, workspace=None):
+    """Normal equations of the Gaussian portrait model on the device
+    (ppf_gauss_lsq_batch): for each of nfit fits the Gram matrix C C^T of
+    the forward-difference Jacobian columns ((m(p + delta_j e_j) - m(p)) /
+    delta_j) * inv_errs and the residual (data - m(p)) * inv_errs, m the
+    portrait gauss_portraits builds.  params [nfit, 2 + 6 ngauss],
+    scattering_index / nu_ref [nfit], freqs [nfit, nchan], free_idx [nfree]
+    (strictly increasing indices into params, npar = the scattering index),
+    delta [nfit, nfree], data [nfit, nchan, nbin] (float32 or float64),
+    inv_errs [nfit, nchan, nbin] -> float64 [nfit, nfree + 1, nfree + 1]
+    on the device: J^T J, J^T r in the last column, chi^2 in the corner.
+    workspace: a uint8 device tensor to reuse between calls (any size; a
+    larger one is allocated when it is too small)."""
+    code = str(model_code)
+    if len(code) != 3 or any(c not in "01" for c in code):
+        raise KeyError(code)     # evolve_parameter's dictionary lookup
+    dev = device(dev)
+    prm = to_dev(params, dev, torch.float64)
+    if prm.dim() == 1:
+        prm = prm.unsqueeze(0)
+    nfit, npar = prm.shape
+    if npar < 2 or (npar - 2) % 6:
+        raise ValueError("params must hold 2 + 6*ngauss values per fit")
+    f = to_dev(freqs, dev, torch.float64).reshape(nfit, -1).contiguous()
+    nchan = f.shape[1]
+    si = to_dev(np.broadcast_to(np.asarray(scattering_index, dtype=float),
+                                (nfit,)), dev, torch.float64).contiguous()
+    nr = to_dev(np.broadcast_to(np.asarray(nu_ref, dtype=float), (nfit,)),
+                dev, torch.float64).contiguous()
+    if not isinstance(data, torch.Tensor):
+        data = np.asarray(data)
+    ddt = torch.float32 if data.dtype in (torch.float32, np.float32) \
+        else torch.float64
+    d = to_dev(data, dev, ddt)
+    if d.dim() == 2:
+        d = d.unsqueeze(0)
+    if d.shape[:2] != (nfit, nchan):
+        raise ValueError("data must be [nfit, nchan, nbin]")
+    nbin = d.shape[2]
+    w = to_dev(inv_errs, dev, torch.float64).reshape(d.shape).contiguous()
+    fi = np.ascontiguousarray(free_idx, dtype=np.int32).reshape(-1)
+    nfree = fi.size
+    dl = np.zeros((nfit, 0))
+    if nfree:
+        dl = np.ascontiguousarray(np.broadcast_to(
+            np.asarray(delta, dtype=np.float64).reshape((-1, nfree)),
+            (nfit, nfree)))
+    lib = _lib.load()
+    need = lib.ppf_gauss_lsq_workspace_bytes(nfit, nchan, nbin, nfree)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    gram = torch.empty((nfit, nfree + 1, nfree + 1), dtype=torch.float64,
+                       device=dev)
+    ctx = _lib.context(dev.index)
+    rc = lib.ppf_gauss_lsq_batch(
+        ctx, nfit, nchan, nbin, (npar - 2) // 6, code.encode(), _p(prm),
+        _p(si), _p(f), _p(nr), nfree, fi.ctypes.data, dl.ctypes.data,
+        _lib.PPF_F32 if ddt == torch.float32 else _lib.PPF_F64, _p(d), _p(w),
+        _p(gram), _p(workspace), workspace.numel(), _stream(dev))
+    _lib.check(rc, ctx)
+    # free_idx / delta are host arrays the stream still reads
+    torch.cuda.current_stream(dev).synchronize()
+    return gram
+
+
+class GaussLsqEvaluator:
+    """The device evaluator of _gaussfit.levenberg_marquardt for ONE fit:
+    (p_ext, free_idx, delta) -> Gram matrix (numpy), p_ext the parameters
+    with the scattering index appended.  The data, weights and workspace
+    stay on the device between calls.  time_kernels=True brackets each call
+    with HIP events; kernel_ms then lists the device time of every call."""
+
+    def __init__(self, model_code, data, inv_errs, freqs, nu_ref, dev=None,
+                 time_kernels=False):
+        self.dev = device(dev)
+        self.code = model_code
+        data = np.asarray(data) if not isinstance(data, torch.Tensor) else data
+        ddt = torch.float32 if data.dtype in (torch.float32, np.float32) \
+            else torch.float64
+        self.data = to_dev(data, self.dev, ddt).unsqueeze(0)
+        self.w = to_dev(inv_errs, self.dev, torch.float64).unsqueeze(0)
+        self.freqs = to_dev(freqs, self.dev, torch.float64).reshape(1, -1)
+        self.nu_ref = float(nu_ref)
+        self.ws = None
+        self.time_kernels = time_kernels
+        self.kernel_ms = []
+
+    def __call__(self, p_ext, free_idx, delta):
+        p_ext = np.asarray(p_ext, dtype=np.float64)
+        nchan, nbin = self.data.shape[1:]
+        need = _lib.load().ppf_gauss_lsq_workspace_bytes(1, nchan, nbin,
+                                                         len(free_idx))
+        if self.ws is None or self.ws.numel() < need:
+            self.ws = torch.empty(max(need, 256), dtype=torch.uint8,
+                                  device=self.dev)
+        if self.time_kernels:
+            e0 = torch.cuda.Event(enable_timing=True)
+            e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+        g = gauss_lsq(self.code, p_ext[None, :-1], [p_ext[-1]], self.freqs,
+                      [self.nu_ref], free_idx, delta, self.data, self.w,
+                      dev=self.dev, workspace=self.ws)
+        if self.time_kernels:
+            e1.record()
+            e1.synchronize()
+            self.kernel_ms.append(e0.elapsed_time(e1))
+        return g[0].cpu().numpy()
+
+
 def spline_portraits(mean_prof, eigvec, tck, freqs, nbin=None, dev=None):
     """PCA + B-spline model portraits (pplib.gen_spline_portrait,
     pplib.py:966-990) on the device (ppf_spline_portrait_batch): mean_prof

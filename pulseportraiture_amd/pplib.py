@@ -201,6 +201,147 @@ def gen_gaussian_portrait(model_code, params, scattering_index, phases, freqs,
     return out
 
 
+def _profile_to_portrait(params):
+    """2 + 3 ngauss profile values (DC, tau, loc, wid, amp ...) -> the 2 + 6
+    ngauss portrait parameters with zero slopes: with the linear code '111'
+    at freqs = [nu_ref] every value passes through exactly."""
+    params = np.asarray(params, dtype=float)
+    ngauss = (len(params) - 2) // 3
+    out = np.zeros(2 + 6 * ngauss)
+    out[:2] = params[:2]
+    out[2::6], out[4::6], out[6::6] = params[2::3], params[3::3], params[4::3]
+    return out
+
+
+def gen_gaussian_profile(params, nbin):
+    """pplib.py:859-883: a profile of ngauss components (DC, tau [bin], then
+    loc, wid, amp each), one row of k_gauss_port."""
+    return gen_gaussian_portrait("111", _profile_to_portrait(params), 0.0,
+                                 np.zeros(nbin), [1.0], 1.0)[0]
+
+
+def _gauss_fit(model_code, data, params, alpha, errs, vary, freqs, nu_ref,
+               evaluator):
+    """The Levenberg-Marquardt fit both Gaussian fits share
+    (_gaussfit.levenberg_marquardt on ppf_gauss_lsq_batch)."""
+    from . import _gaussfit
+    data = np.asarray(data)
+    errs = np.broadcast_to(np.asarray(errs, dtype=float), data.shape)
+    if evaluator is None:
+        evaluator = engine.GaussLsqEvaluator(model_code, data, 1.0 / errs,
+                                             freqs, nu_ref)
+    p0 = np.append(np.asarray(params, dtype=float), float(alpha))
+    lo, hi = _gaussfit.portrait_bounds(len(p0) - 1)
+    return _gaussfit.levenberg_marquardt(evaluator, p0, vary, lo, hi,
+                                         data.size)
+
+
+def fit_gaussian_profile(data, init_params, errs, fit_flags=None,
+                         fit_scattering=False, quiet=True, evaluator=None):
+    """pplib.py:1922-2002 without lmfit: the same bounded least-squares
+    problem (tau >= 0, 0 <= wid <= wid_max, amp >= 0 through lmfit's MINUIT
+    transforms) solved by _gaussfit's MINPACK-style Levenberg-Marquardt on
+    the device's normal equations (one channel of ppf_gauss_lsq_batch).
+    As in the reference a given fit_flags has NO tau entry: it lists DC and
+    then the 3 ngauss component values, and fit_scattering is spliced in.
+    Returns DataBunch(fitted_params, fit_errs, residuals, chi2, dof); a
+    fixed parameter's error is 0.0 (lmfit gives None).  evaluator (not in
+    the reference) replaces the device evaluator, see _gaussfit."""
+    data = np.asarray(data)
+    nparam = len(init_params)
+    ngauss = (nparam - 2) // 3
+    if fit_flags is None:
+        flags = [True] * nparam
+        flags[1] = bool(fit_scattering)
+    else:
+        flags = [bool(fit_flags[0]), bool(fit_scattering)] + \
+                [bool(fit_flags[i]) for i in range(1, nparam - 1)]
+    vary = np.zeros(2 + 6 * ngauss + 1, dtype=bool)
+    vary[:2] = flags[:2]
+    vary[2:-1:6], vary[4:-1:6], vary[6:-1:6] = \
+        flags[2::3], flags[3::3], flags[4::3]
+    errs = np.broadcast_to(np.asarray(errs, dtype=float), data.shape)
+    p, perr, chi2, dof, lm_results = _gauss_fit(
+        "111", data[None, :], _profile_to_portrait(init_params), 0.0,
+        errs[None, :], vary, [1.0], 1.0, evaluator)
+    pick = np.r_[0, 1, np.ravel([[2 + 6 * g, 4 + 6 * g, 6 + 6 * g]
+                                 for g in range(ngauss)])].astype(int)
+    fitted_params, fit_errs = p[pick], perr[pick]
+    if evaluator is None:
+        residuals = data - gen_gaussian_profile(fitted_params, len(data))
+    else:
+        residuals = None
+    if not quiet:
+        print("Multi-Gaussian Profile Fit Results")
+        print("status:", lm_results.message)
+        print("Gaussians:", ngauss)
+        print("DoF:", dof)
+        print("reduced chi-sq: %.2f" % (chi2 / dof))
+    return DataBunch(fitted_params=fitted_params, fit_errs=fit_errs,
+                     residuals=residuals, chi2=chi2, dof=dof)
+
+
+def fit_gaussian_portrait(model_code, data, init_params, scattering_index,
+                          errs, fit_flags, fit_scattering_index, phases, freqs,
+                          nu_ref, join_params=[], P=None, quiet=True,
+                          evaluator=None):
+    """pplib.py:2005-2133 without lmfit: evolving Gaussian components fitted
+    to a portrait by _gaussfit's MINPACK-style Levenberg-Marquardt on lmfit's
+    internal variables (limits pplib.py:2041-2101), every Jacobian and
+    chi^2 from one ppf_gauss_lsq_batch call.  Returns DataBunch(lm_results,
+    fitted_params, fit_errs, scattering_index, scattering_index_err, chi2,
+    dof); lm_results has message, nfev, success, covar and residual (the
+    weighted residuals, flat).  A fixed parameter's error is 0.0 (lmfit
+    gives None).  join_params (several archives in one fit) is outside the
+    accelerated path.  evaluator (not in the reference) replaces the device
+    evaluator, see _gaussfit."""
+    if len(join_params):
+        raise NotImplementedError("fit_gaussian_portrait(join_params=...) is "
+                                  "outside the accelerated path")
+    data = np.asarray(data)
+    errs = np.broadcast_to(np.asarray(errs, dtype=float), data.shape)
+    vary = np.append(np.asarray(fit_flags, dtype=float) != 0,
+                     bool(fit_scattering_index))
+    p, perr, chi2, dof, lm_results = _gauss_fit(
+        model_code, data, init_params, scattering_index, errs, vary,
+        np.asarray(freqs, dtype=float), nu_ref, evaluator)
+    if evaluator is None:
+        model = gen_gaussian_portrait(model_code, p[:-1], p[-1], phases,
+                                      freqs, nu_ref)
+        lm_results.residual = np.ravel((data - model) / errs)
+    if not quiet:
+        print("Gaussian Portrait Fit")
+        print("status:", lm_results.message)
+        print("Gaussians:", (len(init_params) - 2) // 6)
+        print("DoF:", dof)
+        print("reduced chi-sq: %.2g" % (chi2 / dof))
+    return DataBunch(lm_results=lm_results, fitted_params=p[:-1],
+                     fit_errs=perr[:-1], scattering_index=p[-1],
+                     scattering_index_err=perr[-1], chi2=chi2, dof=dof)
+
+
+def write_model(filename, name, model_code, nu_ref, model_params, fit_flags,
+                alpha, fit_alpha, append=False, quiet=False):
+    """pplib.py:2931-2968: a .gmodel file in the reference's format, byte
+    for byte (read_model and the CPU package read it).  model_params[1] is
+    the scattering timescale in seconds."""
+    lines = ["MODEL   %s\n" % name, "CODE    %s\n" % model_code,
+             "FREQ    %.5f\n" % nu_ref,
+             "DC     % .8f %d\n" % (model_params[0], fit_flags[0]),
+             "TAU    % .8f %d\n" % (model_params[1], fit_flags[1]),
+             "ALPHA  % .3f      %d\n" % (alpha, fit_alpha)]
+    for ig in range((len(model_params) - 2) // 6):
+        vals = []
+        for v, f in zip(model_params[2 + ig * 6:8 + ig * 6],
+                        fit_flags[2 + ig * 6:8 + ig * 6]):
+            vals.append("% .8f %d" % (v, f))
+        lines.append("COMP%02d %s\n" % (ig + 1, "  ".join(vals)))
+    with open(filename, "a" if append else "w") as fh:
+        fh.writelines(lines)
+    if not quiet:
+        print("%s written." % filename)
+
+
 def read_model(modelfile, phases=None, freqs=None, P=None, quiet=False):
     """pplib.py:2971-3057: parse a .gmodel file; build the portrait if
     phases/freqs are given."""
