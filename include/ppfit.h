@@ -577,6 +577,46 @@ int ppf_gauss_lsq_batch(ppf_ctx *ctx, int32_t nfit, int32_t nchan, int32_t nbin,
                         const double *inv_errs, double *gram, void *workspace,
                         size_t workspace_bytes, void *stream);
 
+/* Stationary-wavelet denoise-and-score engine (added within ABI 6): the
+ * search of pplib.smart_smooth (pplib.py:1740-1838) over decomposition level
+ * and threshold factor.  The transform is the undecimated 'db8' transform of
+ * a periodic row of even length nbin, written from its definition (DESIGN.md
+ * section 0, ppspline): a_0 = x, a_j / d_j the circular convolution of
+ * a_{j-1} with dec_lo / dec_hi upsampled by 2^(j-1) (the filter wraps at
+ * small nbin), synthesis half the adjoint.
+ * ppf_swt_analyse_batch: per profile (prof [nprof][nbin] f64, device) the
+ * rows a_j, d_j for j = 1 .. nlevel into the workspace, medians
+ * [nprof][nlevel] = np.median(|a_j| u |d_j|) (2 nbin values, exact
+ * selection, the mean of the two middle ones) and noise [nprof] =
+ * get_noise_PS(prof) (ppf_noise_batch's rule, frac = 4); both device, f64.
+ * ppf_swt_score_batch: ncase independent cases on the analysed batch (same
+ * prof, medians, noise, workspace).  cases [ncase][3] int32 = (profile,
+ * level L in [1, nlevel], 0 hard / 1 soft) and fact [ncase] f64 are HOST
+ * arrays, checked here and copied by the call; they must stay untouched
+ * until the stream has passed it.  Per case
+ *     lambda = fact * (medians[profile][L - 1] / 0.6745) * sqrt(2 ln nbin)
+ * thresholds a_L and d_1 .. d_L (hard: 0 where |c| < lambda; soft:
+ * c * max(1 - lambda / |c|, 0)), the row s is synthesised and
+ * out [ncase][3] = (sum_{k >= 1} |rfft(s)_k|^2, get_noise_PS(s) *
+ * sqrt(nbin / 2), sum(((prof - s) / noise[profile])^2) / nbin), what
+ * pplib.fit_wavelet_smooth_function combines; smooth [ncase][nbin] receives
+ * s when not NULL.  No atomics: results are bitwise reproducible.
+ * The workspace (ppf_swt_workspace_bytes; 0 for an unsupported shape) holds
+ * the coefficients of one analysed batch and up to max_ncase cases per call.
+ * PPF_EUNSUP: nbin odd or outside [32, 8192], nlevel > log2(nbin) for a
+ * power of two, nlevel > 1 for any other nbin.  PPF_EINVAL: nlevel < 1, a
+ * case naming a profile or level out of range or another threshold type, a
+ * non-finite factor, a small workspace, a NULL array or context.  All of
+ * this is checked on the host before any launch. */
+size_t ppf_swt_workspace_bytes(int32_t nprof, int32_t nbin, int32_t nlevel, int32_t max_ncase);
+int ppf_swt_analyse_batch(ppf_ctx *ctx, int32_t nprof, int32_t nbin, int32_t nlevel,
+                          const double *prof, double *medians, double *noise, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int ppf_swt_score_batch(ppf_ctx *ctx, int32_t nprof, int32_t nbin, int32_t nlevel,
+                        const double *prof, const double *medians, const double *noise,
+                        int32_t ncase, const int32_t *cases, const double *fact, double *out,
+                        double *smooth, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Spline (PCA + B-spline) model portraits: pplib.gen_spline_portrait
  * (pplib.py:966-990) as called by pplib.read_spline_model (pplib.py:3060-3096)
  * from pptoas.GetTOAs.get_TOAs (pptoas.py:416-419) for make_spline_model

@@ -132,6 +132,12 @@ SIGNATURES = {
                                            _vp, _i32, _vp, _vp, _i32, _vp,
                                            _vp, _vp, _vp, ctypes.c_size_t,
                                            _vp]),
+    "ppf_swt_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32]),
+    "ppf_swt_analyse_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _vp,
+                                             _vp, _vp, ctypes.c_size_t, _vp]),
+    "ppf_swt_score_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _vp,
+                                           _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                           ctypes.c_size_t, _vp]),
     "ppf_spline_portrait_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32,
                                                  _i32, _i32, _i32, _vp, _vp,
                                                  _vp, _vp, _vp, _vp, _vp]),

@@ -1649,6 +1649,106 @@ int ppf_gauss_lsq_batch(ppf_ctx *ctx, int32_t nfit, int32_t nchan, int32_t nbin,
     return PPF_OK;
 }
 
+namespace {
+// workspace of the ppf_swt_* calls: the coefficient rows and the device
+// copies of the case lists
+struct SwtLayout {
+    size_t coef, cases, fact, bytes;
+};
+// PPF_OK, or the error code of an unsupported / invalid transform shape
+int swt_shape(int64_t nprof, int64_t nbin, int64_t nlevel, int64_t max_ncase, SwtLayout &L) {
+    if ((nbin & 1) || nbin < 32 || nbin > 8192 || !nbin_supported((int)nbin)) return PPF_EUNSUP;
+    if (nprof < 0 || nlevel < 1 || max_ncase < 0) return PPF_EINVAL;
+    const bool pow2 = (nbin & (nbin - 1)) == 0;
+    if (pow2 ? ((int64_t)1 << nlevel) > nbin : nlevel > 1) return PPF_EUNSUP;
+    if (nprof > 0x7fffffffLL || max_ncase > 0x7fffffffLL) return PPF_EUNSUP;   // one workgroup each
+    size_t o = 0;
+    L.coef = o;  o += align256(sizeof(double) * (size_t)(nprof > 0 ? nprof : 1) * nlevel * 2 * nbin);
+    L.cases = o; o += align256(sizeof(int32_t) * 3 * (size_t)(max_ncase > 0 ? max_ncase : 1));
+    L.fact = o;  o += align256(sizeof(double) * (size_t)(max_ncase > 0 ? max_ncase : 1));
+    L.bytes = o;
+    return PPF_OK;
+}
+int swt_fail(ppf_ctx *ctx, int rc, int nbin, int nlevel) {
+    return fail(ctx, rc, "swt: nbin=%d nlevel=%d: nbin even in [32, 8192], 1 <= nlevel <= log2(nbin) for a "
+                         "power of two, nlevel = 1 otherwise", nbin, nlevel);
+}
+}  // namespace
+
+size_t ppf_swt_workspace_bytes(int32_t nprof, int32_t nbin, int32_t nlevel, int32_t max_ncase) {
+    SwtLayout L;
+    return swt_shape(nprof, nbin, nlevel, max_ncase, L) == PPF_OK ? L.bytes : 0;
+}
+
+int ppf_swt_analyse_batch(ppf_ctx *ctx, int32_t nprof, int32_t nbin, int32_t nlevel, const double *prof,
+                          double *medians, double *noise, void *workspace, size_t workspace_bytes,
+                          void *stream) {
+    // every argument check on the host, before the context or any launch
+    SwtLayout L;
+    int rc = swt_shape(nprof, nbin, nlevel, 0, L);
+    if (rc) return swt_fail(ctx, rc, nbin, nlevel);
+    if (nprof > 0 && (!prof || !medians || !noise)) return fail(ctx, PPF_EINVAL, "null swt argument");
+    if (nprof > 0 && (!workspace || workspace_bytes < L.bytes))
+        return fail(ctx, PPF_EINVAL, "workspace: %zu bytes given, %zu needed", workspace_bytes, L.bytes);
+    if (!ctx) return PPF_EINVAL;
+    if (nprof == 0) return PPF_OK;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
+    hipStream_t st = (hipStream_t)stream;
+    ppf::SwtArgs a{};
+    if ((rc = twiddles(ctx, nbin, st, &a.T, &a.T2))) return rc;
+    a.nprof = nprof; a.nbin = nbin; a.nlevel = nlevel; a.kc = noise_kc(nbin / 2 + 1, 4);
+    a.pow2 = (nbin & (nbin - 1)) == 0;
+    a.sq2ln = std::sqrt(2.0 * std::log((double)nbin));
+    a.prof = prof; a.coef = (double *)((char *)workspace + L.coef); a.med = medians; a.noise = noise;
+    if ((e = ppf::launch_swt_analyse(a, st)) != hipSuccess) return hip_fail(ctx, e, "k_swt_analyse");
+    return PPF_OK;
+}
+
+int ppf_swt_score_batch(ppf_ctx *ctx, int32_t nprof, int32_t nbin, int32_t nlevel, const double *prof,
+                        const double *medians, const double *noise, int32_t ncase, const int32_t *cases,
+                        const double *fact, double *out, double *smooth, void *workspace,
+                        size_t workspace_bytes, void *stream) {
+    SwtLayout L;
+    int rc = swt_shape(nprof, nbin, nlevel, ncase, L);
+    if (rc) return swt_fail(ctx, rc, nbin, nlevel);
+    if (ncase > 0 && (!cases || !fact || !out || !prof || !medians || !noise))
+        return fail(ctx, PPF_EINVAL, "null swt argument");
+    for (int c = 0; c < ncase; ++c) {
+        const int32_t *k = cases + 3 * (size_t)c;
+        if (k[0] < 0 || k[0] >= nprof)
+            return fail(ctx, PPF_EINVAL, "case %d: profile %d outside [0, %d)", c, k[0], nprof);
+        if (k[1] < 1 || k[1] > nlevel)
+            return fail(ctx, PPF_EINVAL, "case %d: level %d outside [1, %d]", c, k[1], nlevel);
+        if (k[2] != 0 && k[2] != 1) return fail(ctx, PPF_EINVAL, "case %d: threshold type %d", c, k[2]);
+        if (!std::isfinite(fact[c])) return fail(ctx, PPF_EINVAL, "case %d: factor %g", c, fact[c]);
+    }
+    if (ncase > 0 && (!workspace || workspace_bytes < L.bytes))
+        return fail(ctx, PPF_EINVAL, "workspace: %zu bytes given, %zu needed", workspace_bytes, L.bytes);
+    if (!ctx) return PPF_EINVAL;
+    if (ncase == 0) return PPF_OK;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
+    hipStream_t st = (hipStream_t)stream;
+    ppf::SwtArgs a{};
+    if ((rc = twiddles(ctx, nbin, st, &a.T, &a.T2))) return rc;
+    char *ws = (char *)workspace;
+    if ((e = hipMemcpyAsync(ws + L.cases, cases, sizeof(int32_t) * 3 * (size_t)ncase, hipMemcpyHostToDevice,
+                            st)) != hipSuccess ||
+        (e = hipMemcpyAsync(ws + L.fact, fact, sizeof(double) * (size_t)ncase, hipMemcpyHostToDevice, st)) !=
+            hipSuccess)
+        return hip_fail(ctx, e, "hipMemcpyAsync(cases, fact)");
+    a.nprof = nprof; a.nbin = nbin; a.nlevel = nlevel; a.kc = noise_kc(nbin / 2 + 1, 4); a.ncase = ncase;
+    a.pow2 = (nbin & (nbin - 1)) == 0;
+    a.sq2ln = std::sqrt(2.0 * std::log((double)nbin));
+    a.prof = prof; a.coef = (double *)(ws + L.coef);
+    a.med = const_cast<double *>(medians); a.noise = const_cast<double *>(noise);
+    a.cases = (const int32_t *)(ws + L.cases); a.fact = (const double *)(ws + L.fact);
+    a.out = out; a.smooth = smooth;
+    if ((e = ppf::launch_swt_score(a, st)) != hipSuccess) return hip_fail(ctx, e, "k_swt_score");
+    return PPF_OK;
+}
+
 int ppf_spline_portrait_batch(ppf_ctx *ctx, int32_t nport, int32_t nchan, int32_t nbin_model,
                               int32_t nbin, int32_t ncomp, int32_t nknots, int32_t degree,
                               const double *mean_prof, const double *eigvec, const double *knots,

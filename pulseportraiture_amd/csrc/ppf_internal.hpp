@@ -407,6 +407,26 @@ struct GaussLsqArgs {
 };
 hipError_t launch_gauss_lsq(const GaussLsqArgs &a, hipStream_t st);
 
+// ppf_swt_analyse_batch / ppf_swt_score_batch (ppf_swt.hip): the stationary
+// db8 wavelet transform of profiles and the denoise-and-score cases of
+// pplib.smart_smooth
+struct SwtArgs {
+    int nprof, nbin, nlevel, kc, ncase;
+    bool pow2;                   // nbin a power of two (else nlevel == 1)
+    double sq2ln;                // sqrt(2 ln nbin)
+    const double *prof;          // [nprof][nbin]
+    double *coef;                // [nprof][nlevel][2][nbin]: a_j, d_j
+    double *med;                 // [nprof][nlevel]: median(|a_j| u |d_j|)
+    double *noise;               // [nprof]: get_noise_PS of the profile
+    const int32_t *cases;        // [ncase][3] (device copy): profile, level, soft
+    const double *fact;          // [ncase] (device copy)
+    double *out;                 // [ncase][3]: signal, noise, red_chi2
+    double *smooth;              // [ncase][nbin] or null
+    const double2 *T, *T2;
+};
+hipError_t launch_swt_analyse(const SwtArgs &a, hipStream_t st);
+hipError_t launch_swt_score(const SwtArgs &a, hipStream_t st);
+
 // pplib.gen_spline_portrait (pplib.py:966-990): per (portrait, channel) row,
 // splev of the B-spline curve tck at the channel frequency (FITPACK splev /
 // fpbspl, ext = 0), the eigenvector expansion plus the mean profile, and

@@ -1005,6 +1005,94 @@ class GaussLsqEvaluator:
         return g[0].cpu().numpy()
 
 
+class SwtHandle(object):
+    """One analysed batch of profiles (swt_analyse): the device arrays
+    swt_score reads.  medians [nprof, nlevel] and noise [nprof] are NumPy
+    copies."""
+
+
+def swt_analyse(profs, nlevel, max_ncase=0, dev=None):
+    """The stationary db8 transform of profs [nprof, nbin] (float64) to
+    nlevel levels on the device (ppf_swt_analyse_batch): the coefficient
+    rows stay in the handle's workspace, which has room for max_ncase cases
+    per swt_score call (it grows on demand)."""
+    dev = device(dev)
+    p = to_dev(profs, dev, torch.float64)
+    if p.dim() == 1:
+        p = p.unsqueeze(0)
+    nprof, nbin = p.shape
+    nlevel = int(nlevel)
+    lib = _lib.load()
+    h = SwtHandle()
+    h.dev, h.prof, h.nprof, h.nbin, h.nlevel = dev, p, nprof, nbin, nlevel
+    h.ncase = max(int(max_ncase), 1)
+    need = lib.ppf_swt_workspace_bytes(nprof, nbin, nlevel, h.ncase)
+    h.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    h.med = torch.empty((nprof, max(nlevel, 1)), dtype=torch.float64,
+                        device=dev)
+    h.sig = torch.empty(nprof, dtype=torch.float64, device=dev)
+    ctx = _lib.context(dev.index)
+    rc = lib.ppf_swt_analyse_batch(ctx, nprof, nbin, nlevel, _p(p), _p(h.med),
+                                   _p(h.sig), _p(h.ws), h.ws.numel(),
+                                   _stream(dev))
+    _lib.check(rc, ctx)
+    h.medians = h.med.cpu().numpy()
+    h.noise = h.sig.cpu().numpy()
+    return h
+
+
+def swt_score(h, cases, facts, smooth=False):
+    """Denoise-and-score cases on an analysed batch (ppf_swt_score_batch):
+    cases [ncase, 3] = (profile, level, 0 hard / 1 soft), facts [ncase] ->
+    (out [ncase, 3] = (signal, noise, red_chi2), the smoothed rows [ncase,
+    nbin] or None), NumPy."""
+    cs = np.ascontiguousarray(cases, dtype=np.int32).reshape(-1, 3)
+    fs = np.ascontiguousarray(facts, dtype=np.float64).reshape(-1)
+    ncase = len(cs)
+    if len(fs) != ncase:
+        raise ValueError("one factor per case")
+    lib = _lib.load()
+    dev = h.dev
+    if ncase > h.ncase:
+        # the coefficients sit at the front of the workspace: a longer case
+        # list needs a larger one, the rows are copied over
+        need = lib.ppf_swt_workspace_bytes(h.nprof, h.nbin, h.nlevel, ncase)
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        ncoef = h.nprof * h.nlevel * 2 * h.nbin * 8
+        ws[:ncoef].copy_(h.ws[:ncoef])
+        h.ws, h.ncase = ws, ncase
+    out = torch.empty((ncase, 3), dtype=torch.float64, device=dev)
+    rows = torch.empty((ncase, h.nbin), dtype=torch.float64, device=dev) \
+        if smooth else None
+    ctx = _lib.context(dev.index)
+    rc = lib.ppf_swt_score_batch(
+        ctx, h.nprof, h.nbin, h.nlevel, _p(h.prof), _p(h.med), _p(h.sig),
+        ncase, cs.ctypes.data, fs.ctypes.data, _p(out), _p(rows), _p(h.ws),
+        h.ws.numel(), _stream(dev))
+    _lib.check(rc, ctx)
+    # cases / facts are host arrays the stream still reads
+    torch.cuda.current_stream(dev).synchronize()
+    return out.cpu().numpy(), (rows.cpu().numpy() if smooth else None)
+
+
+class SwtEvaluator(object):
+    """The device evaluator of pplib.wavelet_smooth / smart_smooth (see
+    _swt.py for the interface)."""
+
+    def __init__(self, dev=None):
+        self.dev = dev
+
+    def noise(self, rows):
+        return noise_rows(np.atleast_2d(np.asarray(rows, dtype=np.float64)),
+                          4, self.dev).cpu().numpy()
+
+    def analyse(self, profs, nlevel, max_ncase=0):
+        return swt_analyse(profs, nlevel, max_ncase, self.dev)
+
+    def score(self, h, cases, facts, smooth=False):
+        return swt_score(h, cases, facts, smooth)
+
+
 def spline_portraits(mean_prof, eigvec, tck, freqs, nbin=None, dev=None):
     """PCA + B-spline model portraits (pplib.gen_spline_portrait,
     pplib.py:966-990) on the device (ppf_spline_portrait_batch): mean_prof

@@ -18,6 +18,7 @@ import time
 
 import numpy as np
 
+from .pplib import DataPortrait as _DataPortrait
 from .pplib import (DataBunch, default_model, file_is_type, fit_gaussian_portrait,
                     fit_gaussian_profile, fit_phase_shift, fit_portrait,
                     gaussian_profile, gen_gaussian_portrait, get_noise,
@@ -27,7 +28,7 @@ from .pplib import (DataBunch, default_model, file_is_type, fit_gaussian_portrai
 _OUTSIDE = "%s is outside the accelerated path"
 
 
-class DataPortrait(object):
+class DataPortrait(_DataPortrait):
     """The data a Gaussian model is fitted to (pplib.py:155-349 for a single
     archive, with ppgauss.py's methods).  datafile: a fold-mode PSRFITS file
     (loaded with dedisperse=True, tscrunch=True on the PSRFITS fast path) or
@@ -39,40 +40,8 @@ class DataPortrait(object):
     def __init__(self, datafile=None, joinfile=None, quiet=False,
                  **load_data_kwargs):
         self.init_params = []
-        if joinfile is not None:
-            raise NotImplementedError(_OUTSIDE % "DataPortrait(joinfile=...)")
-        self.joinfile = None
-        self.njoin = 0
-        self.join_params = []
-        self.join_ichans = []
-        self.all_join_params = []
-        if isinstance(datafile, dict):
-            self.datafile = datafile.get("filename", "DataBunch")
-            self.data = datafile
-        else:
-            if file_is_type(datafile, "ASCII"):
-                raise NotImplementedError(
-                    _OUTSIDE % "DataPortrait(metafile): joining several "
-                    "archives")
-            self.datafile = datafile
-            self.data = load_data(datafile, dedisperse=True,
-                                  dededisperse=False, tscrunch=True,
-                                  pscrunch=True, fscrunch=False,
-                                  quiet=quiet, **load_data_kwargs)
-        self.datafiles = [self.datafile]
-        self.__dict__.update(**self.data)
-        if getattr(self, "source", None) is None:
-            self.source = "noname"
-        self.freqs = np.asarray(self.freqs, dtype=float)
-        self.nchan, self.nbin = np.asarray(self.subints[0, 0]).shape
-        ok = np.asarray(self.ok_ichans[0], dtype=int)
-        self.port = np.asarray(self.masks[0, 0]) * \
-            np.asarray(self.subints[0, 0], dtype=float)
-        self.portx = self.port[ok]
-        self.freqsxs = [self.freqs[0, ok]]
-        self.noise_stdsxs = np.asarray(self.noise_stds)[0, 0, ok]
-        self.SNRsxs = np.asarray(self.SNRs)[0, 0, ok]
-        self.nchanx = len(ok)
+        _DataPortrait.__init__(self, datafile, joinfile, quiet,
+                               **load_data_kwargs)
 
     def fit_profile(self, profile, tau=0.0, fixscat=True, auto_gauss=0.0,
                     profile_fit_flags=None, show=True):

@@ -435,6 +435,9 @@ class _SplineUnpickler(pickle.Unpickler):
         ("builtins", "list"), ("builtins", "tuple"), ("builtins", "int"),
         ("builtins", "float"), ("builtins", "str"), ("builtins", "bytes"),
         ("__builtin__", "list"), ("__builtin__", "tuple"),
+        # protocol 2 spells an EMPTY array's buffer bytes(): the empty tck of
+        # a mean-profile model (make_spline_model with no component)
+        ("__builtin__", "bytes"),
         ("_codecs", "encode"), ("copy_reg", "_reconstructor"),
         ("copyreg", "_reconstructor"), ("__builtin__", "object"),
         ("builtins", "object"),
@@ -679,6 +682,317 @@ def _raise_status(status):
                            "scattering fit (PPF_ST_NOSPACE)")
 
 
+# ------------------------------------- PCA + wavelet smoothing (ppspline) --
+def count_crossings(x, x0):
+    """pplib.py:710-718: how often x crosses the level x0 (changes of the
+    sign of x - x0 between neighbours, less the samples exactly on it)."""
+    d = np.asarray(x) - x0
+    s = np.sign(d)
+    return int(np.count_nonzero(s[1:] != s[:-1]) - np.count_nonzero(d == 0))
+
+
+def get_SNR(prof, fudge=3.25):
+    """pplib.py:2376-2395: sum / (noise sqrt(W_eq)) / fudge of a
+    baseline-removed profile; 0 where the equivalent width is not positive."""
+    prof = np.asarray(prof, dtype=float)
+    noise = get_noise(prof)
+    Weq = prof.sum() / prof.max()
+    mask = np.where(Weq <= 0.0, 0.0, 1.0)
+    Weq = np.where(Weq <= 0.0, 1.0, Weq)
+    return prof.sum() / (noise * Weq ** 0.5) * mask / fudge
+
+
+def normalize_portrait(port, method="rms", weights=None, return_norms=False):
+    """pplib.py:2553-2598: each non-zero profile divided by its mean
+    ('mean'), maximum ('max'), fitted scale against the weighted mean
+    profile ('prof', fit_phase_shift), off-pulse noise ('rms', get_noise)
+    or Euclidean length ('abs')."""
+    if method not in ("mean", "max", "prof", "rms", "abs"):
+        print("Unknown method for normalize_portrait(...), '%s'." % method)
+        return None
+    port = np.asarray(port, dtype=float)
+    norm_port = np.zeros(port.shape)
+    norm_vals = np.ones(len(port))
+    if method == "prof":
+        good = np.where(port.sum(axis=1) != 0.0)[0]
+        w = np.ones(len(good)) if weights is None else \
+            np.asarray(weights)[good]
+        mean_prof = np.average(port[good], axis=0, weights=w)
+    for ichan, prof in enumerate(port):
+        if not prof.any():
+            continue
+        if method == "mean":
+            norm = prof.mean()
+        elif method == "max":
+            norm = prof.max()
+        elif method == "prof":
+            norm = fit_phase_shift(prof, mean_prof).scale
+        elif method == "rms":
+            norm = get_noise(prof)
+        else:
+            norm = (prof ** 2.0).sum() ** 0.5
+        norm_port[ichan] = prof / norm
+        norm_vals[ichan] = norm
+    if return_norms:
+        return norm_port, norm_vals
+    return norm_port
+
+
+def pca(port, mean_prof=None, weights=None, quiet=False):
+    """pplib.py:1564-1602: principal components of the nchan x nbin port,
+    the eigen-decomposition of np.cov(delta_port.T, aweights=weights,
+    ddof=1), sorted by decreasing eigenvalue (eigenvectors are columns).
+
+    The covariance follows np.cov exactly: it subtracts its own weighted
+    average of delta_port again and normalises by sum(w) - sum(w^2) /
+    sum(w).  Host float64; the eigh is LAPACK either way.
+
+    Deviation from the reference: with nchan < nbin the nbin x nbin
+    covariance (rank <= nchan) is never formed; the nchan x nchan dual
+    sqrt(w) Xc Xc^T sqrt(w) is diagonalised and its eigenvectors projected
+    back.  Returned are eigval [nbin] (zero beyond the rank) and eigvec
+    [nbin, min(nchan, nbin)] with unit columns, where the reference returns
+    nbin x nbin; a column whose eigenvalue is below n eps lambda_max (n the
+    diagonalised dimension) is zero, where the reference returns an
+    arbitrary basis of the null space.  Only the first ten columns are ever
+    looked at (find_significant_eigvec).  Eigenvector signs are LAPACK's and
+    may differ from the reference's."""
+    port = np.asarray(port, dtype=np.float64)
+    nmes, ndim = port.shape
+    if not quiet:
+        print("Performing principal component analysis on data with %d "
+              "dimensions and %d measurements..." % (ndim, nmes))
+    w = np.ones(nmes) if weights is None else \
+        np.asarray(weights, dtype=np.float64)
+    if mean_prof is None:
+        mean_prof = (port.T * w).T.sum(axis=0) / w.sum()
+    X = port - mean_prof
+    wsum = w.sum()
+    X = X - (X * w[:, None]).sum(axis=0) / wsum     # np.cov's own average
+    norm = wsum - (w * w).sum() / wsum
+    ncol = min(nmes, ndim)
+    eigval = np.zeros(ndim)
+    if nmes < ndim:
+        Z = X * np.sqrt(w)[:, None]
+        lam, U = np.linalg.eigh(np.dot(Z, Z.T) / norm)
+        order = np.argsort(lam)[::-1]
+        lam, U = lam[order], U[:, order]
+        V = np.dot(Z.T, U)
+    else:
+        lam, V = np.linalg.eigh(np.dot(X.T * w, X) / norm)
+        order = np.argsort(lam)[::-1]
+        lam, V = lam[order], V[:, order]
+    keep = lam >= len(lam) * np.finfo(np.float64).eps * max(lam[0], 0.0)
+    keep &= lam > 0.0
+    eigvec = np.zeros((ndim, ncol))
+    lengths = np.sqrt((V * V).sum(axis=0))
+    eigvec[:, keep] = V[:, keep] / lengths[keep]
+    eigval[:ncol] = np.where(keep, lam, 0.0)
+    return eigval, eigvec
+
+
+def reconstruct_portrait(port, mean_prof, eigvec):
+    """pplib.py:1605-1622: port projected onto the column space of eigvec
+    about mean_prof."""
+    delta_port = np.asarray(port) - mean_prof
+    return np.dot(np.dot(delta_port, eigvec), eigvec.T) + mean_prof
+
+
+def _swt_evaluator(evaluator):
+    from . import _swt
+    return _swt.default_evaluator() if evaluator is None else evaluator
+
+
+def _check_wavelet(wavelet):
+    if wavelet != "db8":
+        raise NotImplementedError("only the 'db8' wavelet is built (the "
+                                  "reference's default), got %r" % (wavelet,))
+
+
+def _soft(threshtype):
+    if threshtype not in ("hard", "soft"):
+        raise ValueError("threshtype must be 'hard' or 'soft'")
+    return int(threshtype == "soft")
+
+
+def wavelet_smooth(port, wavelet="db8", nlevel=5, threshtype="hard", fact=1.0,
+                   evaluator=None):
+    """pplib.py:1692-1737 without PyWavelets: the stationary-wavelet
+    denoised portrait or profile (ppf_swt_analyse_batch /
+    ppf_swt_score_batch; the transform is written from its definition, see
+    _swt.py, and has not been compared with PyWavelets itself).  Only 'db8';
+    even nbin in [32, 8192], nlevel <= log2(nbin) for a power of two and 1
+    otherwise, else NotImplementedError.  evaluator (not in the reference)
+    replaces the device evaluator, see _swt."""
+    from . import _swt
+    _check_wavelet(wavelet)
+    port = np.asarray(port, dtype=np.float64)
+    one_prof = port.ndim == 1
+    rows = np.atleast_2d(port)
+    _swt.check_shape(rows.shape[1], nlevel)
+    ev = _swt_evaluator(evaluator)
+    h = ev.analyse(rows, nlevel, len(rows))
+    soft = _soft(threshtype)
+    smooth = ev.score(h, [(i, nlevel, soft) for i in range(len(rows))],
+                      [fact] * len(rows), smooth=True)[1]
+    return smooth[0] if one_prof else smooth
+
+
+def _wavelet_snr(score, rchi2_tol):
+    """The figure of merit of fit_wavelet_smooth_function from one
+    (signal, noise, red_chi2) triple."""
+    signal, noise, red_chi2 = score
+    if signal:
+        snr = signal / noise if noise else np.inf
+    else:
+        snr = 0.0
+    if abs(red_chi2 - 1.0) > rchi2_tol:
+        snr = 0.0
+    return -snr
+
+
+def fit_wavelet_smooth_function(fact, prof, wavelet, nlevel, threshtype,
+                                rchi2_tol, evaluator=None):
+    """pplib.py:1814-1838: minus the pseudo-S/N of the smoothed profile
+    (Fourier-domain signal over noise), 0 when the reduced chi^2 between
+    profile and smoothed profile is further than rchi2_tol from 1."""
+    from . import _swt
+    _check_wavelet(wavelet)
+    prof = np.asarray(prof, dtype=np.float64)
+    _swt.check_shape(len(prof), nlevel)
+    ev = _swt_evaluator(evaluator)
+    h = ev.analyse(prof[None, :], nlevel, 1)
+    fact = float(np.ravel(fact)[0])
+    out = ev.score(h, [(0, nlevel, _soft(threshtype))], [fact])[0]
+    return _wavelet_snr(out[0], rchi2_tol)
+
+
+def smart_smooth(port, try_nlevels=None, rchi2_tol=0.1, **kwargs):
+    """pplib.py:1740-1811: per profile the (nlevel, fact) of wavelet_smooth
+    that maximise the pseudo-S/N with the reduced chi^2 within rchi2_tol of
+    1, searched as the reference searches: scipy.optimize.brute over fact
+    in [0, 3] (Ns = 30, the default fmin finish) for every level, the best
+    level kept; a profile whose final chi^2 fails the gate comes back zero.
+    The 30 grid values of every (profile, level) are computed by ONE batched
+    evaluator call up front and served to brute from a table; the fmin
+    finish evaluates singly.  try_nlevels = 0, odd nbin (the input back; a
+    single profile as a [1, nbin] array, as the reference has it) and
+    all-zero rows return as in the reference; a length that is not a power
+    of two tries one level.  kwargs: threshtype, wavelet ('db8' only) and evaluator (not
+    in the reference: replaces the device evaluator, see _swt)."""
+    import scipy.optimize as opt
+    from . import _swt
+    if try_nlevels == 0:
+        return port
+    port = np.asarray(port, dtype=np.float64)
+    one_prof = port.ndim == 1
+    rows = np.atleast_2d(port)
+    nbin = rows.shape[1]
+    if nbin % 2 != 0:
+        # as the reference: a single odd-length profile comes back wrapped
+        # in a [1, nbin] array (pplib.py:1765-1769), which is why
+        # find_significant_eigvec finds nothing significant at odd nbin
+        return rows if one_prof else port
+    if np.modf(np.log2(nbin))[0] != 0.0:
+        try_nlevels = 1
+    elif try_nlevels is None:
+        try_nlevels = int(np.log2(nbin))
+    _check_wavelet(kwargs.get("wavelet", "db8"))
+    soft = _soft(kwargs.get("threshtype", "hard"))
+    _swt.check_shape(nbin, try_nlevels)
+    ev = _swt_evaluator(kwargs.get("evaluator"))
+    smooth_port = np.zeros(rows.shape)
+    todo = [i for i, prof in enumerate(rows) if np.any(prof)]
+    if not todo:
+        return smooth_port[0] if one_prof else smooth_port
+    Ns = 30
+    # brute's own grid: the table is keyed by the very floats it will pass
+    grid = np.mgrid[slice(0.0, 3.0, complex(Ns))]
+    ncase = len(todo) * try_nlevels * Ns
+    h = ev.analyse(rows[todo], try_nlevels, ncase)
+    cases = [(ip, lev, soft) for ip in range(len(todo))
+             for lev in range(1, try_nlevels + 1) for _ in range(Ns)]
+    table = ev.score(h, cases, np.tile(grid, len(todo) * try_nlevels))[0]
+    table = table.reshape(len(todo), try_nlevels, Ns, 3)
+    for ip, iprof in enumerate(todo):
+        fun_vals = np.zeros(try_nlevels)
+        fact_mins = np.zeros(try_nlevels)
+        for ilevel in range(try_nlevels):
+            known = dict((float(f), table[ip, ilevel, ig])
+                         for ig, f in enumerate(grid))
+
+            def objective(fact, ip=ip, lev=ilevel + 1, known=known):
+                f = float(np.ravel(fact)[0])
+                score = known.get(f)
+                if score is None:
+                    score = ev.score(h, [(ip, lev, soft)], [f])[0][0]
+                return _wavelet_snr(score, rchi2_tol)
+
+            results = opt.brute(objective, ranges=[(0.0, 3.0)], Ns=Ns,
+                                full_output=True)
+            fact_mins[ilevel] = results[0][0]
+            fun_vals[ilevel] = results[1]
+        ilevel_min = fun_vals.argmin()
+        out, srow = ev.score(h, [(ip, ilevel_min + 1, soft)],
+                             [fact_mins[ilevel_min]], smooth=True)
+        if not abs(out[0, 2] - 1.0) > rchi2_tol:
+            smooth_port[iprof] = srow[0]
+    return smooth_port[0] if one_prof else smooth_port
+
+
+def find_significant_eigvec(eigvec, check_max=10, return_max=10,
+                            snr_cutoff=150.0, check_crossings=True,
+                            check_acorr=True, return_smooth=True, **kwargs):
+    """pplib.py:1625-1689: the indices of the leading eigenvectors (columns
+    of eigvec) whose smart_smooth-ed version has a Fourier-domain S/N of at
+    least snr_cutoff, with the reference's extra look at borderline ones
+    (zero crossings; its autocorrelation branch is kept as written there,
+    where it cannot be reached); with return_smooth also the array of
+    smoothed eigenvectors.  At odd nbin smart_smooth hands a single profile
+    back as a [1, nbin] array, whose rfft(...)[1:] is empty: the S/N is 0 and
+    no eigenvector is significant, as in the reference (make_spline_model
+    then writes the mean-profile model).  At most eigvec.shape[1] columns are examined
+    (pca returns min(nchan, nbin) of them).  kwargs go to smart_smooth."""
+    eigvec = np.asarray(eigvec, dtype=np.float64)
+    ev_ = _swt_evaluator(kwargs.get("evaluator")) \
+        if eigvec.shape[1] else None
+    if return_smooth:
+        smooth_eigvec = np.zeros(eigvec.shape)
+    ieig = []
+    for ivec in range(min(max(check_max, return_max), eigvec.shape[1])):
+        add_eigvec = False
+        raw = eigvec[:, ivec]
+        ev = smart_smooth(raw, **kwargs)
+        ev_noise = ev_.noise(raw[None, :])[0] * np.sqrt(len(ev) / 2.0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ev_snr = np.sum(np.abs(np.fft.rfft(ev)[1:]) ** 2) / ev_noise
+        if ev_snr >= snr_cutoff:
+            close = ev_snr < 3 * snr_cutoff
+            if check_crossings and close:
+                ncross = count_crossings(abs(ev), 0.1 * abs(ev).max())
+                if ncross < int(0.02 * len(ev)):
+                    add_eigvec = True
+            elif check_acorr and close and add_eigvec:
+                acorr = np.correlate(ev, ev, "same")
+                fwhm = acorr.argmax() - \
+                    np.where(acorr > acorr.max() / 2.0)[0].min()
+                add_eigvec = bool(fwhm > 5)
+                if not add_eigvec:
+                    print("Borderline case eigenvector %d failed test." % ivec)
+            else:
+                add_eigvec = True
+        if add_eigvec:
+            ieig.append(ivec)
+            if return_smooth:
+                smooth_eigvec[:, ivec] = ev
+        if ivec + 1 == check_max or len(ieig) == return_max:
+            break
+    ieig = np.array(ieig)
+    if return_smooth:
+        return ieig, smooth_eigvec
+    return ieig
+
+
 # ------------------------------------------------------------- TOA output --
 def filter_TOAs(TOAs, flag, cutoff, criterion=">=", pass_unflagged=False,
                 return_culled=False):
@@ -774,3 +1088,95 @@ def file_is_type(filename, filetype="ASCII"):
         except UnicodeDecodeError:
             return False
     return False
+
+
+# ------------------------------------------------------------ DataPortrait --
+_OUTSIDE = "%s is outside the accelerated path"
+
+
+class DataPortrait(object):
+    """The data a portrait model is made from (pplib.py:155-349 for a single
+    archive); ppgauss.DataPortrait and ppspline.DataPortrait add their
+    model makers.  datafile: a fold-mode PSRFITS file (loaded with
+    dedisperse=True, tscrunch=True on the PSRFITS fast path) or an in-memory
+    DataBunch with load_data's keys (subints [nsub, npol, nchan, nbin],
+    masks, freqs [nsub, nchan], ok_ichans, noise_stds, SNRs [nsub, npol,
+    nchan], Ps, phases, nu0, bw, source; weights [nsub, nchan], unit on
+    ok_ichans when missing); its first sub-integration is the portrait."""
+
+    def __init__(self, datafile=None, joinfile=None, quiet=False,
+                 **load_data_kwargs):
+        if joinfile is not None:
+            raise NotImplementedError(_OUTSIDE % "DataPortrait(joinfile=...)")
+        self.joinfile = None
+        self.njoin = 0
+        self.join_params = []
+        self.join_ichans = []
+        self.all_join_params = []
+        if isinstance(datafile, dict):
+            self.datafile = datafile.get("filename", "DataBunch")
+            self.data = datafile
+        else:
+            if file_is_type(datafile, "ASCII"):
+                raise NotImplementedError(
+                    _OUTSIDE % "DataPortrait(metafile): joining several "
+                    "archives")
+            self.datafile = datafile
+            self.data = load_data(datafile, dedisperse=True,
+                                  dededisperse=False, tscrunch=True,
+                                  pscrunch=True, fscrunch=False,
+                                  quiet=quiet, **load_data_kwargs)
+        self.datafiles = [self.datafile]
+        self.__dict__.update(**self.data)
+        if getattr(self, "source", None) is None:
+            self.source = "noname"
+        self.freqs = np.asarray(self.freqs, dtype=float)
+        self.nchan, self.nbin = np.asarray(self.subints[0, 0]).shape
+        ok = np.asarray(self.ok_ichans[0], dtype=int)
+        self.port = np.asarray(self.masks[0, 0]) * \
+            np.asarray(self.subints[0, 0], dtype=float)
+        self.portx = self.port[ok]
+        self.freqsxs = [self.freqs[0, ok]]
+        self.noise_stdsxs = np.asarray(self.noise_stds)[0, 0, ok]
+        self.SNRsxs = np.asarray(self.SNRs)[0, 0, ok]
+        self.nchanx = len(ok)
+        if getattr(self, "weights", None) is None:
+            self.weights = np.zeros((1, self.nchan))
+            self.weights[0, ok] = 1.0
+
+    def normalize_portrait(self, method="rms"):
+        """pplib.py:379-404: normalize_portrait(...) on the full and the
+        condensed portrait, the noise levels re-measured."""
+        if method not in ("mean", "max", "prof", "rms", "abs"):
+            print("Unknown method for normalize_portrait(...), '%s'." % method)
+            return
+        weights = weightsx = None
+        if method == "prof":
+            w = np.asarray(self.weights, dtype=float)
+            weights, weightsx = w[0], w[w > 0]
+        self.noise_stds = np.array(self.noise_stds, dtype=float)
+        self.unnorm_noise_stds = np.copy(self.noise_stds)
+        self.port, self.norm_values = normalize_portrait(
+            self.port, method, weights=weights, return_norms=True)
+        self.noise_stds[0, 0] = get_noise(self.port, chans=True)
+        self.flux_prof = self.port.mean(axis=1)
+        self.unnorm_noise_stdsxs = np.copy(self.noise_stdsxs)
+        self.portx = normalize_portrait(self.portx, method, weights=weightsx,
+                                        return_norms=False)
+        self.noise_stdsxs = get_noise(self.portx, chans=True)
+        self.flux_profx = self.portx.mean(axis=1)
+
+    def unnormalize_portrait(self):
+        """pplib.py:406-420: undo normalize_portrait."""
+        if not hasattr(self, "unnorm_noise_stds"):
+            return
+        ok = np.asarray(self.ok_ichans[0], dtype=int)
+        self.port = (self.norm_values * self.port.T).T
+        self.noise_stds = np.copy(self.unnorm_noise_stds)
+        del self.unnorm_noise_stds
+        self.flux_prof = self.port.mean(axis=1)
+        self.portx = (self.norm_values[ok] * self.portx.T).T
+        self.noise_stdsxs = np.copy(self.unnorm_noise_stdsxs)
+        del self.unnorm_noise_stdsxs
+        self.flux_profx = self.portx.mean(axis=1)
+        self.norm_values = np.ones(len(self.port))
