@@ -648,6 +648,39 @@ int ppf_synth_batch(ppf_ctx *ctx, int32_t nsub, int32_t nchan, int32_t nbin,
                     int64_t first_sub, int32_t out_dtype, void *out,
                     void *stream);
 
+/* Simulated fold-mode archives (added within ABI 6): the profiles
+ * pplib.make_fake_pulsar (pplib.py:3302-3499) writes, built on the device and
+ * stored as the samples a PSRFITS SUBINT table holds.  One workgroup per row
+ * (sub-int s, polarisation p, channel n):
+ *     X_k = M_k exp(2 pi i k phase[s][n]) B_k gain[s][p][n],   0 <= k < nbin/2,
+ *     B_k = 1 / (1 + 2 pi i k tau_n[s][n])   (1 for tau_n = 0),
+ * M = rfft(model[model_of[s]][n]); DC keeps its real part, and the Nyquist
+ * harmonic is Re(M_N) cos(2 pi N phase) Re(B_N) gain, what the reference's
+ * two real transforms (rotation, then scattering) leave of it.  The inverse
+ * real transform of X plus N(0, noise[n]) per bin (none for noise[n] = 0) is
+ * the row; the deviates come from ppf_synth_batch's counter RNG keyed by
+ * (seed, first_sub + s, p, n, bin), so a sub-int's samples do not depend on
+ * how a job is split into calls.
+ * model [nmodel][nchan][nbin] f64, model_of [nsub] int32 (clamped to [0,
+ * nmodel)), phase and tau_n [nsub][nchan] f64 (turns), gain
+ * [nsub][npol][nchan] f64, noise [nchan] f64: device arrays.
+ * out_kind PPF_FAKE_F64: out [nsub][npol][nchan][nbin] f64 rows (dat_scl,
+ * dat_offs unused).  PPF_FAKE_I16: the same rows quantised per profile as
+ * psrfits.quantize does it, bit for bit (offset f32((lo + hi) / 2), scale
+ * f32(max((hi - lo) / 2 / 32767, 1e-30)), rint, clipped), out the big-endian
+ * int16 of the DATA column in its layout [nsub][npol][nchan][nbin], dat_scl /
+ * dat_offs [nsub][npol * nchan] f32 in host byte order.
+ * PPF_EUNSUP: nbin odd or outside [32, 8192] (the LDS row transforms), more
+ * than 2^31 - 1 rows.  PPF_EINVAL: a count below its minimum, first_sub < 0,
+ * another out_kind, out not 16-byte aligned, a NULL array or context.  All of
+ * this is checked on the host before any launch. */
+enum ppf_fake_kind { PPF_FAKE_I16 = 0, PPF_FAKE_F64 = 1 };
+int ppf_fake_batch(ppf_ctx *ctx, int32_t nsub, int32_t npol, int32_t nchan, int32_t nbin,
+                   int32_t nmodel, const double *model, const int32_t *model_of,
+                   const double *phase, const double *tau_n, const double *gain,
+                   const double *noise, uint64_t seed, int64_t first_sub, int32_t out_kind,
+                   void *out, float *dat_scl, float *dat_offs, void *stream);
+
 /* Host-side (CPU) helper: real roots of a degree <= 8 polynomial, highest
  * power first, with np.roots semantics (companion-matrix eigenvalues with an
  * exactly zero imaginary part; pptoaslib.py:834-836, 902-904).  Returns the

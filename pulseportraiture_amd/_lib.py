@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("PPFIT_LIB", os.path.join(_HERE, "lib", "libppfit.so")
 PPF_OK, PPF_EINVAL, PPF_EHIP, PPF_ENOMEM, PPF_EUNSUP = 0, -1, -2, -3, -4
 PPF_F32, PPF_F64 = 0, 1
 PPF_MODE_FULL, PPF_MODE_LEGACY2 = 0, 1
+PPF_FAKE_I16, PPF_FAKE_F64 = 0, 1   # ppf_fake_batch out_kind
 ST_SUCCESS, ST_MAXITER, ST_CONVERGED, ST_LINALG = 0, 1, 2, 3
 ST_NO_ROOT, ST_SINGULAR, ST_NONFINITE, ST_NOFIT = 0x100, 0x200, 0x400, 0x800
 ST_NOSPACE = 0x1000
@@ -145,6 +146,10 @@ SIGNATURES = {
                                        _vp, _vp, ctypes.c_double,
                                        ctypes.c_double, ctypes.c_uint64,
                                        ctypes.c_int64, _i32, _vp, _vp]),
+    "ppf_fake_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64,
+                                      ctypes.c_int64, _i32, _vp, _vp, _vp,
+                                      _vp]),
     "ppf_unpack_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32]),
     "ppf_unpack_psrfits_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32,
                                                 _i32, _vp, ctypes.c_int64,

@@ -1820,6 +1820,54 @@ int ppf_synth_batch(ppf_ctx *ctx, int32_t nsub, int32_t nchan, int32_t nbin, con
     return PPF_OK;
 }
 
+int ppf_fake_batch(ppf_ctx *ctx, int32_t nsub, int32_t npol, int32_t nchan, int32_t nbin, int32_t nmodel,
+                   const double *model, const int32_t *model_of, const double *phase,
+                   const double *tau_n, const double *gain, const double *noise, uint64_t seed,
+                   int64_t first_sub, int32_t out_kind, void *out, float *dat_scl, float *dat_offs,
+                   void *stream) {
+    // every argument check on the host, before the context or any launch
+    if ((nbin & 1) || nbin < 32 || nbin > 8192 || !nbin_supported(nbin))
+        return fail(ctx, PPF_EUNSUP, "nbin=%d: even nbin in [32, 8192] (the LDS row transforms)", nbin);
+    if (nsub < 0 || npol < 1 || nchan < 1 || nmodel < 1 || first_sub < 0)
+        return fail(ctx, PPF_EINVAL, "bad fake shape (nsub=%d npol=%d nchan=%d nmodel=%d first_sub=%lld)",
+                    nsub, npol, nchan, nmodel, (long long)first_sub);
+    if (out_kind != PPF_FAKE_I16 && out_kind != PPF_FAKE_F64) return fail(ctx, PPF_EINVAL, "out_kind");
+    if ((int64_t)nsub * npol * nchan > 0x7fffffffLL)   // one workgroup per row
+        return fail(ctx, PPF_EUNSUP, "nsub * npol * nchan = %lld rows: at most 2^31 - 1 per call",
+                    (long long)((int64_t)nsub * npol * nchan));
+    if (nsub > 0 && (!model || !model_of || !phase || !tau_n || !gain || !noise || !out ||
+                     (out_kind == PPF_FAKE_I16 && (!dat_scl || !dat_offs))))
+        return fail(ctx, PPF_EINVAL, "null fake argument");
+    if (((uintptr_t)out & 15) || ((uintptr_t)dat_scl & 3) || ((uintptr_t)dat_offs & 3))
+        return fail(ctx, PPF_EINVAL, "out must be 16-byte aligned, dat_scl / dat_offs 4-byte aligned");
+    if (!ctx) return PPF_EINVAL;
+    if (nsub == 0) return PPF_OK;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
+    hipStream_t st = (hipStream_t)stream;
+    const double2 *T, *T2;
+    int rc = twiddles(ctx, nbin, st, &T, &T2);
+    if (rc) return rc;
+    // the templates' spectra in a buffer owned by this call (as ppf_synth_batch)
+    double2 *Mft = nullptr;
+    const size_t nharm = (size_t)nbin / 2 + 1;
+    e = hipMallocAsync((void **)&Mft, sizeof(double2) * (size_t)nmodel * nchan * nharm, st);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipMallocAsync(fake)");
+    ppf::RfftArgs ra{nbin, rfft_log2(nbin), PPF_F64, model, T, T2, Mft};
+    if ((e = ppf::launch_rfft_rows(ra, (int64_t)nmodel * nchan, st)) != hipSuccess) {
+        (void)hipFreeAsync(Mft, st);
+        return hip_fail(ctx, e, "k_rfft_rows");
+    }
+    ppf::FakeArgs a{};
+    a.nsub = nsub; a.npol = npol; a.nchan = nchan; a.nbin = nbin; a.nmodel = nmodel; a.kind = out_kind;
+    a.Mft = Mft; a.model_of = model_of; a.phase = phase; a.tau = tau_n; a.gain = gain; a.noise = noise;
+    a.seed = seed; a.first = first_sub; a.T = T; a.T2 = T2; a.out = out; a.scl = dat_scl; a.offs = dat_offs;
+    e = ppf::launch_fake(a, st);
+    (void)hipFreeAsync(Mft, st);
+    if (e != hipSuccess) return hip_fail(ctx, e, "k_fake");
+    return PPF_OK;
+}
+
 int ppf_poly_real_roots_host(const double *coeffs, int deg, double *out) {
     if (!coeffs || !out || deg < 0 || deg > 8) return -2;
     return ppf::poly_real_roots(coeffs, deg, out);

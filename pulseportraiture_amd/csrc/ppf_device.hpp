@@ -74,6 +74,18 @@ __device__ __forceinline__ double2 cexp2pi(double t) {
     return cmk(c, s);
 }
 
+// counter-based RNG of the synthetic-data kernels (k_synth, k_fake): a hash
+// of the sample's key, and its map to a uniform deviate in (0, 1]
+__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+__device__ __forceinline__ double u01(uint64_t h) {   // (0, 1]
+    return ((double)(h >> 11) + 1.0) * (1.0 / 9007199254740992.0);
+}
+
 // ---------------------------------------------------------------------------
 // reductions (fixed order -> bitwise reproducible)
 // ---------------------------------------------------------------------------

@@ -330,6 +330,23 @@ struct SynthArgs {
     void *out;
 };
 
+// ppf_fake_batch (ppf_fake.hip): simulated archive rows, quantised on the device
+constexpr int kFakeI16 = 0, kFakeF64 = 1;   // PPF_FAKE_I16 / PPF_FAKE_F64
+struct FakeArgs {
+    int nsub, npol, nchan, nbin, nmodel, kind;
+    const double2 *Mft;          // [nmodel][nchan][N+1]
+    const int32_t *model_of;     // [nsub]
+    const double *phase, *tau;   // [nsub][nchan]: rotation [rot], scattering time [rot]
+    const double *gain;          // [nsub][npol][nchan]
+    const double *noise;         // [nchan]
+    uint64_t seed;
+    int64_t first;
+    const double2 *T, *T2;
+    void *out;                   // [nsub][npol][nchan][nbin] big-endian int16 or f64
+    float *scl, *offs;           // [nsub][npol * nchan] (kFakeI16)
+};
+hipError_t launch_fake(const FakeArgs &a, hipStream_t st);
+
 // pptoaslib.get_scales_full (pptoaslib.py:953-971) per (sub-int, channel) row
 struct ScalesArgs {
     int nsub, nchan, nharm, log10_tau;

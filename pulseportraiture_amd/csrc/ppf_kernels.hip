@@ -1309,16 +1309,7 @@ __global__ __launch_bounds__(kBlock) void k_phase_shift(PhaseShiftArgs a) {
 // ===========================================================================
 // k_synth: synthetic sub-integrations (bench / tests)
 // ===========================================================================
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ double u01(uint64_t h) {   // (0, 1]
-    return ((double)(h >> 11) + 1.0) * (1.0 / 9007199254740992.0);
-}
-
+// (the counter RNG, splitmix64 / u01, is in ppf_device.hpp)
 template <bool MX>
 __global__ __launch_bounds__(kBlock) void k_synth(SynthArgs a) {
     extern __shared__ __attribute__((aligned(16))) double2 lds[];

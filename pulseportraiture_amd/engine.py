@@ -153,6 +153,18 @@ def dev_to_host(t):
     return h.numpy().copy()
 
 
+def dev_to_host_view(t):
+    """dev_to_host without the final copy: a NumPy view of the caller's
+    page-locked "view" buffer holding device tensor t (synchronises the
+    current stream).  Valid until the same thread's next call."""
+    n = t.numel() * t.element_size()
+    buf = _pinned("view", n)
+    h = buf[:n].view(t.dtype).view(t.shape)
+    h.copy_(t, non_blocking=True)
+    torch.cuda.current_stream(t.device).synchronize()
+    return h.numpy()
+
+
 def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -1154,6 +1166,63 @@ def synth(model, freqs, phi, DM, P, nu_ref, noise, seed, out_dtype=torch.float32
         _p(out), _stream(dev))
     _lib.check(rc, ctx)
     return out
+
+
+def fake_subints(model, model_of, phase, tau_n, gain, noise, seed, first_sub=0,
+                 quantized=False, dev=None):
+    """Simulated archive rows on the device (ppf_fake_batch, k_fake): per
+    (sub-int s, polarisation p, channel n) the template model[model_of[s]][n]
+    rotated by phase[s][n] turns, scattered by tau_n[s][n] turns (0: not),
+    scaled by gain[s][p][n], plus N(0, noise[n]) per bin (noise[n] = 0: no
+    noise at all) from the counter RNG keyed by (seed, first_sub + s, p, n,
+    bin): sub-int s of a call with first_sub = f is sub-int f + s of the
+    whole job, however it is split.
+
+    model [nmodel, nchan, nbin] (or [nchan, nbin]), model_of [nsub], phase and
+    tau_n [nsub, nchan], gain [nsub, npol, nchan], noise [nchan].
+
+    quantized=False: float64 rows [nsub, npol, nchan, nbin].
+    quantized=True: (data, scl, offs): the same rows as psrfits.quantize
+    digitises them, data a uint8 tensor [nsub, npol * nchan * nbin * 2] of
+    big-endian int16 in the SUBINT DATA layout (the bytes of the file), scl /
+    offs float32 [nsub, npol * nchan]."""
+    dev = device(dev)
+    m = to_dev(model, dev, torch.float64)
+    if m.dim() == 2:
+        m = m.unsqueeze(0)
+    nmodel, nchan, nbin = m.shape
+    g = to_dev(gain, dev, torch.float64)
+    if g.dim() != 3 or g.shape[2] != nchan:
+        raise ValueError("gain must be [nsub, npol, nchan]")
+    nsub, npol = int(g.shape[0]), int(g.shape[1])
+    mo = np.asarray(_host(model_of), dtype=np.int64).reshape(-1)
+    if mo.size != nsub or (nsub and (mo.min() < 0 or mo.max() >= nmodel)):
+        raise ValueError("model_of must hold nsub indices in [0, nmodel)")
+    mo_t = to_dev(mo.astype(np.int32), dev, torch.int32)
+    ph = to_dev(phase, dev, torch.float64)
+    tn = to_dev(tau_n, dev, torch.float64)
+    nz = to_dev(noise, dev, torch.float64).reshape(-1).contiguous()
+    if tuple(ph.shape) != (nsub, nchan) or tuple(tn.shape) != (nsub, nchan) \
+            or nz.numel() != nchan:
+        raise ValueError("phase, tau_n must be [nsub, nchan], noise [nchan]")
+    if quantized:
+        out = torch.empty((nsub, npol * nchan * nbin * 2), dtype=torch.uint8,
+                          device=dev)
+        scl = torch.empty((nsub, npol * nchan), dtype=torch.float32,
+                          device=dev)
+        offs = torch.empty_like(scl)
+    else:
+        out = torch.empty((nsub, npol, nchan, nbin), dtype=torch.float64,
+                          device=dev)
+        scl = offs = None
+    ctx = _lib.context(dev.index)
+    rc = _lib.load().ppf_fake_batch(
+        ctx, nsub, npol, nchan, nbin, nmodel, _p(m), _p(mo_t), _p(ph), _p(tn),
+        _p(g), _p(nz), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)),
+        int(first_sub), _lib.PPF_FAKE_I16 if quantized else _lib.PPF_FAKE_F64,
+        _p(out), _p(scl), _p(offs), _stream(dev))
+    _lib.check(rc, ctx)
+    return (out, scl, offs) if quantized else out
 
 
 def results_numpy(res):

@@ -593,6 +593,43 @@ def rotate_profile(profile, phase=0.0):
                               ref_len=True).cpu().numpy()[0]
 
 
+def add_DM_nu(port, phase=0.0, DM=None, P=None, freqs=None, xs=[-2.0],
+              Cs=[1.0], nu_ref=np.inf):
+    """pplib.py:2601-2638: rotate_portrait with the dispersive term sum_j C_j
+    (nu**x_j - nu_ref**x_j); the per-channel phases on the host, the
+    rotation on the GPU (ppf_rotate_batch)."""
+    port = np.asarray(port)
+    nchan = len(port)
+    if DM is None and freqs is None:
+        ph = np.full(nchan, float(phase))
+    else:
+        D = Dconst * DM / P
+        freqs = np.asarray(freqs, dtype=float)
+        if not hasattr(Cs, "__iter__"):
+            Cs = np.ones(len(xs))
+        if len(Cs) < len(xs):
+            Cs = list(Cs) + list(np.ones(len(xs) - len(Cs)))
+        freq_term = 0.0
+        for C, x in zip(Cs, xs):
+            freq_term = freq_term + C * (freqs ** x - nu_ref ** x)
+        ph = phase + (D * freq_term)
+    return engine.rotate_rows(port, ph, ref_len=True).cpu().numpy()
+
+
+def add_scintillation(port, params=None, random=True, nsin=2, amax=1.0,
+                      wmax=3.0):
+    """pplib.py:1190-1218: the sinusoidal pattern on the host, the product a
+    broadcast."""
+    from . import fake
+    port = np.asarray(port)
+    if params is None and random is False:
+        return port
+    if params is None:
+        params = fake.random_scint_params(nsin, amax, wmax)
+    pattern = fake.scint_pattern(len(port), params)
+    return np.transpose(np.transpose(port) * pattern)
+
+
 def fit_phase_shift(data, model, noise=None, bounds=[-0.5, 0.5], Ns=100):
     """pplib.py:2136-2182 on the GPU: brute grid of Ns points + scipy-fmin
     replica (Nelder-Mead) polish, then the reference's error formulas."""
@@ -991,6 +1028,82 @@ def find_significant_eigvec(eigvec, check_max=10, return_max=10,
     if return_smooth:
         return ieig, smooth_eigvec
     return ieig
+
+
+# ------------------------------------------------------- simulated archives --
+def make_fake_pulsar(modelfile, ephemeris, outfile="fake_pulsar.fits", nsub=1,
+                     npol=1, nchan=512, nbin=2048, nu0=1500.0, bw=800.0,
+                     tsub=300.0, phase=0.0, dDM=0.0, start_MJD=None,
+                     weights=None, noise_stds=1.0, scales=1.0,
+                     dedispersed=False, t_scat=0.0, alpha=scattering_alpha,
+                     scint=False, xs=None, Cs=None, nu_DM=np.inf,
+                     state="Stokes", telescope="GBT", quiet=False, seed=None,
+                     dev=None):
+    """pplib.py:3302-3499 without PSRCHIVE: one fold-mode PSRFITS file of
+    simulated data.  The profiles are built and digitised on the device
+    (engine.fake_subints, k_fake) and cross to the host as the 2-byte samples
+    the file stores (psrfits.write_psrfits_rows).
+
+    The arguments are the reference's, plus seed (the device RNG's; None
+    draws one from np.random) and dev.  Departures, all of them documented in
+    fake.fake_tables / fake.read_par / fake.fake_epochs:
+      - the ephemeris is read by the reference's plain-text fallback parser
+        (PSR or PSRJ, RAJ, DECJ, F0 or P0, F1, PEPOCH, DM);
+      - the folding period of a sub-int is 1 / (F0 + F1 dt) at its centre;
+        the reference takes it from a TEMPO polyco through PSRCHIVE,
+        topocentric Doppler shift included;
+      - with xs=None the rows are rotated by phase and DM + dDM (the
+        ephemeris DM goes into the header), which the reference leaves to
+        PSRCHIVE's dededisperse() with the effect that its phase and dDM do
+        nothing; with xs given, phase is transformed once per sub-int, not
+        compounded;
+      - the noise comes from the device RNG, so the global NumPy stream is
+        consumed only by seed=None and by scint=True, not once per profile.
+    Every channel gets data whatever its weight.  Each polarisation is the
+    same model with its own noise draw; npol = 1 is written as AA+BB, npol =
+    4 as IQUV (state "Stokes") or AABBCRCI ("Coherence").  Other npol and
+    dedispersed=True raise NotImplementedError (the loader does not recognise
+    dedispersed files), as does an odd nbin or one outside [32, 8192]."""
+    from . import fake, psrfits
+    if dedispersed:
+        raise NotImplementedError("dedispersed=True: psrfits.load_data does "
+                                  "not recognise dedispersed files")
+    if npol == 1:
+        pol_type = "AA+BB"
+    elif npol == 4 and state in ("Stokes", "Coherence"):
+        pol_type = "IQUV" if state == "Stokes" else "AABBCRCI"
+    else:
+        raise NotImplementedError("npol=%r state=%r: npol 1, or 4 as Stokes "
+                                  "/ Coherence" % (npol, state))
+    if nbin % 2 or nbin < 32 or nbin > 8192:
+        raise NotImplementedError("nbin=%d: even nbin in [32, 8192]" % nbin)
+    setup = fake.fake_setup(modelfile, ephemeris, nsub=nsub, npol=npol,
+                            nchan=nchan, nbin=nbin, nu0=nu0, bw=bw, tsub=tsub,
+                            phase=phase, dDM=dDM, start_MJD=start_MJD,
+                            noise_stds=noise_stds, scales=scales,
+                            t_scat=t_scat, alpha=alpha, scint=scint, xs=xs,
+                            Cs=Cs, nu_DM=nu_DM)
+    if setup == 0:
+        return 0
+    par, ep, tab, mdl = setup
+    if weights is None:
+        weights = np.ones([nsub, nchan])
+    if seed is None:
+        seed = int(np.random.randint(0, 2 ** 31 - 1))
+    dev = engine.device(dev)
+    data, scl, offs = engine.fake_subints(
+        fake.templates(mdl, tab, dev=dev), tab.model_of, tab.phi, tab.tau_n,
+        tab.gain, tab.noise, seed, quantized=True, dev=dev)
+    DECJ = par.DECJ if par.DECJ[0] in "+-" else "+" + par.DECJ
+    psrfits.write_psrfits_rows(
+        outfile, engine.dev_to_host_view(data), engine.dev_to_host(scl),
+        engine.dev_to_host(offs), np.tile(tab.freqs, (nsub, 1)), weights,
+        ep.Ps, ep.offs_sub, np.full(nsub, float(tsub)), nbin,
+        stt_imjd=ep.stt_imjd, stt_smjd=ep.stt_smjd, stt_offs=ep.stt_offs,
+        npol=npol, pol_type=pol_type, telescope=telescope, source=par.PSR,
+        dm=par.DM, obsfreq=nu0, obsbw=bw, ra=par.RAJ, dec=DECJ)
+    if not quiet:
+        print("\nUnloaded %s.\n" % outfile)
 
 
 # ------------------------------------------------------------- TOA output --

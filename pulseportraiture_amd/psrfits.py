@@ -396,38 +396,71 @@ def write_psrfits(filename, data, scl, offs, freqs, weights, periods,
     data = np.asarray(data, dtype=np.int16)
     nsub, npol_, nchan, nbin = data.shape
     assert npol_ == npol
+    raw = data.reshape(nsub, -1).astype(">i2").view(np.uint8)
+    return write_psrfits_rows(
+        filename, raw, scl, offs, freqs, weights, periods, offs_sub, tsubint,
+        nbin, stt_imjd=stt_imjd, stt_smjd=stt_smjd, stt_offs=stt_offs,
+        npol=npol, pol_type=pol_type, telescope=telescope, frontend=frontend,
+        backend=backend, source=source, dm=dm, be_delay=be_delay,
+        par_ang=par_ang)
+
+
+def write_psrfits_rows(filename, data, scl, offs, freqs, weights, periods,
+                       offs_sub, tsubint, nbin, stt_imjd=56000, stt_smjd=0,
+                       stt_offs=0.0, npol=1, pol_type="AA+BB", telescope="GBT",
+                       frontend="Rcvr1_2", backend="GUPPI", source="J1234+5678",
+                       dm=0.0, be_delay=0.0, par_ang=None, obsfreq=None,
+                       obsbw=None, ra=None, dec=None):
+    """write_psrfits for DATA rows already in file byte order (the output of
+    engine.fake_subints(quantized=True)): data is a uint8 array [nsub, npol *
+    nchan * nbin * 2] of big-endian int16 in the DATA layout [npol][nchan]
+    [nbin], written as it is, row by row, with no conversion or copy on the
+    host.  obsfreq / obsbw (default: the mean of freqs[0] and the channel
+    spacing times nchan) and the RA / DEC cards can be given."""
+    data = np.asarray(data)
+    freqs = np.asarray(freqs, dtype=float)
+    nsub, nchan = freqs.shape
+    if data.dtype != np.uint8 or data.shape != (nsub, npol * nchan * nbin * 2):
+        raise ValueError("data must be uint8 [nsub, npol * nchan * nbin * 2]")
     cols = [("TSUBINT", "1D", None), ("OFFS_SUB", "1D", None),
             ("PERIOD", "1D", None), ("PAR_ANG", "1E", None),
             ("DAT_FREQ", "%dD" % nchan, None), ("DAT_WTS", "%dE" % nchan, None),
             ("DAT_OFFS", "%dE" % (nchan * npol), None),
             ("DAT_SCL", "%dE" % (nchan * npol), None),
             ("DATA", "%dI" % (nbin * nchan * npol), "(%d,%d,%d)" % (nbin, nchan, npol))]
-    rowdt = np.dtype([("TSUBINT", ">f8"), ("OFFS_SUB", ">f8"), ("PERIOD", ">f8"),
-                      ("PAR_ANG", ">f4"), ("DAT_FREQ", ">f8", (nchan,)),
-                      ("DAT_WTS", ">f4", (nchan,)), ("DAT_OFFS", ">f4", (nchan * npol,)),
-                      ("DAT_SCL", ">f4", (nchan * npol,)),
-                      ("DATA", ">i2", (nbin * nchan * npol,))])
-    rows = np.zeros(nsub, dtype=rowdt)
-    rows["TSUBINT"] = tsubint
-    rows["OFFS_SUB"] = offs_sub
-    rows["PERIOD"] = periods
-    rows["PAR_ANG"] = 0.0 if par_ang is None else par_ang
-    rows["DAT_FREQ"] = freqs
-    rows["DAT_WTS"] = weights
-    rows["DAT_OFFS"] = offs
-    rows["DAT_SCL"] = scl
-    rows["DATA"] = data.reshape(nsub, -1)
-    obsbw = float(freqs[0, -1] - freqs[0, 0]) * nchan / max(nchan - 1, 1)
+    # the columns ahead of DATA, which ends each row
+    metadt = np.dtype([("TSUBINT", ">f8"), ("OFFS_SUB", ">f8"), ("PERIOD", ">f8"),
+                       ("PAR_ANG", ">f4"), ("DAT_FREQ", ">f8", (nchan,)),
+                       ("DAT_WTS", ">f4", (nchan,)), ("DAT_OFFS", ">f4", (nchan * npol,)),
+                       ("DAT_SCL", ">f4", (nchan * npol,))])
+    meta = np.zeros(nsub, dtype=metadt)
+    meta["TSUBINT"] = tsubint
+    meta["OFFS_SUB"] = offs_sub
+    meta["PERIOD"] = periods
+    meta["PAR_ANG"] = 0.0 if par_ang is None else par_ang
+    meta["DAT_FREQ"] = freqs
+    meta["DAT_WTS"] = weights
+    meta["DAT_OFFS"] = offs
+    meta["DAT_SCL"] = scl
+    rowbytes = metadt.itemsize + data.shape[1]
+    if obsbw is None:
+        obsbw = float(freqs[0, -1] - freqs[0, 0]) * nchan / max(nchan - 1, 1)
+    if obsfreq is None:
+        obsfreq = float(np.mean(freqs[0]))
     prim = [("SIMPLE", True), ("BITPIX", 8), ("NAXIS", 0), ("EXTEND", True),
             ("HDRVER", "6.1"), ("FITSTYPE", "PSRFITS"), ("OBS_MODE", "PSR"),
             ("TELESCOP", telescope), ("FRONTEND", frontend),
-            ("BACKEND", backend), ("SRC_NAME", source),
-            ("OBSFREQ", float(np.mean(freqs[0]))), ("OBSBW", obsbw),
-            ("OBSNCHAN", nchan), ("STT_IMJD", int(stt_imjd)),
-            ("STT_SMJD", int(stt_smjd)), ("STT_OFFS", float(stt_offs)),
-            ("BE_DELAY", float(be_delay)), ("CHAN_DM", float(dm))]
+            ("BACKEND", backend), ("SRC_NAME", source)]
+    if ra is not None:
+        prim.append(("RA", ra))
+    if dec is not None:
+        prim.append(("DEC", dec))
+    prim += [("OBSFREQ", float(obsfreq)), ("OBSBW", float(obsbw)),
+             ("OBSNCHAN", nchan), ("STT_IMJD", int(stt_imjd)),
+             ("STT_SMJD", int(stt_smjd)), ("STT_OFFS", float(stt_offs)),
+             ("BE_DELAY", float(be_delay)), ("CHAN_DM", float(dm))]
     ext = [("XTENSION", "BINTABLE"), ("BITPIX", 8), ("NAXIS", 2),
-           ("NAXIS1", rowdt.itemsize), ("NAXIS2", nsub), ("PCOUNT", 0),
+           ("NAXIS1", rowbytes), ("NAXIS2", nsub), ("PCOUNT", 0),
            ("GCOUNT", 1), ("TFIELDS", len(cols))]
     for i, (name, form, dim) in enumerate(cols, 1):
         ext += [("TTYPE%d" % i, name), ("TFORM%d" % i, form)]
@@ -437,12 +470,13 @@ def write_psrfits(filename, data, scl, offs, freqs, weights, periods,
             ("NPOL", npol), ("POL_TYPE", pol_type), ("NBIN", nbin),
             ("NCHAN", nchan), ("CHAN_BW", float(obsbw / nchan)),
             ("DM", float(dm)), ("NSBLK", 1)]
-    body = rows.tobytes()
     with open(filename, "wb") as fh:
         fh.write(_header(prim))
         fh.write(_header(ext))
-        fh.write(body)
-        fh.write(b"\0" * (-len(body) % BLOCK))
+        for i in range(nsub):
+            fh.write(meta[i].tobytes())
+            fh.write(data[i])
+        fh.write(b"\0" * (-(nsub * rowbytes) % BLOCK))
     return filename
 
 
