@@ -13,7 +13,8 @@ the bench fit mode (phase+DM, full, scat) and kernel:
            unit = one sub-integration
   dsum  -- the guess-profile pass k_dsum_w; unit = one sub-integration
   xspec -- the cross-spectrum pass k_xspec_w; unit = one sub-integration
-  pass  -- the streaming trust-region evaluation k_pass<true>; unit = one
+  pass  -- the streaming trust-region evaluation k_pass (k_pass<true> in
+           traces recorded before it lost its template parameter); unit = one
            evaluation of one sub-integration (the run's launches process
            nsub x mean_passes_per_fit evaluations per call)
   moments -- k_moments (moments from the stored cross spectrum): every
@@ -28,7 +29,7 @@ import json
 import os
 
 KERNELS = {"xmom": ("k_xmom_g<", ", true>"), "dsum": ("k_dsum_w<", ""),
-           "xspec": ("k_xspec_w", ""), "pass": ("k_pass<true>", ""),
+           "xspec": ("k_xspec_w", ""), "pass": ("k_pass", ""),
            "moments": ("k_moments", ""), "accum": ("k_align", ""), "noise": ("k_noise_w<", "")}
 
 

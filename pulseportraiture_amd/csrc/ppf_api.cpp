@@ -231,10 +231,15 @@ static bool mom16_layout(const FitLayout &L, int nbin) {
     return L.momx || (!L.fused && !ppf::is_pow2(ppf::rfft_len(nbin)));
 }
 
-
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 bool bluestein_plan(int64_t nbin, int64_t n, bool packed, ppf::LongNoiseArgs &a);
+
+// the long-transform plan of the rFFT of real rows of nbin samples (even
+// nbin: two samples per complex point)
+bool long_row_plan(int64_t nbin, ppf::LongNoiseArgs &f) {
+    return bluestein_plan(nbin, (nbin & 1) ? nbin : nbin / 2, !(nbin & 1), f);
+}
 
 // fits at nbin past the LDS transforms (even > 8192, odd > 4095): the rows'
 // rFFTs on the long transforms, then the X-based fit.  With the GetTOAs
@@ -254,14 +259,14 @@ bool grid_gsh(int nbin, int Ns, bool lng) {
 bool long_fit_ok(const ppf_fit_desc *d) {
     ppf::LongNoiseArgs f;
     if (d->guess && ((size_t)d->nbin / 2 + 2) * sizeof(double2) > 150u * 1024u) return false;
-    return !nbin_supported(d->nbin) && d->nbin > 4095 &&
-           bluestein_plan(d->nbin, (d->nbin & 1) ? d->nbin : d->nbin / 2, !(d->nbin & 1), f);
+    return !nbin_supported(d->nbin) && d->nbin > 4095 && long_row_plan(d->nbin, f);
 }
 
 FitLayout fit_layout(const ppf_fit_desc *d) {
     FitLayout L{};
     const size_t nharm = (size_t)d->nbin / 2 + 1;
     const size_t nsub = (size_t)d->nsub, nchan = (size_t)d->nchan;
+    const size_t nmodel = (size_t)(d->nmodel > 0 ? d->nmodel : 1);
     L.cb = d->nchan < 32 ? d->nchan : 32;
     L.nblk = (d->nchan + L.cb - 1) / L.cb;
     L.fused = ppf::xspec_wave_supported(rfft_log2(d->nbin), L.cb) ? 1 : 0;
@@ -279,69 +284,74 @@ FitLayout fit_layout(const ppf_fit_desc *d) {
     if (L.momx) L.xcap = d->nsub;
     L.cbd = d->nchan < 128 ? d->nchan : 128;          // k_dsum channel block
     L.nblkd = (d->nchan + L.cbd - 1) / L.cbd;
+    // regions in the order they are taken, each a multiple of 256 bytes (an
+    // empty one takes none)
     size_t o = 0;
-    L.M = o;     o += align256(sizeof(double2) * (size_t)(d->nmodel > 0 ? d->nmodel : 1) * nchan * nharm);
+    auto take = [&o](size_t bytes) {
+        const size_t at = o;
+        o += align256(bytes);
+        return at;
+    };
+    L.M = take(sizeof(double2) * nmodel * nchan * nharm);
     // tiled slots hold whole tiles of 8 harmonics per channel (1032 at 2048
     // bins); the harmonic-major slots of the same call keep that stride
     L.tiled = (L.momx && ppf::xspec_tiled(rfft_log2(d->nbin))) ? 1 : 0;
     L.xnh = L.tiled ? (int)ppf::xtile_harm((int64_t)nharm) : (int)nharm;
-    L.X = o;     o += align256(sizeof(double2) * (size_t)L.xcap * nchan * (size_t)L.xnh);
-    L.chan = o;  o += align256(sizeof(double) * nsub * nchan * 4);
-    L.stats = o; o += align256(sizeof(double) * nsub * 2 * nchan * 10);
-    L.x0 = o;    o += align256(sizeof(double) * nsub * 8);
-    L.state = o; o += align256(ppf::tr_state_bytes() * nsub);
-    L.partials = o; o += align256(sizeof(double) * nsub * (size_t)ppf::pass_blocks(d->nchan) * 21);
-    L.active = o; o += 256;
-    L.mom = o;   o += align256(sizeof(double2) * nsub * 2 * nchan * (size_t)ppf::kMoments);
-    L.dphi = o;  o += align256(sizeof(double) * nsub * nchan * 2);
-    L.mres = o;  o += align256(sizeof(double) * nsub * 2 * nchan);
-    L.hcen = o;  o += mom16_layout(L, d->nbin) ? align256(sizeof(double) * nsub * 2 * nchan) : 0;
-    L.Mpow = o;  o += align256(sizeof(double) * (size_t)(d->nmodel > 0 ? d->nmodel : 1) * nchan);
-    L.MP = o;    o += align256(sizeof(double) * (size_t)(d->nmodel > 0 ? d->nmodel : 1) * nchan * nharm);
-    L.KC = o;    o += align256(sizeof(int32_t) * (size_t)(d->nmodel > 0 ? d->nmodel : 1) * nchan);
-    L.needx = o; o += align256(nsub);
-    L.xslot = o; o += align256(sizeof(int32_t) * nsub);
-    L.xtile = o; o += L.tiled ? align256(nsub) : 0;
-    L.cls = o;   o += align256(sizeof(int32_t) * nsub);
-    L.rec = o;   o += align256(sizeof(double) * nsub * ppf::kRecN);
-    L.hmlist = o; o += align256(sizeof(int32_t) * nsub);
-    L.nglist = o; o += align256(sizeof(int32_t) * nsub);
-    L.rclist = o; o += align256(sizeof(int32_t) * nsub);
-    L.Bt = o;    o += align256(sizeof(double) * (nharm - 1) / 2 * 16);
+    L.X = take(sizeof(double2) * (size_t)L.xcap * nchan * (size_t)L.xnh);
+    L.chan = take(sizeof(double) * nsub * nchan * 4);
+    L.stats = take(sizeof(double) * nsub * 2 * nchan * 10);
+    L.x0 = take(sizeof(double) * nsub * 8);
+    L.state = take(ppf::tr_state_bytes() * nsub);
+    L.partials = take(sizeof(double) * nsub * (size_t)ppf::pass_blocks(d->nchan) * 21);
+    L.active = take(256);
+    L.mom = take(sizeof(double2) * nsub * 2 * nchan * (size_t)ppf::kMoments);
+    L.dphi = take(sizeof(double) * nsub * nchan * 2);
+    L.mres = take(sizeof(double) * nsub * 2 * nchan);
+    L.hcen = take(mom16_layout(L, d->nbin) ? sizeof(double) * nsub * 2 * nchan : 0);
+    L.Mpow = take(sizeof(double) * nmodel * nchan);
+    L.MP = take(sizeof(double) * nmodel * nchan * nharm);
+    L.KC = take(sizeof(int32_t) * nmodel * nchan);
+    L.needx = take(nsub);
+    L.xslot = take(sizeof(int32_t) * nsub);
+    L.xtile = take(L.tiled ? nsub : 0);
+    L.cls = take(sizeof(int32_t) * nsub);
+    L.rec = take(sizeof(double) * nsub * ppf::kRecN);
+    L.hmlist = take(sizeof(int32_t) * nsub);
+    L.nglist = take(sizeof(int32_t) * nsub);
+    L.rclist = take(sizeof(int32_t) * nsub);
+    L.Bt = take(sizeof(double) * (nharm - 1) / 2 * 16);
     if (d->guess) {
-        L.gP = o; o += align256(sizeof(double) * nsub * (size_t)L.nblkd * (size_t)d->nbin);
-        L.gw = o; o += align256(sizeof(double) * nsub * (size_t)L.nblkd * 2);
-        L.nuref = o; o += align256(sizeof(double) * nsub);
-        L.Msum = o; o += align256(sizeof(double2) * (size_t)(d->nmodel > 0 ? d->nmodel : 1) * nharm);
+        L.gP = take(sizeof(double) * nsub * (size_t)L.nblkd * (size_t)d->nbin);
+        L.gw = take(sizeof(double) * nsub * (size_t)L.nblkd * 2);
+        L.nuref = take(sizeof(double) * nsub);
+        L.Msum = take(sizeof(double2) * nmodel * nharm);
         if (L.fused) {   // guess spectrum fused into k_xspec_w (k_classify: gflag)
             const size_t ng = (size_t)ppf::guess_slots(rfft_log2(d->nbin));
-            L.gpart = o; o += align256(sizeof(double2) * nsub * (size_t)L.nblkx * ng);
-            L.gwx = o;   o += align256(sizeof(double) * nsub * (size_t)L.nblkx * 3);
-            L.gflag = o; o += align256(nsub);
+            L.gpart = take(sizeof(double2) * nsub * (size_t)L.nblkx * ng);
+            L.gwx = take(sizeof(double) * nsub * (size_t)L.nblkx * 3);
+            L.gflag = take(nsub);
         }
     }
     L.lng = long_fit_ok(d) ? 1 : 0;
     if (L.lng) {
         ppf::LongNoiseArgs f;
-        bluestein_plan(d->nbin, (d->nbin & 1) ? d->nbin : d->nbin / 2, !(d->nbin & 1), f);
+        long_row_plan(d->nbin, f);
         const size_t row_b = (size_t)f.M * sizeof(double2);
-        const int64_t rows = (int64_t)(nsub > (size_t)(d->nmodel > 0 ? d->nmodel : 1) ? nsub
-                                       : (size_t)(d->nmodel > 0 ? d->nmodel : 1)) * (int64_t)nchan;
+        const int64_t rows = (int64_t)(nsub > nmodel ? nsub : nmodel) * (int64_t)nchan;
         int64_t rc = (int64_t)((size_t)(256u << 20) / (2 * row_b));
         if (rc < 1) rc = 1;
         L.lrows = rows < rc ? rows : rc;
-        L.spec = o;   o += align256(sizeof(double2) * nsub * nchan * nharm);
+        L.spec = take(sizeof(double2) * nsub * nchan * nharm);
         if (d->guess) {
-            L.gprof = o; o += align256(sizeof(double) * nsub * (size_t)d->nbin);
-            L.gspec = o; o += align256(sizeof(double2) * nsub * nharm);
+            L.gprof = take(sizeof(double) * nsub * (size_t)d->nbin);
+            L.gspec = take(sizeof(double2) * nsub * nharm);
         }
-        L.lchirp = o; o += align256(2 * row_b);
-        L.lA = o;     o += align256((size_t)L.lrows * row_b);
-        L.lY = o;     o += align256((size_t)L.lrows * row_b);
+        L.lchirp = take(2 * row_b);
+        L.lA = take((size_t)L.lrows * row_b);
+        L.lY = take((size_t)L.lrows * row_b);
     }
-    if (d->guess && grid_gsh(d->nbin, d->guess_Ns, L.lng)) {
-        L.gsh = o; o += align256(sizeof(double) * nsub * ((size_t)d->guess_Ns + 8));
-    }
+    if (d->guess && grid_gsh(d->nbin, d->guess_Ns, L.lng))
+        L.gsh = take(sizeof(double) * nsub * ((size_t)d->guess_Ns + 8));
     L.total = o;
     return L;
 }
@@ -351,8 +361,7 @@ FitLayout fit_layout(const ppf_fit_desc *d) {
 int long_rfft_rows(ppf_ctx *ctx, const FitLayout &L, char *ws, int64_t nbin, int64_t nrows, int dtype,
                    const void *in, double2 *out, bool chirp_ready, hipStream_t st) {
     ppf::LongNoiseArgs f;
-    if (!bluestein_plan(nbin, (nbin & 1) ? nbin : nbin / 2, !(nbin & 1), f))
-        return fail(ctx, PPF_EUNSUP, "nbin=%lld", (long long)nbin);
+    if (!long_row_plan(nbin, f)) return fail(ctx, PPF_EUNSUP, "nbin=%lld", (long long)nbin);
     const double2 *T1, *T2, *unused;
     int rc;
     if ((rc = twiddles(ctx, (int)(2 * f.M1), st, &T1, &unused))) return rc;
@@ -397,6 +406,444 @@ int check_fit_desc(ppf_ctx *ctx, const ppf_fit_desc *d) {
     FitLayout L = fit_layout(d);
     if (d->workspace_bytes < L.total)
         return fail(ctx, PPF_ENOMEM, "workspace %zu < %zu bytes", d->workspace_bytes, L.total);
+    return PPF_OK;
+}
+
+// ---- profiling plumbing ----------------------------------------------------
+using EvPair = std::pair<hipEvent_t, hipEvent_t>;
+
+// (start, end) pair i of a pool, created on demand; null, with the error in
+// *e, where an event cannot be created
+EvPair *event_pair(std::vector<EvPair> &v, int i, hipError_t *e) {
+    if ((int)v.size() <= i) {
+        EvPair pr{};
+        if ((*e = hipEventCreate(&pr.first)) != hipSuccess) return nullptr;
+        if ((*e = hipEventCreate(&pr.second)) != hipSuccess) {
+            (void)hipEventDestroy(pr.first);
+            return nullptr;
+        }
+        v.push_back(pr);
+    }
+    return &v[i];
+}
+
+// ms between two recorded events of one stream, once the later one has passed
+int event_ms(ppf_ctx *ctx, hipEvent_t a, hipEvent_t b, double *ms) {
+    hipError_t e = hipEventSynchronize(b);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipEventSynchronize");
+    float t = 0.f;
+    if ((e = hipEventElapsedTime(&t, a, b)) != hipSuccess) return hip_fail(ctx, e, "hipEventElapsedTime");
+    *ms = (double)t;
+    return PPF_OK;
+}
+
+// The ms-history getters' common part: checks the arguments, clamps n to the
+// profiled calls the ring still holds and calls entry(c, slot) for history
+// entry c = 0..n-1 (oldest first, in ring slot `slot`).  Returns n or an error.
+template <class F>
+int for_history(ppf_ctx *ctx, int n, const double *ms, F &&entry) {
+    if (!ctx || !ms || n < 0) return PPF_EINVAL;
+    if (!ctx->prof) return fail(ctx, PPF_EINVAL, "profiling is off");
+    const long avail = ctx->ncalls < ppf_ctx::kRing ? ctx->ncalls : ppf_ctx::kRing;
+    if (n > avail) n = (int)avail;
+    for (int c = 0; c < n; ++c)
+        if (int rc = entry(c, (int)((ctx->ncalls - n + c) % ppf_ctx::kRing))) return rc;
+    return n;
+}
+
+// ---- ppf_fit_batch: what the stages of one call share, then the stages -----
+struct FitCall {
+    ppf_ctx *ctx;
+    const ppf_fit_desc *d;
+    hipStream_t st;
+    FitLayout L;
+    char *ws;
+    const double2 *T, *T2;       // twiddles of nbin (long rows: null, no LDS transform runs)
+    double2 *Mft;                // [nmodel][nchan][nharm] model spectra
+    double *Mpow;
+    int nharm, kc;               // harmonics per row, get_noise_PS cut
+    int slot;                    // profiling ring slot of the call
+    // fused moment pass (k_xmom) only on the wave-FFT shapes; elsewhere the
+    // moments are taken from X (k_moments)
+    bool fused;
+    // the caller expects no streaming fit (C2's pipeline): the launches
+    // whose sub-ints are then few or none stride over k_classify's lists
+    bool bounded;
+    // moment-mode sub-ints (no scattering) on the fused path never need the
+    // cross spectrum in HBM: k_xmom_g re-FFTs their rows; k_classify marks
+    // the others and gives each an X slot
+    uint8_t *needx;
+    int32_t *xslot;
+    uint8_t *xtile;              // null: no tiled slot
+    // fused guess: the sub-ints k_xspec_w streams whose mean-model cutoff
+    // fits its guess harmonics accumulate the guess spectrum there
+    uint8_t *gflag;              // null: no fused guess (then gpart, gwx too)
+    double2 *gpart;
+    double *gwx;
+    // the words behind active: [4], [5] k_tr_init's kind counts, [8]
+    // k_classify's arrival ticket, [9], [10] its list counts
+    unsigned *kinds;
+    int32_t *cls;
+    double *rec;
+
+    template <class U>
+    U *at(size_t off) const { return (U *)(ws + off); }
+    const int32_t *KC() const { return at<const int32_t>(L.KC); }
+    unsigned *counts() const { return kinds + 4; }
+    void mark(int i) const { if (ctx->prof) (void)hipEventRecord(ctx->ring[slot][i], st); }
+    // events around one solver launch (profiling only; where a pair cannot
+    // be created the launch goes untimed)
+    EvPair *solv_begin(int kind) const {
+        hipError_t e;
+        EvPair *pe = ctx->prof ? event_pair(ctx->solv_ev[slot], ctx->nsolv[slot], &e) : nullptr;
+        if (!pe) return nullptr;
+        ctx->solv_kind[slot].resize(ctx->solv_ev[slot].size());
+        ctx->solv_kind[slot][ctx->nsolv[slot]++] = kind;
+        (void)hipEventRecord(pe->first, st);
+        return pe;
+    }
+    void solv_end(EvPair *pe) const { if (pe) (void)hipEventRecord(pe->second, st); }
+
+    int begin();
+    int models(), spectra(), guess();     // stages 0, 1, 2 of ppf_stage_ms_history
+    ppf::SolveArgs solve_args() const;
+    ppf::XmomArgs xmom_args(const ppf::SolveArgs &sa) const;
+    int round(const ppf::SolveArgs &sa, const ppf::XmomArgs &ma, bool any_pass, bool any_mom, bool first);
+    int solve(const ppf::SolveArgs &sa), postfit(const ppf::SolveArgs &sa);   // stage 3
+};
+
+// the call's layout, twiddles and workspace pointers (ctx, d, st are set);
+// opens its profiling slot
+int FitCall::begin() {
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
+    L = fit_layout(d);
+    int rc;
+    if (!L.lng && (rc = twiddles(ctx, d->nbin, st, &T, &T2))) return rc;
+    ws = (char *)d->workspace;
+    Mft = at<double2>(L.M); Mpow = at<double>(L.Mpow);
+    nharm = d->nbin / 2 + 1; kc = noise_kc(nharm, 4);
+    fused = L.fused && !L.momx;
+    bounded = (d->options & PPF_OPT_NO_X) != 0;
+    needx = at<uint8_t>(L.needx); xslot = at<int32_t>(L.xslot);
+    xtile = L.tiled ? at<uint8_t>(L.xtile) : nullptr;
+    if (d->guess && L.fused && ppf::xspec_guess_fused_n(rfft_log2(d->nbin))) {
+        gflag = at<uint8_t>(L.gflag); gpart = at<double2>(L.gpart); gwx = at<double>(L.gwx);
+    }
+    kinds = at<unsigned>(L.active + 16); cls = at<int32_t>(L.cls); rec = at<double>(L.rec);
+    slot = (int)(ctx->ncalls % ppf_ctx::kRing);
+    for (int i = 0; i < 4; ++i) ctx->ran[slot][i] = true;
+    ctx->npass[slot] = ctx->nsolv[slot] = 0;
+    ctx->ran[slot][2] = d->guess != 0;
+    ctx->ran[slot][4] = ctx->ran[slot][5] = false;
+    return PPF_OK;
+}
+
+// stage 0: model spectra, their power and harmonic cutoffs; k_classify
+int FitCall::models() {
+    hipError_t e;
+    if (L.lng) {
+        if (int rc = long_rfft_rows(ctx, L, ws, d->nbin, (int64_t)d->nmodel * d->nchan, PPF_F64, d->model, Mft,
+                                    false, st))
+            return rc;
+    } else {
+        ppf::RfftArgs ra{d->nbin, rfft_log2(d->nbin), PPF_F64, d->model, T, T2, Mft};
+        if ((e = ppf::launch_rfft_rows(ra, (int64_t)d->nmodel * d->nchan, st)) != hipSuccess)
+            return hip_fail(ctx, e, "k_rfft_rows");
+    }
+    if ((e = ppf::launch_model_pow_t(Mft, d->nchan, nharm, d->nmodel, at<double>(L.MP), st)) != hipSuccess)
+        return hip_fail(ctx, e, "k_model_pow_t");
+    if ((e = ppf::launch_model_cut(at<const double>(L.MP), d->nchan, nharm, d->nmodel,
+                                   (d->options & PPF_OPT_NO_HCUT) != 0, at<int32_t>(L.KC), st)) != hipSuccess)
+        return hip_fail(ctx, e, "k_model_cut");
+    if ((e = ppf::launch_model_pow(Mft, d->nchan, nharm, d->nmodel, Mpow, st)) != hipSuccess)
+        return hip_fail(ctx, e, "k_model_pow");
+    if ((e = hipMemsetAsync(kinds, 0, 8 * sizeof(unsigned), st)) != hipSuccess)
+        return hip_fail(ctx, e, "hipMemsetAsync");
+    ppf::ClassifyArgs ca{};
+    ca.nsub = d->nsub; ca.nchan = d->nchan; ca.log10_tau = d->log10_tau;
+    ca.fused = fused ? 1 : 0; ca.xcap = L.xcap;
+    ca.fit_flags = d->fit_flags; ca.init = d->init; ca.freqs = d->freqs; ca.P = d->P;
+    ca.nu_fits = d->nu_fits; ca.mask = d->chan_mask; ca.model_index = d->model_index;
+    ca.KC = KC(); ca.klim = gflag ? 64 * ppf::guess_npl(rfft_log2(d->nbin)) : -1;
+    ca.guess_DM = d->guess ? d->guess_DM : nullptr; ca.guess_ref = d->guess ? d->guess_ref : 0;
+    ca.needx = needx; ca.xslot = xslot; ca.xtile = xtile; ca.gflag = gflag; ca.cls = cls; ca.rec = rec;
+    ca.hm_list = at<int32_t>(L.hmlist); ca.ng_list = at<int32_t>(L.nglist); ca.counts = counts();
+    if ((e = ppf::launch_classify(ca, st)) != hipSuccess) return hip_fail(ctx, e, "k_classify");
+    return PPF_OK;
+}
+
+// stage 1: the spectrum pass (wave, long-row or block FFT): the per-channel
+// terms and the cross spectra of the sub-ints that need them
+int FitCall::spectra() {
+    hipError_t e;
+    ppf::XspecArgs xa{};
+    xa.nsub = d->nsub; xa.nchan = d->nchan; xa.nbin = d->nbin; xa.log2N = rfft_log2(d->nbin);
+    xa.kc = kc; xa.nblk = L.nblkx; xa.cb = L.cbx; xa.dtype = d->data_dtype;
+    // k_xspec_w: channel-block-major (mode 2) when the model spectra
+    // outgrow the L2s, sub-int-major otherwise; k_xmom_g stages its model
+    // row in LDS per workgroup and keeps mode 1 (xmom_args)
+    constexpr long long kOrder2Bytes = 32ll << 20;
+    const long long model_bytes = (long long)d->nchan * (d->nbin / 2 + 1) * 16;
+    const int xcdx = (L.nblkx % 8 == 0) ? 1 : 0;
+    xa.xcd_swizzle = (xcdx && model_bytes > kOrder2Bytes) ? 2 : xcdx;
+    xa.data = d->data; xa.Mft = Mft; xa.model_index = d->model_index; xa.mask = d->chan_mask;
+    xa.errs = d->errs; xa.freqs = d->freqs; xa.P = d->P; xa.T = T; xa.T2 = T2;
+    xa.X = at<double2>(L.X); xa.chan = at<double>(L.chan);
+    xa.Mpow = Mpow; xa.xslot = xslot; xa.xtile = xtile; xa.xnh = L.xnh;
+    xa.gflag = gflag; xa.cls = cls; xa.rec = rec;
+    if (bounded && xtile) {
+        xa.list = at<int32_t>(L.hmlist);
+        xa.nlist = counts() + 1;
+    }
+    if (gflag) {
+        xa.gpart = gpart; xa.gw = gwx; xa.guess_weights = d->guess_weights;
+        xa.guess_DM = d->guess_DM; xa.nu_fits = d->nu_fits; xa.guess_ref = d->guess_ref;
+    }
+    const bool wave = L.fused != 0;
+    xa.needx = (fused || L.momx) ? needx : nullptr;
+    // fused: only k_pass reads X, and only below its channels' cutoffs;
+    // momx: k_moments reads it below the same cutoffs
+    // block-FFT path: only k_xspec_wm (the smooth non-power-of-two lengths)
+    // uses it, writing X below the same cutoffs its readers stop at
+    xa.KC = (fused || L.momx || !wave) ? KC() : nullptr;
+    if (wave) {
+        // (nothing to do when the caller has ruled out X: every sub-int is
+        // fitted from k_xmom_g's moments)
+        if (!(fused && L.xcap == 0) && (e = ppf::launch_xspec_wave(xa, st)) != hipSuccess)
+            return hip_fail(ctx, e, "k_xspec_w");
+    } else if (L.lng) {
+        double2 *spec = at<double2>(L.spec);
+        if (int rc = long_rfft_rows(ctx, L, ws, d->nbin, (int64_t)d->nsub * d->nchan, d->data_dtype, d->data,
+                                    spec, true, st))
+            return rc;
+        xa.spec = spec;
+        if ((e = ppf::launch_xspec_spec(xa, st)) != hipSuccess) return hip_fail(ctx, e, "k_xspec_spec");
+    } else {
+        if ((e = ppf::launch_xspec(xa, st)) != hipSuccess) return hip_fail(ctx, e, "k_xspec");
+    }
+    return PPF_OK;
+}
+
+// stage 2: the GetTOAs guess.  Guess profile: time-domain dedispersion
+// (k_dsum), then FFTFIT against the mean model (k_guess)
+int FitCall::guess() {
+    hipError_t e;
+    int rc;
+    ppf::DsumArgs da{};
+    da.nsub = d->nsub; da.nchan = d->nchan; da.nbin = d->nbin; da.dtype = d->data_dtype;
+    da.cbd = L.cbd; da.nblkd = L.nblkd; da.data = d->data; da.mask = d->chan_mask;
+    da.freqs = d->freqs; da.P = d->P; da.guess_DM = d->guess_DM; da.guess_weights = d->guess_weights;
+    da.guess_ref = d->guess_ref; da.nu_fits = d->nu_fits;
+    da.gP = at<double>(L.gP); da.gw = at<double>(L.gw); da.nuref = at<double>(L.nuref);
+    da.gflag = gflag;
+    if (bounded && gflag) {
+        da.list = at<int32_t>(L.nglist);
+        da.nlist = counts() + 2;
+    }
+    mark(7);
+    if ((e = ppf::launch_dsum(da, st)) != hipSuccess) return hip_fail(ctx, e, "k_dsum");
+    mark(8);
+    ctx->ran[slot][5] = true;
+    double2 *msum = at<double2>(L.Msum);
+    if ((e = ppf::launch_model_sum(Mft, d->nchan, nharm, d->nmodel, msum, st)) != hipSuccess)
+        return hip_fail(ctx, e, "k_model_sum");
+    ppf::GuessArgs ga{};
+    ga.nsub = d->nsub; ga.nchan = d->nchan; ga.nbin = d->nbin; ga.log2N = rfft_log2(d->nbin);
+    ga.kc = kc; ga.nblkd = L.nblkd; ga.Ns = d->guess_Ns; ga.mask = d->chan_mask; ga.guess_ref = d->guess_ref;
+    ga.freqs = d->freqs; ga.P = d->P; ga.guess_DM = d->guess_DM; ga.guess_tau = d->guess_tau;
+    ga.nu_fits = d->nu_fits; ga.gP = da.gP; ga.gw = da.gw; ga.T = T; ga.T2 = T2;
+    ga.KC = KC(); ga.x0 = at<double>(L.x0); ga.Msum = msum; ga.Mft = Mft; ga.model_index = d->model_index;
+    ga.gflag = gflag; ga.gpart = gpart; ga.gwx = gwx; ga.nblk = L.nblkx;
+    if (L.lng) {
+        // the profiles' rFFTs on the long transforms (same plan as the rows)
+        double *prof = at<double>(L.gprof);
+        double2 *gspec = at<double2>(L.gspec);
+        if ((e = ppf::launch_gsum(d->nsub, L.nblkd, d->nbin, da.gP, prof, st)) != hipSuccess)
+            return hip_fail(ctx, e, "k_gsum");
+        if ((rc = long_rfft_rows(ctx, L, ws, d->nbin, d->nsub, PPF_F64, prof, gspec, true, st))) return rc;
+        ga.gspec = gspec;
+    }
+    if (grid_gsh(d->nbin, ga.Ns, L.lng)) ga.gsh = at<double>(L.gsh);
+    ppf::CzPlan cz{};
+    if (cz_plan(ga.Ns, d->nbin / 2 + 1, cz)) {
+        if ((rc = cz_tables(ctx, cz, st, &ga.czB, &ga.czT))) return rc;
+        ga.czP = cz.P; ga.czJ = cz.J; ga.czQ = cz.Q; ga.czK = cz.K;
+    }
+    if ((e = ppf::launch_guess(ga, st)) != hipSuccess) return hip_fail(ctx, e, "k_guess");
+    return PPF_OK;
+}
+
+// the solver kernels' argument block (k_tr_init .. k_postfit)
+ppf::SolveArgs FitCall::solve_args() const {
+    ppf::SolveArgs sa{};
+    sa.nsub = d->nsub; sa.nchan = d->nchan; sa.nbin = d->nbin;
+    sa.X = at<double2>(L.X); sa.Mft = Mft; sa.model_index = d->model_index; sa.chan = at<double>(L.chan);
+    sa.MP = at<const double>(L.MP); sa.KC = KC();
+    sa.freqs = d->freqs; sa.P = d->P; sa.mask = d->chan_mask; sa.init = d->init;
+    sa.fit_flags = d->fit_flags; sa.nu_fits = d->nu_fits; sa.nu_outs = d->nu_outs; sa.bounds = d->bounds;
+    sa.log10_tau = d->log10_tau; sa.option = d->option; sa.is_toa = d->is_toa; sa.mode = d->mode;
+    sa.max_iter = d->max_iter; sa.guess = d->guess; sa.x0 = at<double>(L.x0);
+    sa.newton = (d->options & PPF_OPT_SCIPY_TR) ? 0 : 1;
+    sa.stats = at<double>(L.stats); sa.results = d->results; sa.scales = d->scales;
+    sa.scale_errs = d->scale_errs; sa.channel_snrs = d->channel_snrs; sa.covariance = d->covariance;
+    sa.state = at<ppf::TRState>(L.state); sa.partials = at<double>(L.partials);
+    sa.active = at<unsigned>(L.active);
+    sa.rc_count = sa.active + 1;             // reset together with active
+    sa.rc_list = at<int32_t>(L.rclist); sa.kinds = kinds; sa.rec = rec;
+    sa.mom = at<double2>(L.mom); sa.dphi = at<double>(L.dphi); sa.mres = at<double>(L.mres);
+    // 16 moments about each wave's band centre (mom16_layout)
+    const bool m16 = mom16_layout(L, d->nbin);
+    sa.mom16 = m16;
+    sa.hcen = m16 ? at<double>(L.hcen) : nullptr;
+    sa.xslot = xslot; sa.xtile = xtile; sa.xnh = L.xnh;
+    return sa;
+}
+
+// the fused moment pass's argument block (k_xmom_g: its model row staged in
+// LDS per workgroup, so sub-int-major order whatever the model size)
+ppf::XmomArgs FitCall::xmom_args(const ppf::SolveArgs &sa) const {
+    ppf::XmomArgs ma{};
+    ma.nsub = d->nsub; ma.nchan = d->nchan; ma.nbin = d->nbin; ma.log2N = rfft_log2(d->nbin);
+    ma.nblk = L.nblk; ma.cb = L.cb; ma.dtype = d->data_dtype; ma.xcd_swizzle = (L.nblk % 8 == 0) ? 1 : 0;
+    ma.data = d->data; ma.Mft = Mft; ma.model_index = d->model_index; ma.mask = d->chan_mask;
+    ma.chan = at<double>(L.chan); ma.dphi = sa.dphi; ma.T = T; ma.T2 = T2; ma.state = sa.state;
+    ma.mom = (double *)sa.mom; ma.Bt = at<const double>(L.Bt);
+    ma.kc = kc; ma.errs = d->errs; ma.Mpow = Mpow; ma.mres = sa.mres; ma.nmodel = d->nmodel;
+    ma.rc_count = sa.rc_count; ma.rc_list = sa.rc_list; ma.KC = KC();
+    return ma;
+}
+
+// re-centring passes: usually few sub-ints, so 8-channel blocks (4x the
+// workgroups, a quarter of the rounds each) keep more CUs busy; a channel's
+// moments do not depend on its block
+ppf::XmomArgs recentre_args(ppf::XmomArgs mr) {
+    if (mr.cb > 8) {
+        mr.cb = 8;
+        mr.nblk = (mr.nchan + 7) / 8;
+        mr.xcd_swizzle = (mr.nblk % 8 == 0) ? 1 : 0;
+    }
+    return mr;
+}
+
+// One round of the iteration loop: for the streaming fits (any_pass) k_pass
+// and k_tr_step, for the moment fits (any_mom) the (re)centring moment pass
+// and k_tr_mom.  first: the call's first round, whose moment pass is the
+// full one.
+int FitCall::round(const ppf::SolveArgs &sa, const ppf::XmomArgs &ma, bool any_pass, bool any_mom, bool first) {
+    hipError_t e;
+    if (any_pass) {
+        EvPair *pe = nullptr;
+        if (ctx->prof) {
+            if (!(pe = event_pair(ctx->pass_ev[slot], ctx->npass[slot], &e)))
+                return hip_fail(ctx, e, "hipEventCreate");
+            ++ctx->npass[slot];
+            (void)hipEventRecord(pe->first, st);
+        }
+        if ((e = ppf::launch_pass(sa, st)) != hipSuccess) return hip_fail(ctx, e, "k_pass");
+        if (pe) (void)hipEventRecord(pe->second, st);
+    }
+    if (any_mom) {
+        if (first) mark(5);
+        if (!fused) e = ppf::launch_moments(sa, st);
+        else e = first ? ppf::launch_xmom(ma, true, st) : ppf::launch_xmom(recentre_args(ma), false, st);
+        if (e != hipSuccess) return hip_fail(ctx, e, fused ? "k_xmom" : "k_moments");
+        if (first) {
+            mark(6);
+            ctx->ran[slot][4] = true;
+        }
+    }
+    if ((e = hipMemsetAsync(sa.active, 0, 2 * sizeof(unsigned), st)) != hipSuccess)
+        return hip_fail(ctx, e, "hipMemsetAsync");
+    if (any_pass) {
+        EvPair *pe = solv_begin(1);
+        if ((e = ppf::launch_tr_step(sa, st)) != hipSuccess) return hip_fail(ctx, e, "k_tr_step");
+        solv_end(pe);
+    }
+    if (any_mom) {
+        EvPair *pe = solv_begin(0);
+        if ((e = ppf::launch_tr_mom(sa, st)) != hipSuccess) return hip_fail(ctx, e, "k_tr_mom");
+        solv_end(pe);
+    }
+    return PPF_OK;
+}
+
+// stage 3: k_tr_init and the trust-region iterations
+int FitCall::solve(const ppf::SolveArgs &sa) {
+    hipError_t e;
+    int rc;
+    if (!ctx->host_active && (e = hipHostMalloc((void **)&ctx->host_active, 4 * sizeof(unsigned))) != hipSuccess)
+        return hip_fail(ctx, e, "hipHostMalloc");
+    if ((e = ppf::launch_tr_init(sa, st)) != hipSuccess) return hip_fail(ctx, e, "k_tr_init");
+    // how many fits iterate on the moments and how many on streaming passes:
+    // the iteration loop launches only the kernels some fit needs.  Where
+    // PPF_OPT_NO_X took effect (fit_layout: the fused path without moments
+    // from X, xcap == 0) no X slot exists, a sub-int that would stream has
+    // ended with PPF_ST_NOSPACE in k_tr_init and every other fit is a
+    // moment fit, so the answer is known without the read-back and its
+    // stream synchronisation (round 6: one host round trip less per call, a
+    // few percent of a ppalign iteration); the moment kernels of a batch
+    // with nothing left to fit exit at once.  Everywhere else (block-FFT and
+    // long rows, moments from X) the option reserves nothing less and every
+    // streaming sub-int holds a valid slot, so the counts decide.  Without
+    // the option they are read here.  With it (the C2 pipeline: moments from
+    // X at 2048 bins) the caller expects no streaming fit, and the counts
+    // ride along with the first read-back of the iteration loop instead
+    // (kinds_late): no round trip of their own, and a streaming sub-int that
+    // is there after all gets its k_pass from the second group on -- a
+    // sub-int's iterations do not depend on the round they start in
+    const bool spin = (d->options & PPF_OPT_SPIN_WAIT) != 0;
+    const bool no_stream = L.fused && L.xcap == 0;
+    bool kinds_late = !no_stream && bounded;
+    bool any_mom = true, any_pass = false;
+    if (!no_stream && !kinds_late) {
+        if ((rc = read_back(ctx, ctx->host_active + 1, sa.kinds, 2, st, spin))) return rc;
+        any_mom = ctx->host_active[1] != 0;
+        any_pass = ctx->host_active[2] != 0;
+    }
+    const ppf::XmomArgs ma = xmom_args(sa);
+    if (fused && (e = ppf::launch_btab(d->nbin / 2, at<double>(L.Bt), st)) != hipSuccess)
+        return hip_fail(ctx, e, "k_btab");
+    // trust-region iterations.  Scattering fits: each iteration = one
+    // streaming pass (k_pass) + one step (k_tr_step).  Other fits: k_moments
+    // (re)centres the moment sets of the sub-ints that asked, k_tr_mom runs
+    // iterations until the fit stops or leaves the expansion radius.  Groups
+    // of rounds are queued without host synchronisation; the count of
+    // sub-ints still needing work is read back between groups.
+    const int maxiter = d->max_iter > 0 ? d->max_iter : 200 * 5;
+    int iter = 0;
+    // Moment-only batches read the counter after the first round: most
+    // phase+DM fits finish inside it (C2: 1.0 data passes per fit), so the
+    // empty re-centring launches that a longer first group would queue
+    // are not worth the one synchronisation they save.
+    for (int group = any_pass ? 3 : 1; any_mom || any_pass; group = 2) {
+        for (int g = 0; g < group; ++g)
+            if ((rc = round(sa, ma, any_pass, any_mom, iter == 0 && g == 0))) return rc;
+        iter += group;
+        // (the same stream, in order: the counts have landed when the
+        // read-back behind them has)
+        if (kinds_late && (e = hipMemcpyAsync(ctx->host_active + 1, sa.kinds, 2 * sizeof(unsigned),
+                                              hipMemcpyDeviceToHost, st)) != hipSuccess)
+            return hip_fail(ctx, e, "hipMemcpyAsync");
+        if ((rc = read_back(ctx, ctx->host_active, sa.active, 1, st, spin))) return rc;
+        if (kinds_late) {
+            kinds_late = false;
+            if (ctx->host_active[2] != 0) {
+                any_pass = true;      // fits still in PH_INIT: not counted in active yet
+                continue;
+            }
+        }
+        if (*ctx->host_active == 0 || iter > maxiter + 2) break;
+    }
+    return PPF_OK;
+}
+
+// stage 3's end: the output transform, covariances, scales and chi2
+int FitCall::postfit(const ppf::SolveArgs &sa) {
+    EvPair *pe = solv_begin(2);
+    const hipError_t e = ppf::launch_postfit(sa, st);
+    if (e != hipSuccess) return hip_fail(ctx, e, "k_postfit");
+    solv_end(pe);
     return PPF_OK;
 }
 
@@ -458,92 +905,55 @@ int ppf_set_profiling(ppf_ctx *ctx, int enable) {
 }
 
 int ppf_stage_ms_history(ppf_ctx *ctx, int n, double *ms) {
-    if (!ctx || !ms || n < 0) return PPF_EINVAL;
-    if (!ctx->prof) return fail(ctx, PPF_EINVAL, "profiling is off");
-    long avail = ctx->ncalls < ppf_ctx::kRing ? ctx->ncalls : ppf_ctx::kRing;
-    if (n > avail) n = (int)avail;
-    for (int c = 0; c < n; ++c) {
-        int slot = (int)((ctx->ncalls - n + c) % ppf_ctx::kRing);
-        hipError_t e = hipEventSynchronize(ctx->ring[slot][4]);
-        if (e != hipSuccess) return hip_fail(ctx, e, "hipEventSynchronize");
+    return for_history(ctx, n, ms, [&](int c, int slot) -> int {
         for (int i = 0; i < 4; ++i) {
-            float t = 0.f;
-            if (ctx->ran[slot][i]) {
-                e = hipEventElapsedTime(&t, ctx->ring[slot][i], ctx->ring[slot][i + 1]);
-                if (e != hipSuccess) return hip_fail(ctx, e, "hipEventElapsedTime");
-            }
-            ms[c * 4 + i] = (double)t;
+            ms[c * 4 + i] = 0.0;
+            if (!ctx->ran[slot][i]) continue;
+            if (int rc = event_ms(ctx, ctx->ring[slot][i], ctx->ring[slot][i + 1], &ms[c * 4 + i])) return rc;
         }
-    }
-    return n;
+        return PPF_OK;
+    });
 }
 
 int ppf_kernel_ms_history(ppf_ctx *ctx, int n, double *ms) {
-    if (!ctx || !ms || n < 0) return PPF_EINVAL;
-    if (!ctx->prof) return fail(ctx, PPF_EINVAL, "profiling is off");
-    long avail = ctx->ncalls < ppf_ctx::kRing ? ctx->ncalls : ppf_ctx::kRing;
-    if (n > avail) n = (int)avail;
-    for (int c = 0; c < n; ++c) {
-        int slot = (int)((ctx->ncalls - n + c) % ppf_ctx::kRing);
-        hipError_t e = hipEventSynchronize(ctx->ring[slot][4]);
-        if (e != hipSuccess) return hip_fail(ctx, e, "hipEventSynchronize");
+    return for_history(ctx, n, ms, [&](int c, int slot) -> int {
         for (int i = 0; i < 2; ++i) {
-            float t = 0.f;
-            if (ctx->ran[slot][4 + i]) {
-                e = hipEventElapsedTime(&t, ctx->ring[slot][5 + 2 * i], ctx->ring[slot][6 + 2 * i]);
-                if (e != hipSuccess) return hip_fail(ctx, e, "hipEventElapsedTime");
-            }
-            ms[c * 2 + i] = (double)t;
+            ms[c * 2 + i] = 0.0;
+            if (!ctx->ran[slot][4 + i]) continue;
+            if (int rc = event_ms(ctx, ctx->ring[slot][5 + 2 * i], ctx->ring[slot][6 + 2 * i], &ms[c * 2 + i]))
+                return rc;
         }
-    }
-    return n;
+        return PPF_OK;
+    });
 }
 
 int ppf_pass_ms_history(ppf_ctx *ctx, int n, double *ms) {
-    if (!ctx || !ms || n < 0) return PPF_EINVAL;
-    if (!ctx->prof) return fail(ctx, PPF_EINVAL, "profiling is off");
-    long avail = ctx->ncalls < ppf_ctx::kRing ? ctx->ncalls : ppf_ctx::kRing;
-    if (n > avail) n = (int)avail;
-    for (int c = 0; c < n; ++c) {
-        int slot = (int)((ctx->ncalls - n + c) % ppf_ctx::kRing);
-        double tot = 0.0;
+    return for_history(ctx, n, ms, [&](int c, int slot) -> int {
+        double tot = 0.0, t;
         for (int i = 0; i < ctx->npass[slot]; ++i) {
-            const auto &pr = ctx->pass_ev[slot][i];
-            hipError_t e = hipEventSynchronize(pr.second);
-            if (e != hipSuccess) return hip_fail(ctx, e, "hipEventSynchronize");
-            float t = 0.f;
-            e = hipEventElapsedTime(&t, pr.first, pr.second);
-            if (e != hipSuccess) return hip_fail(ctx, e, "hipEventElapsedTime");
-            tot += (double)t;
+            const EvPair &pr = ctx->pass_ev[slot][i];
+            if (int rc = event_ms(ctx, pr.first, pr.second, &t)) return rc;
+            tot += t;
         }
         ms[c * 2 + 0] = tot;
         ms[c * 2 + 1] = (double)ctx->npass[slot];
-    }
-    return n;
+        return PPF_OK;
+    });
 }
 
 int ppf_solver_ms_history(ppf_ctx *ctx, int n, double *ms) {
-    if (!ctx || !ms || n < 0) return PPF_EINVAL;
-    if (!ctx->prof) return fail(ctx, PPF_EINVAL, "profiling is off");
-    long avail = ctx->ncalls < ppf_ctx::kRing ? ctx->ncalls : ppf_ctx::kRing;
-    if (n > avail) n = (int)avail;
-    for (int c = 0; c < n; ++c) {
-        int slot = (int)((ctx->ncalls - n + c) % ppf_ctx::kRing);
-        double *o = ms + c * 6;
+    return for_history(ctx, n, ms, [&](int c, int slot) -> int {
+        double *o = ms + c * 6, t;
         for (int i = 0; i < 6; ++i) o[i] = 0.0;
         for (int i = 0; i < ctx->nsolv[slot]; ++i) {
-            const auto &pr = ctx->solv_ev[slot][i];
-            hipError_t e = hipEventSynchronize(pr.second);
-            if (e != hipSuccess) return hip_fail(ctx, e, "hipEventSynchronize");
-            float t = 0.f;
-            e = hipEventElapsedTime(&t, pr.first, pr.second);
-            if (e != hipSuccess) return hip_fail(ctx, e, "hipEventElapsedTime");
+            const EvPair &pr = ctx->solv_ev[slot][i];
+            if (int rc = event_ms(ctx, pr.first, pr.second, &t)) return rc;
             const int k = ctx->solv_kind[slot][i];
-            o[2 * k] += (double)t;
+            o[2 * k] += t;
             o[2 * k + 1] += 1.0;
         }
-    }
-    return n;
+        return PPF_OK;
+    });
 }
 
 int ppf_last_stage_ms(ppf_ctx *ctx, double *ms4) {
@@ -572,390 +982,20 @@ int ppf_fit_batch(ppf_ctx *ctx, const ppf_fit_desc *d, void *stream) {
     if (!ctx) return PPF_EINVAL;
     int rc = check_fit_desc(ctx, d);
     if (rc) return rc;
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
-    hipStream_t st = (hipStream_t)stream;
-    const FitLayout L = fit_layout(d);
-    // (long rows: no LDS transform runs, so no twiddle table of nbin)
-    const double2 *T = nullptr, *T2 = nullptr;
-    if (!L.lng && (rc = twiddles(ctx, d->nbin, st, &T, &T2))) return rc;
-    char *ws = (char *)d->workspace;
-    double2 *Mft = (double2 *)(ws + L.M);
-    const int nharm = d->nbin / 2 + 1;
-    const int kc = noise_kc(nharm, 4);
-
-    const int slot = (int)(ctx->ncalls % ppf_ctx::kRing);
-    auto mark = [&](int i) {
-        if (ctx->prof) (void)hipEventRecord(ctx->ring[slot][i], st);
-    };
-    for (int i = 0; i < 4; ++i) ctx->ran[slot][i] = true;
-    ctx->npass[slot] = 0;
-    ctx->nsolv[slot] = 0;
-    // events around one solver launch (profiling only)
-    auto solv_begin = [&](int kind) -> std::pair<hipEvent_t, hipEvent_t> * {
-        if (!ctx->prof) return nullptr;
-        auto &v = ctx->solv_ev[slot];
-        auto &kv = ctx->solv_kind[slot];
-        if ((int)v.size() <= ctx->nsolv[slot]) {
-            std::pair<hipEvent_t, hipEvent_t> pr{};
-            if (hipEventCreate(&pr.first) != hipSuccess) return nullptr;
-            if (hipEventCreate(&pr.second) != hipSuccess) {
-                (void)hipEventDestroy(pr.first);
-                return nullptr;
-            }
-            v.push_back(pr);
-            kv.push_back(0);
-        }
-        kv[ctx->nsolv[slot]] = kind;
-        auto *pe = &v[ctx->nsolv[slot]++];
-        (void)hipEventRecord(pe->first, st);
-        return pe;
-    };
-    auto solv_end = [&](std::pair<hipEvent_t, hipEvent_t> *pe) {
-        if (pe) (void)hipEventRecord(pe->second, st);
-    };
-    ctx->ran[slot][2] = d->guess != 0;
-    ctx->ran[slot][4] = ctx->ran[slot][5] = false;
-    mark(0);
-    if (L.lng) {
-        if ((rc = long_rfft_rows(ctx, L, ws, d->nbin, (int64_t)d->nmodel * d->nchan, PPF_F64, d->model, Mft,
-                                 false, st)))
-            return rc;
-    } else {
-        ppf::RfftArgs ra{d->nbin, rfft_log2(d->nbin), PPF_F64, d->model, T, T2, Mft};
-        if ((e = ppf::launch_rfft_rows(ra, (int64_t)d->nmodel * d->nchan, st)) != hipSuccess)
-            return hip_fail(ctx, e, "k_rfft_rows");
-    }
-    double *Mpow = (double *)(ws + L.Mpow);
-    if ((e = ppf::launch_model_pow_t(Mft, d->nchan, nharm, d->nmodel, (double *)(ws + L.MP), st)) !=
-        hipSuccess)
-        return hip_fail(ctx, e, "k_model_pow_t");
-    if ((e = ppf::launch_model_cut((const double *)(ws + L.MP), d->nchan, nharm, d->nmodel,
-                                   (d->options & PPF_OPT_NO_HCUT) != 0, (int32_t *)(ws + L.KC),
-                                   st)) != hipSuccess)
-        return hip_fail(ctx, e, "k_model_cut");
-    if ((e = ppf::launch_model_pow(Mft, d->nchan, nharm, d->nmodel, Mpow, st)) != hipSuccess)
-        return hip_fail(ctx, e, "k_model_pow");
-    // moment-mode sub-ints (no scattering) on the fused path never need the
-    // cross spectrum in HBM: k_xmom_g re-FFTs their rows; k_classify marks
-    // the others and gives each an X slot
-    const int use_moments = 1;
-    uint8_t *needx = (uint8_t *)(ws + L.needx);
-    int32_t *xslot = (int32_t *)(ws + L.xslot);
-    uint8_t *xtile = L.tiled ? (uint8_t *)(ws + L.xtile) : nullptr;
-    // fused guess: the sub-ints k_xspec_w streams whose mean-model cutoff
-    // fits its guess harmonics accumulate the guess spectrum there
-    uint8_t *gflag = nullptr;
-    if (d->guess && L.fused && ppf::xspec_guess_fused_n(rfft_log2(d->nbin))) gflag = (uint8_t *)(ws + L.gflag);
-    // the words behind active: [4], [5] k_tr_init's kind counts, [8]
-    // k_classify's arrival ticket, [9], [10] its list counts
-    unsigned *kinds = (unsigned *)(ws + L.active + 16);
-    if ((e = hipMemsetAsync(kinds, 0, 8 * sizeof(unsigned), st)) != hipSuccess)
-        return hip_fail(ctx, e, "hipMemsetAsync");
-    ppf::ClassifyArgs ca{};
-    ca.nsub = d->nsub; ca.nchan = d->nchan; ca.log10_tau = d->log10_tau;
-    ca.fused = (L.fused && !L.momx) ? 1 : 0; ca.xcap = L.xcap;
-    ca.fit_flags = d->fit_flags; ca.init = d->init; ca.freqs = d->freqs; ca.P = d->P;
-    ca.nu_fits = d->nu_fits; ca.mask = d->chan_mask; ca.model_index = d->model_index;
-    ca.KC = (const int32_t *)(ws + L.KC);
-    ca.klim = gflag ? 64 * ppf::guess_npl(rfft_log2(d->nbin)) : -1;
-    ca.guess_DM = d->guess ? d->guess_DM : nullptr; ca.guess_ref = d->guess ? d->guess_ref : 0;
-    ca.needx = needx; ca.xslot = xslot; ca.xtile = xtile; ca.gflag = gflag;
-    ca.cls = (int32_t *)(ws + L.cls); ca.rec = (double *)(ws + L.rec);
-    ca.hm_list = (int32_t *)(ws + L.hmlist); ca.ng_list = (int32_t *)(ws + L.nglist);
-    ca.counts = kinds + 4;
-    if ((e = ppf::launch_classify(ca, st)) != hipSuccess) return hip_fail(ctx, e, "k_classify");
-    mark(1);
-
-    ppf::XspecArgs xa{};
-    xa.nsub = d->nsub; xa.nchan = d->nchan; xa.nbin = d->nbin; xa.log2N = rfft_log2(d->nbin);
-    xa.kc = kc; xa.nblk = L.nblkx; xa.cb = L.cbx; xa.dtype = d->data_dtype;
-    // k_xspec_w: channel-block-major (mode 2) when the model spectra
-    // outgrow the L2s, sub-int-major otherwise; k_xmom_g stages its model
-    // row in LDS per workgroup and keeps mode 1
-    constexpr long long kOrder2Bytes = 32ll << 20;
-    const long long model_bytes = (long long)d->nchan * (d->nbin / 2 + 1) * 16;
-    const int xcd1 = (L.nblk % 8 == 0) ? 1 : 0;
-    const int xcdx = (L.nblkx % 8 == 0) ? 1 : 0;
-    xa.xcd_swizzle = (xcdx && model_bytes > kOrder2Bytes) ? 2 : xcdx;
-    xa.data = d->data; xa.Mft = Mft; xa.model_index = d->model_index; xa.mask = d->chan_mask;
-    xa.errs = d->errs; xa.freqs = d->freqs; xa.P = d->P; xa.T = T; xa.T2 = T2;
-    xa.X = (double2 *)(ws + L.X); xa.chan = (double *)(ws + L.chan);
-    xa.Mpow = Mpow;
-    xa.xslot = xslot;
-    xa.xtile = xtile;
-    xa.xnh = L.xnh;
-    xa.gflag = gflag;
-    xa.cls = ca.cls;
-    xa.rec = ca.rec;
-    // the caller expects no streaming fit (C2's pipeline): the launches
-    // whose sub-ints are then few or none stride over k_classify's lists
-    const bool bounded = (d->options & PPF_OPT_NO_X) != 0;
-    if (bounded && xtile) {
-        xa.list = ca.hm_list;
-        xa.nlist = ca.counts + 1;
-    }
-    if (gflag) {
-        xa.gpart = (double2 *)(ws + L.gpart);
-        xa.gw = (double *)(ws + L.gwx);
-        xa.guess_weights = d->guess_weights;
-        xa.guess_DM = d->guess_DM;
-        xa.nu_fits = d->nu_fits;
-        xa.guess_ref = d->guess_ref;
-    }
-    const bool wave = L.fused != 0;
-    // fused moment pass (k_xmom) only on the wave-FFT shapes; elsewhere the
-    // moments are taken from X (k_moments)
-    const bool fused = wave && use_moments && !L.momx;
-    xa.needx = (fused || L.momx) ? needx : nullptr;
-    // fused: only k_pass reads X, and only below its channels' cutoffs;
-    // momx: k_moments reads it below the same cutoffs
-    // block-FFT path: only k_xspec_wm (the smooth non-power-of-two lengths)
-    // uses it, writing X below the same cutoffs its readers stop at
-    xa.KC = (fused || L.momx || !wave) ? (const int32_t *)(ws + L.KC) : nullptr;
-    if (wave) {
-        // (nothing to do when the caller has ruled out X: every sub-int is
-        // fitted from k_xmom_g's moments)
-        if (!(fused && L.xcap == 0) &&
-            (e = ppf::launch_xspec_wave(xa, st)) != hipSuccess)
-            return hip_fail(ctx, e, "k_xspec_w");
-    } else if (L.lng) {
-        double2 *spec = (double2 *)(ws + L.spec);
-        if ((rc = long_rfft_rows(ctx, L, ws, d->nbin, (int64_t)d->nsub * d->nchan, d->data_dtype, d->data, spec,
-                                 true, st)))
-            return rc;
-        xa.spec = spec;
-        if ((e = ppf::launch_xspec_spec(xa, st)) != hipSuccess) return hip_fail(ctx, e, "k_xspec_spec");
-    } else {
-        if ((e = ppf::launch_xspec(xa, st)) != hipSuccess) return hip_fail(ctx, e, "k_xspec");
-    }
-    mark(2);
-
-    if (d->guess) {
-        // guess profile: time-domain dedispersion (k_dsum), then FFTFIT
-        // against the mean model (k_guess)
-        ppf::DsumArgs da{};
-        da.nsub = d->nsub; da.nchan = d->nchan; da.nbin = d->nbin; da.dtype = d->data_dtype;
-        da.cbd = L.cbd; da.nblkd = L.nblkd; da.data = d->data; da.mask = d->chan_mask;
-        da.freqs = d->freqs; da.P = d->P; da.guess_DM = d->guess_DM;
-        da.guess_weights = d->guess_weights;
-        da.guess_ref = d->guess_ref; da.nu_fits = d->nu_fits;
-        da.gP = (double *)(ws + L.gP); da.gw = (double *)(ws + L.gw);
-        da.nuref = (double *)(ws + L.nuref);
-        da.gflag = gflag;
-        if (bounded && gflag) {
-            da.list = ca.ng_list;
-            da.nlist = ca.counts + 2;
-        }
-        mark(7);
-        if ((e = ppf::launch_dsum(da, st)) != hipSuccess) return hip_fail(ctx, e, "k_dsum");
-        mark(8);
-        ctx->ran[slot][5] = true;
-        double2 *msum = (double2 *)(ws + L.Msum);
-        if ((e = ppf::launch_model_sum(Mft, d->nchan, nharm, d->nmodel, msum, st)) != hipSuccess)
-            return hip_fail(ctx, e, "k_model_sum");
-        ppf::GuessArgs ga{};
-        ga.nsub = d->nsub; ga.nchan = d->nchan; ga.nbin = d->nbin; ga.log2N = rfft_log2(d->nbin);
-        ga.kc = kc; ga.nblkd = L.nblkd; ga.Ns = d->guess_Ns; ga.mask = d->chan_mask;
-        ga.guess_ref = d->guess_ref;
-        ga.freqs = d->freqs; ga.P = d->P; ga.guess_DM = d->guess_DM; ga.guess_tau = d->guess_tau;
-        ga.nu_fits = d->nu_fits; ga.gP = da.gP; ga.gw = da.gw; ga.T = T; ga.T2 = T2;
-        ga.KC = (const int32_t *)(ws + L.KC);
-        ga.x0 = (double *)(ws + L.x0); ga.Msum = msum; ga.Mft = Mft;
-        ga.model_index = d->model_index;
-        ga.gflag = gflag;
-        ga.gpart = xa.gpart;
-        ga.gwx = xa.gw;
-        ga.nblk = L.nblkx;
-        if (L.lng) {
-            // the profiles' rFFTs on the long transforms (same plan as the rows)
-            double *prof = (double *)(ws + L.gprof);
-            double2 *gspec = (double2 *)(ws + L.gspec);
-            if ((e = ppf::launch_gsum(d->nsub, L.nblkd, d->nbin, da.gP, prof, st)) != hipSuccess)
-                return hip_fail(ctx, e, "k_gsum");
-            if ((rc = long_rfft_rows(ctx, L, ws, d->nbin, d->nsub, PPF_F64, prof, gspec, true, st))) return rc;
-            ga.gspec = gspec;
-        }
-        if (grid_gsh(d->nbin, ga.Ns, L.lng)) ga.gsh = (double *)(ws + L.gsh);
-        ppf::CzPlan cz{};
-        if (cz_plan(ga.Ns, d->nbin / 2 + 1, cz)) {
-            if ((rc = cz_tables(ctx, cz, st, &ga.czB, &ga.czT))) return rc;
-            ga.czP = cz.P; ga.czJ = cz.J; ga.czQ = cz.Q; ga.czK = cz.K;
-        }
-        if ((e = ppf::launch_guess(ga, st)) != hipSuccess) return hip_fail(ctx, e, "k_guess");
-    }
-    mark(3);
-
-    ppf::SolveArgs sa{};
-    sa.nsub = d->nsub; sa.nchan = d->nchan; sa.nbin = d->nbin;
-    sa.X = xa.X; sa.Mft = Mft; sa.model_index = d->model_index; sa.chan = xa.chan;
-    sa.MP = (const double *)(ws + L.MP);
-    sa.KC = (const int32_t *)(ws + L.KC);
-    sa.freqs = d->freqs; sa.P = d->P; sa.mask = d->chan_mask; sa.init = d->init;
-    sa.fit_flags = d->fit_flags; sa.nu_fits = d->nu_fits; sa.nu_outs = d->nu_outs;
-    sa.bounds = d->bounds;
-    sa.log10_tau = d->log10_tau; sa.option = d->option; sa.is_toa = d->is_toa; sa.mode = d->mode;
-    sa.max_iter = d->max_iter; sa.guess = d->guess; sa.x0 = (double *)(ws + L.x0);
-    sa.newton = (d->options & PPF_OPT_SCIPY_TR) ? 0 : 1;
-    sa.stats = (double *)(ws + L.stats); sa.results = d->results; sa.scales = d->scales;
-    sa.scale_errs = d->scale_errs; sa.channel_snrs = d->channel_snrs; sa.covariance = d->covariance;
-    sa.any_plain = 1;
-    sa.any_scat = 1;
-    sa.state = (ppf::TRState *)(ws + L.state);
-    sa.partials = (double *)(ws + L.partials);
-    sa.active = (unsigned *)(ws + L.active);
-    sa.rc_count = sa.active + 1;             // reset together with active
-    sa.rc_list = (int32_t *)(ws + L.rclist);
-    sa.kinds = kinds;
-    sa.rec = ca.rec;
-    if (!ctx->host_active) {
-        e = hipHostMalloc((void **)&ctx->host_active, 4 * sizeof(unsigned));
-        if (e != hipSuccess) return hip_fail(ctx, e, "hipHostMalloc");
-    }
-    sa.moments = use_moments;
-    sa.mom = (double2 *)(ws + L.mom);
-    sa.dphi = (double *)(ws + L.dphi);
-    sa.mres = (double *)(ws + L.mres);
-    // 16 moments about each wave's band centre (mom16_layout)
-    const bool m16 = mom16_layout(L, d->nbin);
-    sa.mom16 = m16;
-    sa.hcen = m16 ? (double *)(ws + L.hcen) : nullptr;
-    sa.xslot = xslot;
-    sa.xtile = xtile;
-    sa.xnh = L.xnh;
-    if (sa.moments) sa.any_plain = 0;      // plain fits go through the moments
-    if ((e = ppf::launch_tr_init(sa, st)) != hipSuccess) return hip_fail(ctx, e, "k_tr_init");
-    // how many fits iterate on the moments and how many on streaming passes:
-    // the iteration loop launches only the kernels some fit needs.  Where
-    // PPF_OPT_NO_X took effect (fit_layout: the fused path without moments
-    // from X, xcap == 0) no X slot exists, a sub-int that would stream has
-    // ended with PPF_ST_NOSPACE in k_tr_init and every other fit is a
-    // moment fit, so the answer is known without the read-back and its
-    // stream synchronisation (round 6: one host round trip less per call, a
-    // few percent of a ppalign iteration); the moment kernels of a batch
-    // with nothing left to fit exit at once.  Everywhere else (block-FFT and
-    // long rows, moments from X) the option reserves nothing less and every
-    // streaming sub-int holds a valid slot, so the counts decide.  Without
-    // the option they are read here.  With it (the C2 pipeline: moments from
-    // X at 2048 bins) the caller expects no streaming fit, and the counts
-    // ride along with the first read-back of the iteration loop instead
-    // (kinds_late): no round trip of their own, and a streaming sub-int that
-    // is there after all gets its k_pass from the second group on -- a
-    // sub-int's iterations do not depend on the round they start in
-    const bool no_stream = sa.moments && L.fused && L.xcap == 0;
-    bool kinds_late = !no_stream && sa.moments && (d->options & PPF_OPT_NO_X);
-    bool any_mom = true, any_pass = false;
-    if (!no_stream && !kinds_late) {
-        if ((rc = read_back(ctx, ctx->host_active + 1, sa.kinds, 2, st, d->options & PPF_OPT_SPIN_WAIT))) return rc;
-        any_mom = ctx->host_active[1] != 0;
-        any_pass = ctx->host_active[2] != 0;
-    }
-    ppf::XmomArgs ma{};
-    ma.nsub = d->nsub; ma.nchan = d->nchan; ma.nbin = d->nbin; ma.log2N = xa.log2N;
-    ma.nblk = L.nblk; ma.cb = L.cb; ma.dtype = d->data_dtype; ma.xcd_swizzle = xcd1;
-    ma.data = d->data; ma.Mft = Mft; ma.model_index = d->model_index; ma.mask = d->chan_mask;
-    ma.chan = xa.chan; ma.dphi = sa.dphi; ma.T = T; ma.T2 = T2; ma.state = sa.state;
-    ma.mom = (double *)sa.mom;
-    ma.Bt = (const double *)(ws + L.Bt);
-    ma.kc = kc; ma.errs = d->errs; ma.Mpow = Mpow; ma.mres = sa.mres; ma.nmodel = d->nmodel;
-    ma.rc_count = sa.rc_count; ma.rc_list = sa.rc_list;
-    ma.KC = (const int32_t *)(ws + L.KC);
-    if (fused && (e = ppf::launch_btab(d->nbin / 2, (double *)(ws + L.Bt), st)) != hipSuccess)
-        return hip_fail(ctx, e, "k_btab");
-    // trust-region iterations.  Scattering fits: each iteration = one
-    // streaming pass (k_pass) + one step (k_tr_step).  Other fits: k_moments
-    // (re)centres the moment sets of the sub-ints that asked, k_tr_mom runs
-    // iterations until the fit stops or leaves the expansion radius.  Groups
-    // of rounds are queued without host synchronisation; the count of
-    // sub-ints still needing work is read back between groups.
-    const int maxiter = d->max_iter > 0 ? d->max_iter : 200 * 5;
-    int iter = 0;
-    // Moment-only batches read the counter after the first round: most
-    // phase+DM fits finish inside it (C2: 1.0 data passes per fit), so the
-    // empty re-centring launches that a longer first group would queue
-    // are not worth the one synchronisation they save.
-    for (int group = (sa.moments && !any_pass) ? 1 : (sa.moments ? 3 : 6); any_mom || any_pass;
-         group = sa.moments ? 2 : 4) {
-        for (int g = 0; g < group; ++g) {
-            if (any_pass) {
-                std::pair<hipEvent_t, hipEvent_t> *pe = nullptr;
-                if (ctx->prof) {
-                    auto &v = ctx->pass_ev[slot];
-                    if ((int)v.size() <= ctx->npass[slot]) {
-                        std::pair<hipEvent_t, hipEvent_t> pr{};
-                        if ((e = hipEventCreate(&pr.first)) != hipSuccess)
-                            return hip_fail(ctx, e, "hipEventCreate");
-                        if ((e = hipEventCreate(&pr.second)) != hipSuccess) {
-                            (void)hipEventDestroy(pr.first);
-                            return hip_fail(ctx, e, "hipEventCreate");
-                        }
-                        v.push_back(pr);
-                    }
-                    pe = &v[ctx->npass[slot]++];
-                    (void)hipEventRecord(pe->first, st);
-                }
-                if ((e = ppf::launch_pass(sa, st)) != hipSuccess) return hip_fail(ctx, e, "k_pass");
-                if (pe) (void)hipEventRecord(pe->second, st);
-            }
-            if (sa.moments && any_mom) {
-                const bool full = iter == 0 && g == 0;
-                if (full) mark(5);
-                if (fused && !full) {
-                    // re-centring passes: usually few sub-ints, so 8-channel
-                    // blocks (4x the workgroups, a quarter of the rounds
-                    // each) keep more CUs busy; a channel's moments do not
-                    // depend on its block
-                    ppf::XmomArgs mr = ma;
-                    if (mr.cb > 8) {
-                        mr.cb = 8;
-                        mr.nblk = (d->nchan + 7) / 8;
-                        mr.xcd_swizzle = (mr.nblk % 8 == 0) ? 1 : 0;
-                    }
-                    e = ppf::launch_xmom(mr, false, st);
-                } else {
-                    e = fused ? ppf::launch_xmom(ma, full, st) : ppf::launch_moments(sa, st);
-                }
-                if (e != hipSuccess) return hip_fail(ctx, e, fused ? "k_xmom" : "k_moments");
-                if (full) {
-                    mark(6);
-                    ctx->ran[slot][4] = true;
-                }
-            }
-            if ((e = hipMemsetAsync(sa.active, 0, 2 * sizeof(unsigned), st)) != hipSuccess)
-                return hip_fail(ctx, e, "hipMemsetAsync");
-            if (any_pass) {
-                auto *pe = solv_begin(1);
-                if ((e = ppf::launch_tr_step(sa, st)) != hipSuccess) return hip_fail(ctx, e, "k_tr_step");
-                solv_end(pe);
-            }
-            if (sa.moments && any_mom) {
-                auto *pe = solv_begin(0);
-                if ((e = ppf::launch_tr_mom(sa, st)) != hipSuccess) return hip_fail(ctx, e, "k_tr_mom");
-                solv_end(pe);
-            }
-        }
-        iter += group;
-        // (the same stream, in order: the counts have landed when the
-        // read-back behind them has)
-        if (kinds_late && (e = hipMemcpyAsync(ctx->host_active + 1, sa.kinds, 2 * sizeof(unsigned),
-                                              hipMemcpyDeviceToHost, st)) != hipSuccess)
-            return hip_fail(ctx, e, "hipMemcpyAsync");
-        if ((rc = read_back(ctx, ctx->host_active, sa.active, 1, st, d->options & PPF_OPT_SPIN_WAIT))) return rc;
-        if (kinds_late) {
-            kinds_late = false;
-            if (ctx->host_active[2] != 0) {
-                any_pass = true;      // fits still in PH_INIT: not counted in active yet
-                continue;
-            }
-        }
-        if (*ctx->host_active == 0 || iter > maxiter + 2) break;
-    }
-    {
-        auto *pe = solv_begin(2);
-        if ((e = ppf::launch_postfit(sa, st)) != hipSuccess) return hip_fail(ctx, e, "k_postfit");
-        solv_end(pe);
-    }
-    mark(4);
+    FitCall c{};
+    c.ctx = ctx; c.d = d; c.st = (hipStream_t)stream;
+    if ((rc = c.begin())) return rc;
+    c.mark(0);
+    if ((rc = c.models())) return rc;
+    c.mark(1);
+    if ((rc = c.spectra())) return rc;
+    c.mark(2);
+    if (d->guess && (rc = c.guess())) return rc;
+    c.mark(3);
+    const ppf::SolveArgs sa = c.solve_args();
+    if ((rc = c.solve(sa))) return rc;
+    if ((rc = c.postfit(sa))) return rc;
+    c.mark(4);
     if (ctx->prof) ++ctx->ncalls;
     return PPF_OK;
 }
@@ -1453,8 +1493,7 @@ int ppf_phase_shift_batch(ppf_ctx *ctx, int32_t nprof, int32_t nbin, int32_t in_
         }
     }
     ppf::LongNoiseArgs f;
-    if (!bluestein_plan(nbin, (nbin & 1) ? nbin : nbin / 2, !(nbin & 1), f))
-        return fail(ctx, PPF_EUNSUP, "nbin=%d", nbin);
+    if (!long_row_plan(nbin, f)) return fail(ctx, PPF_EUNSUP, "nbin=%d", nbin);
     const size_t nharm = (size_t)nbin / 2 + 1, row_b = (size_t)f.M * sizeof(double2);
     FitLayout L{};
     const int64_t rows = std::max<int64_t>(nprof, nmodel);

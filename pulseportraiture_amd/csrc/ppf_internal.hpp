@@ -175,13 +175,11 @@ struct SolveArgs {
     double *stats;               // [nsub][2][nchan][10]
     ppf_result *results;
     double *scales, *scale_errs, *channel_snrs, *covariance;
-    int any_plain, any_scat;
     TRState *state;              // [nsub]
     double *partials;            // [nsub][pass_blocks(nchan)][21]
     unsigned *active;            // sub-ints still iterating (k_tr_step)
     unsigned *kinds;             // k_tr_init: [0] moment-mode fits, [1] streaming-pass fits
     // moment-expansion solver for fits without scattering (ppf_moments)
-    int moments;                 // 1: enabled
     double2 *mom;                // [nsub][2][nchan][kMoments]
     double *dphi;                // [nsub][nchan][2]: d phi_n / d(DM, GM)
     double *mres;                // [nsub][2][nchan]: moment-centre residual per channel

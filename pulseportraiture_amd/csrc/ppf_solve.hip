@@ -4,7 +4,7 @@
 //   k_tr_init                     per sub-int: prologue (usable channels,
 //                                 nu_fit defaults, Sd, dof, start point)
 //   repeat { k_pass ; k_tr_step } until every sub-int has stopped
-//     k_pass<SCAT,U>              grid (sub-int x block of 64 channels): one
+//     k_pass                      grid (sub-int x block of 64 channels): one
 //                                 streaming pass over the cross spectrum at
 //                                 the point each sub-int wants evaluated ->
 //                                 per-channel C, C', C'' (+ scattering sums)
@@ -375,7 +375,7 @@ __global__ __launch_bounds__(kBlock) void k_tr_init(SolveArgs a) {
     }
     // moment mode: phase-only channel model (no scattering), the objective
     // and its derivatives from per-channel Taylor moments (ppf_moments)
-    const int mmode = (a.moments && !scat && nf > 0 && cnt > 0.0) ? 1 : 0;
+    const int mmode = (!scat && nf > 0 && cnt > 0.0) ? 1 : 0;
     if (lane == 0) {
         S.mmode = mmode;
         S.mom16 = (mmode && a.mom16) ? 1 : 0;
@@ -417,7 +417,6 @@ __global__ __launch_bounds__(kBlock) void k_tr_init(SolveArgs a) {
 // ===========================================================================
 constexpr int kPassChans = kBlock;             // channels per workgroup
 
-template <bool SCAT>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) void k_pass(SolveArgs a) {
     __shared__ double red[kWaves * 21];
     const int nblk = (a.nchan + kPassChans - 1) / kPassChans;
@@ -436,7 +435,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
         s = blockIdx.x % a.nsub;
     }
     const TRState &S = a.state[s];
-    if (S.phase == PH_DONE || S.scat != (SCAT ? 1 : 0) || S.mmode) return;
+    if (S.phase == PH_DONE || !S.scat || S.mmode) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nharm = (a.nbin >> 1) + 1;
     const double *fr = a.freqs + (int64_t)s * a.nchan;
@@ -492,10 +491,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
                                       a.xnh * a.nchan + n;
         const double *Pc = a.MP + (int64_t)mi * nharm * a.nchan + n;
         const int64_t xs = a.nchan;
-        if (SCAT) {
-            aa = kTwoPi * tau_lin * pow(nu / g.nu_tau, alpha);
-            inv_e2 = chan[n * 4 + 1];
-        }
+        aa = kTwoPi * tau_lin * pow(nu / g.nu_tau, alpha);
+        inv_e2 = chan[n * 4 + 1];
         // Scattering terms in closed form (pptoaslib.py:344-455 restated):
         // with u = 2 pi k tau_n, d = 1 / (1 + u^2), w = conj(B) = d (1 + iu),
         //   B - 1 = -iu B, so dB ~ B (B - 1) = -iu B^2, d2B ~ -u^2 B^3 and
@@ -527,7 +524,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
                 const int k = min(kb + u, kend - 1);
                 // X streamed past the L2, which keeps |M|^2 (ld_stream)
                 xo[u] = ld_stream(Xc + k * xs);
-                if (SCAT) po[u] = Pc[k * xs];
+                po[u] = Pc[k * xs];
             }
         };
         double2 E = cmk(1.0, 0.0);
@@ -540,34 +537,28 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
                 const double kk = (double)(kb + u);
                 const bool in = kb + u < kb1;
                 const double2 y = in ? cmul(xv[u], E) : cmk(0.0, 0.0);
-                if (!SCAT) {
-                    a0 += y.x;
-                    a1 = fma(kk, y.y, a1);
-                    a2 = fma(kk * kk, y.x, a2);
-                } else {
-                    const double uu = aa * kk, u2 = uu * uu;
-                    const double den = 1.0 + u2;
-                    // 1 / den: hardware reciprocal + two Newton steps (den in
-                    // [1, inf): no scaling or special cases needed)
-                    double d = __builtin_amdgcn_rcp(den);
-                    d = fma(d, fma(-den, d, 1.0), d);
-                    d = fma(d, fma(-den, d, 1.0), d);
-                    const double ud = uu * d;
-                    const double2 z1 = cmk(fma(y.x, d, -y.y * ud), fma(y.y, d, y.x * ud));
-                    const double2 z2 = cmk(fma(z1.x, d, -z1.y * ud), fma(z1.y, d, z1.x * ud));
-                    const double z3 = fma(z2.x, d, -z2.y * ud);
-                    a0 += z1.x;
-                    a1 = fma(kk, z1.y, a1);
-                    a2 = fma(kk * kk, z1.x, a2);
-                    q1 = fma(-uu, z2.y, q1);
-                    q1p = fma(kk * uu, z2.x, q1p);
-                    q2 = fma(-u2, z3, q2);
-                    const double Pk = (in ? pv[u] : 0.0) * inv_e2;
-                    s0 = fma(d, Pk, s0);
-                    const double tp = u2 * d * d * Pk;
-                    t1 += tp;
-                    t2 = fma(tp * d, 1.0 - u2, t2);
-                }
+                const double uu = aa * kk, u2 = uu * uu;
+                const double den = 1.0 + u2;
+                // 1 / den: hardware reciprocal + two Newton steps (den in
+                // [1, inf): no scaling or special cases needed)
+                double d = __builtin_amdgcn_rcp(den);
+                d = fma(d, fma(-den, d, 1.0), d);
+                d = fma(d, fma(-den, d, 1.0), d);
+                const double ud = uu * d;
+                const double2 z1 = cmk(fma(y.x, d, -y.y * ud), fma(y.y, d, y.x * ud));
+                const double2 z2 = cmk(fma(z1.x, d, -z1.y * ud), fma(z1.y, d, z1.x * ud));
+                const double z3 = fma(z2.x, d, -z2.y * ud);
+                a0 += z1.x;
+                a1 = fma(kk, z1.y, a1);
+                a2 = fma(kk * kk, z1.x, a2);
+                q1 = fma(-uu, z2.y, q1);
+                q1p = fma(kk * uu, z2.x, q1p);
+                q2 = fma(-u2, z3, q2);
+                const double Pk = (in ? pv[u] : 0.0) * inv_e2;
+                s0 = fma(d, Pk, s0);
+                const double tp = u2 * d * d * Pk;
+                t1 += tp;
+                t2 = fma(tp * d, 1.0 - u2, t2);
                 E = cmul(E, W);
             }
         };
@@ -609,45 +600,26 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
     if (use_n && (!split || wave == 0)) {
         double my[10];
         my[0] = a0; my[1] = -kTwoPi * a1; my[2] = -kTwoPi * kTwoPi * a2;
-        if (SCAT) {
-            my[3] = q1; my[4] = -kTwoPi * q1p; my[5] = q2;
-            my[6] = s0; my[7] = -2.0 * t1; my[8] = 2.0 * t1; my[9] = -2.0 * t2;
-        } else {
-            my[3] = my[4] = my[5] = my[7] = my[8] = my[9] = 0.0;
-            my[6] = chan[n * 4 + 3];
-        }
+        my[3] = q1; my[4] = -kTwoPi * q1p; my[5] = q2;
+        my[6] = s0; my[7] = -2.0 * t1; my[8] = 2.0 * t1; my[9] = -2.0 * t2;
         double *dst = stats + (int64_t)n * 10;
 #pragma unroll
         for (int q = 0; q < 10; ++q) dst[q] = my[q];
         const double C = my[0], Sn = my[6], iS = 1.0 / Sn;
-        if (!SCAT) {
-            const double dph[3] = {1.0, kDconst * (pow(nu, -2.0) - nuDM2) / g.P,
-                                   kDconst * kDconst * (pow(nu, -4.0) - nuGM4) / g.P};
-            const double Cp = my[1], Cpp = my[2];
-            const double hn = -2.0 * (C * Cpp + Cp * Cp) * iS;
-            acc[0] = -C * C * iS;
-            for (int i = 0; i < 3; ++i) {
-                if (!(flagmask >> i & 1)) continue;
-                acc[1 + i] = -2.0 * C * Cp * dph[i] * iS;
-                for (int j = i; j < 3; ++j)
-                    if (flagmask >> j & 1) acc[6 + uidx(i, j)] = hn * dph[i] * dph[j];
-            }
-        } else {
-            Fac fc = make_fac(nu, g, alpha);
-            double dC[5], dS[5], d2C[5][5], d2S[5][5];
-            chan_derivs(my, fc, dC, dS, d2C, d2S);
-            const double iS2 = iS * iS, iS3 = iS2 * iS, C2 = C * C;
-            acc[0] = -C2 * iS;
-            for (int i = 0; i < 5; ++i) {
-                if (!(flagmask >> i & 1)) continue;
-                acc[1 + i] = -(2.0 * C * dC[i] * iS - C2 * dS[i] * iS2);
-                for (int j = i; j < 5; ++j)
-                    if (flagmask >> j & 1)
-                        acc[6 + uidx(i, j)] =
-                            -2.0 * (C * d2C[i][j] * iS - 0.5 * C2 * d2S[i][j] * iS2 +
-                                    dC[i] * dC[j] * iS + C2 * dS[i] * dS[j] * iS3 -
-                                    C * (dC[i] * dS[j] + dS[i] * dC[j]) * iS2);
-            }
+        Fac fc = make_fac(nu, g, alpha);
+        double dC[5], dS[5], d2C[5][5], d2S[5][5];
+        chan_derivs(my, fc, dC, dS, d2C, d2S);
+        const double iS2 = iS * iS, iS3 = iS2 * iS, C2 = C * C;
+        acc[0] = -C2 * iS;
+        for (int i = 0; i < 5; ++i) {
+            if (!(flagmask >> i & 1)) continue;
+            acc[1 + i] = -(2.0 * C * dC[i] * iS - C2 * dS[i] * iS2);
+            for (int j = i; j < 5; ++j)
+                if (flagmask >> j & 1)
+                    acc[6 + uidx(i, j)] =
+                        -2.0 * (C * d2C[i][j] * iS - 0.5 * C2 * d2S[i][j] * iS2 +
+                                dC[i] * dC[j] * iS + C2 * dS[i] * dS[j] * iS3 -
+                                C * (dC[i] * dS[j] + dS[i] * dC[j]) * iS2);
         }
     }
     // fixed-order reduction: lanes (channel order) -> waves -> block partial
@@ -2038,16 +2010,9 @@ hipError_t launch_tr_init(const SolveArgs &a, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <bool SCAT>
-static void launch_pass_t(const SolveArgs &a, hipStream_t st, dim3 g) {
-    hipLaunchKernelGGL((k_pass<SCAT>), g, dim3(kBlock), 0, st, a);
-}
-
 hipError_t launch_pass(const SolveArgs &a, hipStream_t st) {
     const int nblk = (a.nchan + kPassChans - 1) / kPassChans;
-    dim3 g((unsigned)((int64_t)a.nsub * nblk));
-    if (a.any_plain) launch_pass_t<false>(a, st, g);
-    if (a.any_scat) launch_pass_t<true>(a, st, g);
+    hipLaunchKernelGGL(k_pass, dim3((unsigned)((int64_t)a.nsub * nblk)), dim3(kBlock), 0, st, a);
     return hipGetLastError();
 }
 
@@ -2061,7 +2026,7 @@ hipError_t launch_tr_step(const SolveArgs &a, hipStream_t st) {
         else hipLaunchKernelGGL(k_tr_step_l<false>, gl, dim3(64), lds, st, a);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        if (a.any_scat) hipLaunchKernelGGL(k_tr_gates, g, dim3(kBlock), 0, st, a);
+        hipLaunchKernelGGL(k_tr_gates, g, dim3(kBlock), 0, st, a);
         return hipGetLastError();
     }
     if (a.bounds)
@@ -2101,11 +2066,8 @@ hipError_t launch_tr_mom(const SolveArgs &a, hipStream_t st) {
     // updates overlap other workgroups' evaluation passes): C2 k_tr_mom 163
     // vs 171 ms per 120 calls, C4 332.8-338.6k vs 322.7-330.6k
     // archive-iterations/s in one call (profiles/r05/ab_tb1_status.txt)
-    // (the 64- and 256-thread instantiations are still compiled, not launched)
-    const int tb = 128;
-    if (tb == 64) hipLaunchKernelGGL(k_tr_mom<64>, dim3((unsigned)a.nsub), dim3(64), 0, st, a);
-    else if (tb == 128) hipLaunchKernelGGL(k_tr_mom<128>, dim3((unsigned)a.nsub), dim3(128), 0, st, a);
-    else hipLaunchKernelGGL(k_tr_mom<256>, dim3((unsigned)a.nsub), dim3(256), 0, st, a);
+    // (the 64- and 256-thread variants were measured and are no longer compiled)
+    hipLaunchKernelGGL(k_tr_mom<128>, dim3((unsigned)a.nsub), dim3(128), 0, st, a);
     return hipGetLastError();
 }
 

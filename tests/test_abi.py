@@ -121,6 +121,29 @@ def test_workspace_query_and_validation_without_gpu():
                                None, 0, None, 0, None) == _lib.PPF_EINVAL
 
 
+def test_workspace_bytes_match_golden_table():
+    """ppf_fit_workspace_bytes, byte for byte, over the descriptor grid of
+    tests/golden/make_golden_workspace.py (the table comes from a build of
+    the commit before the workspace carving was last rewritten)."""
+    import json
+    golden = os.path.join(os.path.dirname(__file__), "golden")
+    with open(os.path.join(golden, "fit_workspace.json")) as f:
+        entries = json.load(f)
+    assert len(entries) == 8 * 3 * 2 * 2 * 3 * 4 * 2
+    assert len({tuple(e[:-1]) for e in entries}) == len(entries)
+    assert {e[0] for e in entries} == {64, 1000, 1001, 1024, 2048, 4096,
+                                       8194, 16384}
+    assert {e[6] for e in entries} == {0, _lib.OPT_NO_X, _lib.OPT_MOM_X,
+                                       _lib.OPT_FUSED_MOM}
+    lib = _lib.load()
+    d = _lib.FitDesc()
+    for nbin, nchan, nsub, nmodel, guess, ns, options, xs, nbytes in entries:
+        d.nbin, d.nchan, d.nsub, d.nmodel = nbin, nchan, nsub, nmodel
+        d.guess, d.guess_Ns, d.options, d.x_subints = guess, ns, options, xs
+        assert lib.ppf_fit_workspace_bytes(ctypes.byref(d)) == nbytes, \
+            (nbin, nchan, nsub, nmodel, guess, ns, options, xs)
+
+
 @pytest.mark.parametrize("seed", range(40))
 def test_poly_real_roots_matches_np_roots(seed):
     rng = np.random.default_rng(seed)
