@@ -483,7 +483,11 @@ int ppf_scales_batch(ppf_ctx *ctx, int32_t nsub, int32_t nchan, int32_t nharm, c
  * wts: float32 [nsub][nchan] or NULL; stats: [nsub][nchan][3] = off-pulse
  * mean, off-pulse sigma, S/N (on-pulse sum / (sigma sqrt(n_on)));
  * total: [nsub][nbin] weighted total profiles; wstart: int32 [nsub] window
- * starts.  Any nbin >= 2.  workspace: ppf_unpack_workspace_bytes(). */
+ * starts (the first minimum in bin order).  raw and sub_stride must be
+ * multiples of the element size (2, 1, 4, 4 bytes for elem 0..3): PPF_EINVAL
+ * otherwise, before any launch.  Any nbin >= 2: the total profile is held in
+ * one workgroup's LDS up to 18,816 bins and read from `total` past that.
+ * workspace: ppf_unpack_workspace_bytes(). */
 size_t ppf_unpack_workspace_bytes(int32_t nsub, int32_t nchan, int32_t nbin);
 int ppf_unpack_psrfits_batch(ppf_ctx *ctx, int32_t nsub, int32_t npol, int32_t nchan, int32_t nbin,
                              int32_t elem, const void *raw, int64_t sub_stride, const float *scl,

@@ -1386,6 +1386,10 @@ int ppf_unpack_psrfits_batch(ppf_ctx *ctx, int32_t nsub, int32_t npol, int32_t n
     const int64_t esize = elem == 0 ? 2 : (elem == 1 ? 1 : 4);
     if (sub_stride < (int64_t)(pol_mode == 1 ? 2 : 1) * nchan * nbin * esize)
         return fail(ctx, PPF_EINVAL, "sub_stride %lld < one sub-int's DATA", (long long)sub_stride);
+    // the kernel loads whole elements: every sub-int block starts on one
+    if (sub_stride % esize || (uintptr_t)raw % (uintptr_t)esize)
+        return fail(ctx, PPF_EINVAL, "raw and sub_stride must be multiples of the %lld-byte element",
+                    (long long)esize);
     if (nsub == 0) return PPF_OK;
     if (!raw || !scl || !offs || !out || !stats || !total || !wstart || !workspace)
         return fail(ctx, PPF_EINVAL, "null unpack pointer");

@@ -71,15 +71,23 @@ __global__ __launch_bounds__(256) void k_unpack(UnpackArgs a) {
     }
 }
 
+// The total profile of a sub-int sits in LDS (nbin doubles) while its window
+// sums are formed; a profile past kBaseLdsMax bytes (nbin > 18,816) is read
+// back from a.total instead (GLOBAL: written by this workgroup just before,
+// visible to it after the barrier), so any length runs.
+constexpr size_t kBaseLdsMax = 150u * 1024u - 3u * 1024u;   // next to rb / ri
+
+template <bool GLOBAL>
 __global__ __launch_bounds__(256) void k_base_window(UnpackArgs a) {
-    extern __shared__ double tot[];
+    extern __shared__ double tot_lds[];
     const int s = blockIdx.x;
     const int nblk = (a.nchan + kUnpackChans - 1) / kUnpackChans;
+    double *tot = GLOBAL ? a.total + (int64_t)s * a.nbin : tot_lds;
     for (int b = threadIdx.x; b < a.nbin; b += blockDim.x) {
         double t = 0.0;
         for (int k = 0; k < nblk; ++k) t += a.part[((int64_t)s * nblk + k) * a.nbin + b];
         tot[b] = t;
-        a.total[(int64_t)s * a.nbin + b] = t;
+        if (!GLOBAL) a.total[(int64_t)s * a.nbin + b] = t;
     }
     __syncthreads();
     // window sums by thread: each thread scans its share of start bins with
@@ -150,8 +158,17 @@ hipError_t launch_unpack(const UnpackArgs &a, hipStream_t st) {
     hipLaunchKernelGGL(k_unpack, dim3((unsigned)((int64_t)a.nsub * nblk)), dim3(256), 0, st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_base_window, dim3((unsigned)a.nsub), dim3(256), (size_t)a.nbin * sizeof(double),
-                       st, a);
+    const size_t lds = (size_t)a.nbin * sizeof(double);
+    if (lds > kBaseLdsMax) {
+        hipLaunchKernelGGL(k_base_window<true>, dim3((unsigned)a.nsub), dim3(256), 0, st, a);
+    } else {
+        if (lds > 48 * 1024) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_base_window<false>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(k_base_window<false>, dim3((unsigned)a.nsub), dim3(256), lds, st, a);
+    }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     const int64_t rows = (int64_t)a.nsub * a.nchan;
     hipLaunchKernelGGL(k_row_stats, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a);

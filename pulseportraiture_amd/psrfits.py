@@ -410,24 +410,31 @@ def write_psrfits_rows(filename, data, scl, offs, freqs, weights, periods,
                        stt_offs=0.0, npol=1, pol_type="AA+BB", telescope="GBT",
                        frontend="Rcvr1_2", backend="GUPPI", source="J1234+5678",
                        dm=0.0, be_delay=0.0, par_ang=None, obsfreq=None,
-                       obsbw=None, ra=None, dec=None):
+                       obsbw=None, ra=None, dec=None, elem="I"):
     """write_psrfits for DATA rows already in file byte order (the output of
     engine.fake_subints(quantized=True)): data is a uint8 array [nsub, npol *
     nchan * nbin * 2] of big-endian int16 in the DATA layout [npol][nchan]
     [nbin], written as it is, row by row, with no conversion or copy on the
     host.  obsfreq / obsbw (default: the mean of freqs[0] and the channel
-    spacing times nchan) and the RA / DEC cards can be given."""
+    spacing times nchan) and the RA / DEC cards can be given.  elem: the
+    FITS sample type of DATA, "I" (big-endian int16), "B" (uint8: 1 byte
+    per sample) or "E" (big-endian float32: 4)."""
     data = np.asarray(data)
     freqs = np.asarray(freqs, dtype=float)
     nsub, nchan = freqs.shape
-    if data.dtype != np.uint8 or data.shape != (nsub, npol * nchan * nbin * 2):
-        raise ValueError("data must be uint8 [nsub, npol * nchan * nbin * 2]")
+    if elem not in ("I", "B", "E"):
+        raise ValueError("elem must be 'I', 'B' or 'E'")
+    esize = _TFORM[elem][0]
+    if data.dtype != np.uint8 or \
+            data.shape != (nsub, npol * nchan * nbin * esize):
+        raise ValueError("data must be uint8 [nsub, npol * nchan * nbin * %d]"
+                         % esize)
     cols = [("TSUBINT", "1D", None), ("OFFS_SUB", "1D", None),
             ("PERIOD", "1D", None), ("PAR_ANG", "1E", None),
             ("DAT_FREQ", "%dD" % nchan, None), ("DAT_WTS", "%dE" % nchan, None),
             ("DAT_OFFS", "%dE" % (nchan * npol), None),
             ("DAT_SCL", "%dE" % (nchan * npol), None),
-            ("DATA", "%dI" % (nbin * nchan * npol), "(%d,%d,%d)" % (nbin, nchan, npol))]
+            ("DATA", "%d%s" % (nbin * nchan * npol, elem), "(%d,%d,%d)" % (nbin, nchan, npol))]
     # the columns ahead of DATA, which ends each row
     metadt = np.dtype([("TSUBINT", ">f8"), ("OFFS_SUB", ">f8"), ("PERIOD", ">f8"),
                        ("PAR_ANG", ">f4"), ("DAT_FREQ", ">f8", (nchan,)),
@@ -852,6 +859,8 @@ class _Pending(object):
             st_up, st = sts
             with span("load.queue"):
                 dbuf = torch.empty(nraw + naux, dtype=torch.uint8, device=dev)
+                # (the entry wants raw and the sub-int stride on element
+                # boundaries: an allocation's start, nbytes = whole elements)
                 raw_d = dbuf[:nsub * nbytes].view(nsub, nbytes)
                 aux_d = dbuf[nraw:nraw + naux].view(torch.float32)
                 with torch.cuda.stream(st_up):
