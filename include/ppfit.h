@@ -50,8 +50,8 @@ extern "C" {
  * queries), ppf_align_phases, PPF_OPT_SPIN_WAIT; ppf_fit_batch /
  * ppf_gauss_portrait_batch / ppf_phase_shift_batch accept nbin past the LDS
  * transforms (even > 8192, odd > 4095) on the long transforms.
- * ppf_inst_response_batch was added later without a bump (purely additive:
- * no structure or existing signature changed). */
+ * ppf_inst_response_batch and ppf_pack_psrfits_batch were added later without
+ * a bump (purely additive: no structure or existing signature changed). */
 #define PPF_ABI_VERSION 6
 
 enum ppf_error {
@@ -495,6 +495,33 @@ int ppf_unpack_psrfits_batch(ppf_ctx *ctx, int32_t nsub, int32_t npol, int32_t n
                              int32_t rm_baseline, float *out, double *stats, double *total,
                              int32_t *wstart, void *workspace, size_t workspace_bytes,
                              void *stream);
+
+/* The inverse of ppf_unpack_psrfits_batch (added within ABI 6: purely
+ * additive, a library without the symbol is a stale build): float rows on
+ * the device become the DATA bytes of a fold-mode SUBINT table, as
+ * pplib.write_archive / unload_new_archive (pplib.py:3146-3300) store them.
+ * rows: [nrow][nbin] float32 (PPF_F32) or float64 (PPF_F64), device; raw:
+ * [nrow][nbin * esize] bytes in file order; scl, offs: float32 [nrow]
+ * (DAT_SCL, DAT_OFFS of each row).
+ *   elem 0, big-endian int16 (esize 2): per row, with lo / hi its minimum /
+ *     maximum, offs = f32((lo + hi) / 2), scl = f32(max((hi - lo) / 2 / 32767,
+ *     1e-30)), q = clip(rint((x - offs) / scl), -32768, 32767): float64
+ *     arithmetic, one rounding per operation, round-half-even -- the numbers
+ *     of psrfits.quantize bit for bit, and those of ppf_fake_batch's
+ *     PPF_FAKE_I16.
+ *   elem 2, big-endian float32 (esize 4): the sample is (float)x, scl = 1,
+ *     offs = 0.
+ * Any nbin >= 1 (rows are never staged in LDS); rows with nbin % 8 == 0 and
+ * 16-byte aligned rows / raw take 16-byte accesses, every other shape
+ * element-wide ones.  No atomics: the output is bitwise reproducible.  A row
+ * holding a NaN or an Inf is the caller's error: its bytes are unspecified
+ * (no fault).  PPF_EINVAL, before any launch: nrow < 0, nbin < 1, an elem
+ * other than 0 / 2, an in_dtype other than PPF_F32 / PPF_F64, a byte count
+ * past int64; then nrow == 0 returns PPF_OK (nothing else is looked at);
+ * then a NULL ctx or array, rows / raw not aligned to their element. */
+int ppf_pack_psrfits_batch(ppf_ctx *ctx, int64_t nrow, int32_t nbin, int32_t in_dtype,
+                           const void *rows, int32_t elem, void *raw,
+                           float *scl, float *offs, void *stream);
 
 /* nbytes from page-locked host memory src (a pinned buffer: hipHostMalloc /
  * torch pin_memory) to device memory dst, read by a kernel over PCIe on

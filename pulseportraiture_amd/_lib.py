@@ -156,6 +156,8 @@ SIGNATURES = {
                                                 _vp, _vp, _vp, _i32, _i32,
                                                 _vp, _vp, _vp, _vp, _vp,
                                                 ctypes.c_size_t, _vp]),
+    "ppf_pack_psrfits_batch": (ctypes.c_int, [_vp, ctypes.c_int64, _i32, _i32,
+                                              _vp, _i32, _vp, _vp, _vp, _vp]),
     "ppf_copy_from_pinned": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64,
                                             _vp]),
     "ppf_read_rows": (ctypes.c_int, [_i32, ctypes.c_int64, ctypes.c_int64,
@@ -189,7 +191,8 @@ def load():
                     fn = getattr(lib, name)
                 except AttributeError:
                     # an entry point added without an ABI bump
-                    # (ppf_inst_response_batch): a library built before it
+                    # (ppf_inst_response_batch, ppf_pack_psrfits_batch): a
+                    # library built before it
                     raise RuntimeError(
                         "libppfit ABI mismatch: %s missing (rebuild with "
                         "make)" % name) from None

@@ -1409,6 +1409,29 @@ int ppf_unpack_psrfits_batch(ppf_ctx *ctx, int32_t nsub, int32_t npol, int32_t n
     return PPF_OK;
 }
 
+int ppf_pack_psrfits_batch(ppf_ctx *ctx, int64_t nrow, int32_t nbin, int32_t in_dtype,
+                           const void *rows, int32_t elem, void *raw, float *scl, float *offs,
+                           void *stream) {
+    if (nrow < 0 || nbin < 1 || (elem != 0 && elem != 2) ||
+        (in_dtype != PPF_F32 && in_dtype != PPF_F64))
+        return fail(ctx, PPF_EINVAL, "bad pack arguments (nrow=%lld nbin=%d in_dtype=%d elem=%d)",
+                    (long long)nrow, nbin, in_dtype, elem);
+    // the byte counts stay inside int64
+    if (nrow > INT64_MAX / ((int64_t)nbin * 8))
+        return fail(ctx, PPF_EINVAL, "pack: nrow=%lld x nbin=%d overflows", (long long)nrow, nbin);
+    if (nrow == 0) return PPF_OK;      // nothing to launch: nothing else is looked at
+    if (!ctx) return PPF_EINVAL;
+    if (!rows || !raw || !scl || !offs) return fail(ctx, PPF_EINVAL, "null pack pointer");
+    // whole elements are loaded and stored
+    if ((uintptr_t)rows % (in_dtype == PPF_F32 ? 4 : 8) || (uintptr_t)raw % (elem == 0 ? 2 : 4))
+        return fail(ctx, PPF_EINVAL, "pack: rows / raw must be aligned to their element size");
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
+    ppf::PackArgs a{nrow, nbin, in_dtype == PPF_F32, elem, rows, (uint8_t *)raw, scl, offs};
+    if ((e = ppf::launch_pack(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e, "k_pack");
+    return PPF_OK;
+}
+
 int ppf_copy_from_pinned(ppf_ctx *ctx, void *dst, const void *src, int64_t nbytes, void *stream) {
     if (!ctx) return PPF_EINVAL;
     if (nbytes < 0 || (nbytes > 0 && (!dst || !src)))

@@ -19,8 +19,9 @@
 //            is 0 gets none (the reference's `if noise:`).
 //            out_kind PPF_FAKE_F64 stores the float64 row.  PPF_FAKE_I16 takes
 //            the block minimum / maximum of that same LDS row and applies
-//            psrfits.quantize's arithmetic to it (float64, round-half-even, FP
-//            contraction off, so the integers are the host's bit for bit):
+//            psrfits.quantize's arithmetic to it (ppf_quant.hpp: float64,
+//            round-half-even, FP contraction off, so the integers are the
+//            host's bit for bit):
 //                offs = f32((lo + hi) / 2)
 //                scl  = f32(max((hi - lo) / 2 / 32767, 1e-30))
 //                q    = clip(rint((x - offs) / scl), -32768, 32767)
@@ -33,32 +34,14 @@
 
 #include "ppf_device.hpp"
 #include "ppf_internal.hpp"
+#include "ppf_quant.hpp"
 
 namespace ppf {
 
-namespace {
-
-// psrfits.quantize, one operation per rounding
-__device__ __forceinline__ float fake_offs(double lo, double hi) {
-#pragma clang fp contract(off)
-    return (float)((lo + hi) / 2.0);
+// two neighbouring bins of the LDS row -> their four file bytes
+__device__ __forceinline__ unsigned quant_q2z(double2 z, double offs, double scl) {
+    return quant_q2(z.x, z.y, offs, scl);
 }
-__device__ __forceinline__ float fake_scl(double lo, double hi) {
-#pragma clang fp contract(off)
-    return (float)fmax((hi - lo) / 2.0 / 32767.0, 1e-30);
-}
-// the sample's two bytes in file order, as the low half of a little-endian word
-__device__ __forceinline__ unsigned fake_q(double x, double offs, double scl) {
-#pragma clang fp contract(off)
-    double q = rint((x - offs) / scl);
-    q = fmin(fmax(q, -32768.0), 32767.0);
-    return (unsigned)__builtin_bswap16((unsigned short)(short)(int)q);
-}
-__device__ __forceinline__ unsigned fake_q2(double2 z, double offs, double scl) {
-    return fake_q(z.x, offs, scl) | (fake_q(z.y, offs, scl) << 16);
-}
-
-}  // namespace
 
 template <bool MX>
 __global__ __launch_bounds__(kBlock) void k_fake(FakeArgs a) {
@@ -141,7 +124,7 @@ __global__ __launch_bounds__(kBlock) void k_fake(FakeArgs a) {
     if (threadIdx.x < kWaves) lds[threadIdx.x] = keep;
     __syncthreads();
 
-    const float offs_f = fake_offs(lo, hi), scl_f = fake_scl(lo, hi);
+    const float offs_f = quant_offs(lo, hi), scl_f = quant_scl(lo, hi);
     const double offs = (double)offs_f, scl = (double)scl_f;
     if (threadIdx.x == 0) {
         a.scl[row] = scl_f;
@@ -152,15 +135,15 @@ __global__ __launch_bounds__(kBlock) void k_fake(FakeArgs a) {
         uint4 *o = reinterpret_cast<uint4 *>(reinterpret_cast<uint16_t *>(a.out) + row * a.nbin);
         for (int j = threadIdx.x; j < (N >> 2); j += kBlock) {
             uint4 w;
-            w.x = fake_q2(lds[4 * j], offs, scl);
-            w.y = fake_q2(lds[4 * j + 1], offs, scl);
-            w.z = fake_q2(lds[4 * j + 2], offs, scl);
-            w.w = fake_q2(lds[4 * j + 3], offs, scl);
+            w.x = quant_q2z(lds[4 * j], offs, scl);
+            w.y = quant_q2z(lds[4 * j + 1], offs, scl);
+            w.z = quant_q2z(lds[4 * j + 2], offs, scl);
+            w.w = quant_q2z(lds[4 * j + 3], offs, scl);
             o[j] = w;
         }
     } else {
         unsigned *o = reinterpret_cast<unsigned *>(reinterpret_cast<uint16_t *>(a.out) + row * a.nbin);
-        for (int j = threadIdx.x; j < N; j += kBlock) o[j] = fake_q2(lds[j], offs, scl);
+        for (int j = threadIdx.x; j < N; j += kBlock) o[j] = quant_q2z(lds[j], offs, scl);
     }
 }
 

@@ -381,6 +381,18 @@ hipError_t launch_unpack(const UnpackArgs &a, hipStream_t st);
 hipError_t launch_copy_host(const void *src_dev, void *dst, int64_t nbytes, hipStream_t st);
 size_t unpack_partials(int nsub, int nchan, int nbin);
 
+// ppf_pack_psrfits_batch (ppf_pack.hip): float rows -> SUBINT DATA bytes
+struct PackArgs {
+    int64_t nrow;
+    int nbin;
+    int f32in;                   // rows are float32 (else float64)
+    int elem;                    // 0 big-endian int16, 2 big-endian float32
+    const void *rows;            // [nrow][nbin]
+    uint8_t *raw;                // [nrow][nbin * esize]
+    float *scl, *offs;           // [nrow]
+};
+hipError_t launch_pack(const PackArgs &a, hipStream_t st);
+
 // pplib.gen_gaussian_portrait (pplib.py:886-963) per (portrait, channel) row
 struct GaussArgs {
     int nport, nchan, nbin, log2N, ngauss, npar;

@@ -801,6 +801,36 @@ def unpack_psrfits(raw, elem, npol, nchan, nbin, scl, offs, wts=None,
                 _keep=(scl_t, offs_t, wts_t, ws, raw))
 
 
+def pack_rows(rows, elem="I", dev=None):
+    """ppf_pack_psrfits_batch, the inverse of unpack_psrfits: float rows ->
+    (raw, scl, offs), all on the device.  rows: a NumPy array or a device
+    tensor, float32 or float64 (anything else is converted to float64), of
+    any leading shape [..., nbin], flattened to nrow rows.  elem "I": raw
+    uint8 [nrow, nbin * 2] of big-endian int16 with psrfits.quantize's
+    per-row scl / offs (float32 [nrow]), bit for bit; "E": raw uint8 [nrow,
+    nbin * 4] of big-endian float32, scl = 1, offs = 0."""
+    if elem not in ("I", "E"):
+        raise ValueError("elem must be 'I' or 'E'")
+    dev = device(dev)
+    x = to_dev(rows, dev, _data_dtype(rows))
+    if x.dim() < 1 or x.shape[-1] < 1:
+        raise ValueError("rows must be [..., nbin] with nbin >= 1")
+    nbin = int(x.shape[-1])
+    x = x.reshape(-1, nbin)
+    nrow = int(x.shape[0])
+    esize = 2 if elem == "I" else 4
+    raw = torch.empty((nrow, nbin * esize), dtype=torch.uint8, device=dev)
+    scl = torch.empty(nrow, dtype=torch.float32, device=dev)
+    offs = torch.empty_like(scl)
+    ctx = _lib.context(dev.index)
+    rc = _lib.load().ppf_pack_psrfits_batch(
+        ctx, nrow, nbin,
+        _lib.PPF_F32 if x.dtype == torch.float32 else _lib.PPF_F64, _p(x),
+        0 if elem == "I" else 2, _p(raw), _p(scl), _p(offs), _stream(dev))
+    _lib.check(rc, ctx)
+    return raw, scl, offs
+
+
 def scales_batch(D, M, params, P, freqs, nus, log10_tau, errs_FT=None,
                  model_index=None, dev=None):
     """get_scales_full (pptoaslib.py:953-971) per sub-int: D [nsub, nchan,

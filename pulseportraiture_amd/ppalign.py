@@ -17,17 +17,22 @@ each rank its share of ``metafile``; the aligned portrait and the channel
 weights are summed across ranks with one all-reduce per iteration (RCCL over
 xGMI), the only exchange the algorithm has.
 
-Archive I/O stays on PSRCHIVE (``pptoas.load_data``, host side); the output
-archive is written through the template archive object exactly as
-ppalign.py:259-277 does when one is attached (``model_data.arch``).
+The output archive is written through the template archive object exactly
+as ppalign.py:259-277 does when one is attached (``model_data.arch``); a
+template loaded by the PSRFITS fast path has none, and the same file (one
+sub-int, DM 0, channel weights 0 / 1) is written from its metadata by
+``pplib.unload_new_archive``, the samples digitised on the device.
 """
+import os
+
 import numpy as np
 import torch
 
 from . import _lib, engine
 from . import pptoas as _pptoas
-from .pplib import (DataBunch, Dconst, fit_phase_shift, gaussian_profile,
-                    get_noise, guess_fit_freq, rotate_data)
+from .pplib import (DataBunch, Dconst, file_is_type, fit_phase_shift,
+                    gaussian_profile, get_noise, guess_fit_freq, rotate_data,
+                    unload_new_archive)
 
 rm_baseline = _pptoas.rm_baseline       # ppalign.py imports it from pptoas
 
@@ -112,6 +117,16 @@ def _channel_map(data, isub, model_data, same_freqs):
                                       data.freqs[isub, ic]))]
                     for ic in ichans], dtype=int)
     return ichans, mch
+
+
+def _fits_template(model_data):
+    """The template came from the PSRFITS fast path: its DataBunch names a
+    FITS file that exists (a DataBunch built in memory names none, and
+    nothing is written for it)."""
+    name = model_data.get("filename") if isinstance(model_data, dict) else \
+        getattr(model_data, "filename", None)
+    return isinstance(name, str) and os.path.isfile(name) and \
+        file_is_type(name, "FITS")
 
 
 class _Rows(object):
@@ -391,8 +406,9 @@ def align_archives(metafile, initial_guess, fit_dm=True, tscrunch=False,
                    comm=False, dev=None):
     """ppalign.py:65-280.  Returns a DataBunch(port=[npol, nchan, nbin]
     aligned portrait, total_weights=[nchan, nbin], nit=niter) and, like the
-    reference, writes ``outfile`` through ``model_data.arch`` when the
-    template archive object is attached."""
+    reference, writes ``outfile``: through ``model_data.arch`` when the
+    template archive object is attached, else through
+    pplib.unload_new_archive when the template is a PSRFITS file."""
     if isinstance(metafile, str):
         datafiles = [l[:-1] for l in open(metafile, "r").readlines()]
         if outfile is None:
@@ -410,8 +426,10 @@ def align_archives(metafile, initial_guess, fit_dm=True, tscrunch=False,
         print("%s: has npol = 1; need npol == 4." % initial_guess)
         raise SystemExit
     nchan, nbin = model_data.nchan, model_data.nbin
-    model_port = np.asarray((model_data.masks * model_data.subints)[0, 0],
-                            dtype=np.float64)
+    # (masks * subints)[0, 0]; the PSRFITS fast path's masks and rows are
+    # indexed, not multiplied whole
+    model_port = np.asarray(model_data.masks[0, 0], dtype=np.float64) * \
+        np.asarray(model_data.subints[0, 0], dtype=np.float64)
     dev = engine.device(dev)
     # archives are read once and kept resident (the reference re-reads them
     # every iteration; the skip tests give the same outcome each time)
@@ -508,5 +526,13 @@ def align_archives(metafile, initial_guess, fit_dm=True, tscrunch=False,
         arch.unload(outfile)
         if not quiet:
             print("\nUnloaded %s.\n" % outfile)
+    elif arch is None and outfile is not None and _fits_template(model_data):
+        # the PSRFITS fast path attaches no archive object: the same file
+        # (one sub-int, DM 0, channel weight 0 where nothing was summed)
+        # through the template's metadata
+        unload_new_archive(
+            aligned_port[None], model_data, outfile, DM=0.0, dmc=0,
+            weights=np.where(total_weights.sum(axis=1) == 0.0, 0.0, 1.0)[None],
+            quiet=quiet, dev=dev)
     return DataBunch(port=aligned_port, total_weights=total_weights,
                      nsub_fit=R.n)

@@ -1106,6 +1106,142 @@ def make_fake_pulsar(modelfile, ephemeris, outfile="fake_pulsar.fits", nsub=1,
         print("\nUnloaded %s.\n" % outfile)
 
 
+# ------------------------------------------------------- archive writers --
+def _pol_type(npol, state):
+    """The POL_TYPE make_fake_pulsar writes: npol 1 as AA+BB, npol 4 as IQUV
+    (state "Stokes") or AABBCRCI ("Coherence")."""
+    if npol == 1:
+        return "AA+BB"
+    if npol == 4 and state in ("Stokes", "Coherence"):
+        return "IQUV" if state == "Stokes" else "AABBCRCI"
+    raise NotImplementedError("npol=%r state=%r: npol 1, or 4 as Stokes / "
+                              "Coherence" % (npol, state))
+
+
+def write_archive(data, ephemeris, freqs, nu0=None, bw=None,
+                  outfile="pparchive.fits", tsub=1.0, start_MJD=None,
+                  weights=None, dedispersed=False, state="Stokes",
+                  telescope="GBT", quiet=False, elem="I", dev=None):
+    """pplib.py:3189-3299 without PSRCHIVE: data [nsub, npol, nchan, nbin]
+    (a NumPy array or a device tensor) becomes one fold-mode PSRFITS file.
+    The samples are digitised on the device (psrfits.write_archive_rows,
+    ppf_pack_psrfits_batch) and cross to the host as the bytes of the file.
+
+    The arguments are the reference's, with its defaults for nu0 (the mean
+    of freqs) and bw (the span of freqs plus one channel spacing), plus elem
+    ("I": 16-bit samples with per-profile DAT_SCL / DAT_OFFS, "E": float32
+    samples) and dev.  freqs: [nchan], or [nsub, nchan].  Departures:
+      - the ephemeris, the epochs and the folding periods are
+        make_fake_pulsar's (fake.read_par, fake.fake_epochs): start_MJD
+        defaults to PEPOCH, and sub-int i is centred tsub / 2 + i tsub
+        seconds after it with the period 1 / (F0 + F1 dt);
+      - the rows are stored as they are given: the reference hands them to
+        PSRCHIVE as dedispersed and lets its dededisperse() rotate them by
+        the ephemeris DM before unloading.  dedispersed=True raises
+        NotImplementedError (psrfits.load_data does not recognise
+        dedispersed files);
+      - npol 1 is written as AA+BB, npol 4 as IQUV ("Stokes") or AABBCRCI
+        ("Coherence"); other npol raise NotImplementedError.
+    Non-finite data raises ValueError before anything is launched."""
+    from . import fake, psrfits
+    if dedispersed:
+        raise NotImplementedError("dedispersed=True: psrfits.load_data does "
+                                  "not recognise dedispersed files")
+    if len(data.shape) != 4:
+        raise ValueError("data must be [nsub, npol, nchan, nbin]")
+    nsub, npol, nchan, nbin = (int(n) for n in data.shape)
+    pol_type = _pol_type(npol, state)
+    freqs = np.asarray(freqs, dtype=np.float64)
+    if freqs.shape not in ((nchan,), (nsub, nchan)):
+        raise ValueError("freqs must be [nchan] = [%d]" % nchan)
+    if nu0 is None:
+        nu0 = freqs.mean()
+    if bw is None:
+        if nchan < 2:
+            raise ValueError("bw must be given for a single channel")
+        f1 = freqs.reshape(-1, nchan)[0]
+        bw = (freqs.max() - freqs.min()) + abs(f1[1] - f1[0])
+    if weights is None:
+        weights = np.ones([nsub, nchan])
+    weights = np.asarray(weights, dtype=np.float64)
+    if weights.shape != (nsub, nchan):
+        raise ValueError("weights must be [nsub, nchan] = [%d, %d]"
+                         % (nsub, nchan))
+    psrfits.check_finite(data)
+    par = fake.read_par(ephemeris)
+    ep = fake.fake_epochs(par, nsub, tsub, start_MJD)
+    DECJ = par.DECJ if par.DECJ[0] in "+-" else "+" + par.DECJ
+    psrfits.write_archive_rows(
+        outfile, data, np.broadcast_to(freqs, (nsub, nchan)), weights, ep.Ps,
+        ep.offs_sub, np.full(nsub, float(tsub)), stt_imjd=ep.stt_imjd,
+        stt_smjd=ep.stt_smjd, stt_offs=ep.stt_offs, pol_type=pol_type,
+        telescope=telescope, source=par.PSR, dm=par.DM, obsfreq=float(nu0),
+        obsbw=float(bw), ra=par.RAJ, dec=DECJ, elem=elem, dev=dev)
+    if not quiet:
+        print("\nUnloaded %s.\n" % outfile)
+
+
+def unload_new_archive(data, arch, outfile, DM=None, dmc=0, weights=None,
+                       quiet=False, elem="I", dev=None):
+    """pplib.py:3146-3186 without PSRCHIVE: a copy of an archive with new
+    amplitudes.  arch stands in for the PSRCHIVE object: the name of a
+    fold-mode PSRFITS file, or a DataBunch from psrfits.load_data.
+    Telescope, frontend, backend, source, centre frequency, bandwidth,
+    channel frequencies, periods, epochs, sub-int lengths, parallactic
+    angles, weights and DM are copied from it; DM and weights ([nsub,
+    nchan]) override when given.  data: [nsub, npol, nchan, nbin] of arch's
+    shape (a DataBunch from load_data is total intensity: npol 1), a NumPy
+    array or a device tensor, digitised on the device
+    (psrfits.write_archive_rows; elem "I" or "E").
+
+    The data are stored as given, dededispersed (dmc = 0); dmc true raises
+    NotImplementedError (psrfits.load_data does not recognise dedispersed
+    files).  A shape that disagrees with arch and non-finite data raise
+    ValueError.  A DataBunch carries no coordinates: the RA / DEC cards are
+    copied only from a file."""
+    from . import psrfits
+    if dmc:
+        raise NotImplementedError("dmc=%r: psrfits.load_data does not "
+                                  "recognise dedispersed files" % (dmc,))
+    m = psrfits.archive_meta(arch) if isinstance(arch, str) else arch
+    shape = tuple(int(m[k]) for k in ("nsub", "npol", "nchan", "nbin"))
+    if len(data.shape) != 4 or tuple(int(n) for n in data.shape) != shape:
+        raise ValueError("data shape %s != the archive's %s"
+                         % (tuple(data.shape), shape))
+    nsub, npol, nchan, nbin = shape
+    pol_type = m.get("pol_type") or _pol_type(
+        npol, "Stokes" if m.get("state") in (None, "Intensity") else m["state"])
+    weights = np.asarray(m["weights"] if weights is None else weights,
+                         dtype=np.float64)
+    if weights.shape != (nsub, nchan):
+        raise ValueError("weights must be [nsub, nchan] = [%d, %d]"
+                         % (nsub, nchan))
+    psrfits.check_finite(data)
+    # the start of the first sub-int, whose epoch is its centre; OFFS_SUB
+    # counts from there to every centre
+    tsub = np.asarray(m["subtimes"], dtype=np.float64).reshape(nsub)
+    epochs = list(m["epochs"])
+    start = epochs[0] + (-tsub[0] / 2.0)
+    sec = start.fracday() * 86400.0
+    smjd = int(np.floor(sec))
+    offs_sub = np.array([((e.intday() - start.intday()) +
+                          (e.fracday() - start.fracday())) * 86400.0
+                         for e in epochs])
+    psrfits.write_archive_rows(
+        outfile, data, np.asarray(m["freqs"], dtype=np.float64), weights,
+        np.asarray(m["Ps"], dtype=np.float64), offs_sub, tsub,
+        stt_imjd=start.intday(), stt_smjd=smjd, stt_offs=sec - smjd,
+        pol_type=pol_type, telescope=m["telescope"], frontend=m["frontend"],
+        backend=m["backend"], source=m["source"],
+        dm=float(m["DM"] if DM is None else DM),
+        be_delay=float(m.get("backend_delay", 0.0)),
+        par_ang=m.get("parallactic_angles"), obsfreq=float(m["nu0"]),
+        obsbw=float(m["bw"]), ra=m.get("ra"), dec=m.get("dec"), elem=elem,
+        dev=dev)
+    if not quiet:
+        print("\nUnloaded %s.\n" % outfile)
+
+
 # ------------------------------------------------------------- TOA output --
 def filter_TOAs(TOAs, flag, cutoff, criterion=">=", pass_unflagged=False,
                 return_culled=False):

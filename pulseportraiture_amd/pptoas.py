@@ -346,6 +346,11 @@ def _response_table(ird, nbin):
                                              ird["irf_types"])
 
 
+class _SkipArchive(Exception):
+    """An archive template of another shape than the archive: the reference
+    prints a message and goes on to the next archive (pptoas.py:368-377)."""
+
+
 class GetTOAs(object):
     """pptoas.py:87-159."""
 
@@ -373,14 +378,18 @@ class GetTOAs(object):
         """Model portrait per sub-integration (pptoas.py:385-419): the
         .gmodel is parsed once (read_model, pplib.py:2971-3057) and every
         distinct (frequency set, TAU [bin]) portrait of the archive is built
-        in ONE ppf_gauss_portrait_batch launch (k_gauss_port)."""
-        if self.is_FITS_model:
-            raise NotImplementedError("FITS (archive) templates need PSRCHIVE")
+        in ONE ppf_gauss_portrait_batch launch (k_gauss_port).  An archive
+        template (pptoas.py:358-377) is the one portrait every sub-int
+        indexes (_archive_models, which raises _SkipArchive for an archive
+        the template does not fit)."""
         respond = self._response_on()
         if respond:
             # refusals (odd or long nbin, bad widths) before any device work
             table = _response_table(self.ird, len(d.phases))
-        models, index = self._base_models(d, ok_isubs, fit_scat, quiet)
+        if self.is_FITS_model:
+            models, index = self._archive_models(d, ok_isubs)
+        else:
+            models, index = self._base_models(d, ok_isubs, fit_scat, quiet)
         if respond and len(index):
             models, index = self._respond(d, ok_isubs, models, index, table)
         if host and isinstance(models, torch.Tensor):
@@ -428,6 +437,73 @@ class GetTOAs(object):
             np.concatenate(widths))
         return out.view(len(cache), nchan, nbin), \
             np.array(new_index, dtype=np.int32)
+
+    def _archive_template(self):
+        """The archive template of pptoas.py:362-367: load_data(modelfile,
+        tscrunch=True, pscrunch=True, rm_baseline=True) once per call, kept
+        beside the parsed .gmodel in _mcache as (its DataBunch, model =
+        masks * subints of sub-int 0: a float64 [nchan, nbin] portrait on
+        the device)."""
+        mc = self.__dict__.setdefault("_mcache", {})
+        if "fits" not in mc:
+            md = load_data(self.modelfile, dedisperse=False,
+                           dededisperse=False, tscrunch=True, pscrunch=True,
+                           fscrunch=False, rm_baseline=True, flux_prof=False,
+                           refresh_arch=False, return_arch=False, quiet=True)
+            mask = np.asarray(md.masks[0, 0], dtype=np.float64)
+            rows = getattr(md.subints, "device_rows", None)
+            if rows is not None:
+                # (finish() has waited for the loader's stream)
+                model = torch.as_tensor(mask, device=rows.device) * \
+                    rows[0].double()
+            else:
+                model = engine.to_dev(
+                    mask * np.asarray(md.subints[0, 0], dtype=np.float64),
+                    engine.device(), torch.float64)
+            mc["fits"] = (md, model.contiguous())
+        return mc["fits"]
+
+    def _archive_portrait(self, nchan):
+        """(template DataBunch, its portrait for nchan data channels, or None
+        when the channel counts disagree): a one-channel template is tiled
+        over the data's channels (pptoas.py:372-374).  The reference then
+        still compares the template's own channel count with the data's
+        (pptoas.py:375-377) and so skips every archive of more than one
+        channel; the tiled portrait is fitted here."""
+        md, model = self._archive_template()
+        if md.nchan == 1:
+            model = model[:1].expand(nchan, model.shape[1]).contiguous()
+        elif md.nchan != nchan:
+            model = None
+        return md, model
+
+    def _archive_models(self, d, ok_isubs):
+        """_base_models for an archive template (pptoas.py:358-377, 385-387):
+        one portrait, index 0 for every sub-int, used as it is with fit_scat
+        too (the reference rebuilds an unscattered model only from a
+        .gmodel).  Prints the reference's messages: the experimental-
+        functionality warning once per call, a bin or channel count that
+        disagrees (the archive is skipped: _SkipArchive), and the frequency
+        mismatch per sub-int."""
+        if not getattr(self, "_warned", False):
+            print("You are using an experimental functionality of pptoas!")
+            self._warned = True
+        name = getattr(self, "_datafile", None) or d.get("filename", "")
+        nchan, nbin = d.nchan, d.nbin
+        md, model = self._archive_portrait(nchan)
+        self.model_name = self.modelfile
+        if md.nbin != nbin:
+            print("Model nbin %d != data nbin %d for %s; skipping it."
+                  % (md.nbin, nbin, name))
+            raise _SkipArchive(name)
+        if model is None:
+            print("Model nchan %d != data nchan %d for %s; skipping it."
+                  % (md.nchan, nchan, name))
+            raise _SkipArchive(name)
+        for isub in ok_isubs:
+            if np.any(md.freqs[0] - d.freqs[isub]):        # tscrunched
+                print("Frequency mismatch between template and data!")
+        return model[None], np.zeros(len(ok_isubs), dtype=np.int32)
 
     def _base_models(self, d, ok_isubs, fit_scat, quiet):
         """_models before the instrumental response: device portraits (host
@@ -565,6 +641,7 @@ class GetTOAs(object):
         self.add_instrumental_response = add_instrumental_response
         self._ff = [None]   # fit_flags carried across sub-ints (pptoas.py:519-529)
         self._mcache = {}   # template portraits of this call (_models)
+        self._warned = already_warned     # (_archive_models: once per call)
         self._fit_ws = {}   # the fit worker's workspace (_fit_share)
         # With several ranks and at least as many archives as ranks, each
         # rank loads and fits only its own contiguous block of archives
@@ -815,8 +892,13 @@ class GetTOAs(object):
         # their generation on this thread's stream (models_ev)
         _sp = span("prep.models")
         _sp.__enter__()
-        models, model_index = self._models(d, ok_isubs, fit_scat, quiet,
-                                           host=False)
+        self._datafile = datafile           # (_archive_models' messages)
+        try:
+            models, model_index = self._models(d, ok_isubs, fit_scat, quiet,
+                                               host=False)
+        except _SkipArchive:
+            _sp.__exit__(None, None, None)
+            return None
         models_ev = None
         if isinstance(models, torch.Tensor) and models.is_cuda:
             models_ev = torch.cuda.Event()
@@ -1537,6 +1619,7 @@ class GetTOAs(object):
                                               self.ird["irf_types"])
         print("You are using an experimental functionality of pptoas!")
         self._mcache = {}   # template portraits of this call (_models)
+        self._warned = True
         self.nfit = 1
         self.fit_phi = True
         self.fit_tau = fit_scat
@@ -1600,11 +1683,26 @@ class GetTOAs(object):
             MJDs = np.array([d.epochs[isub].in_days() for isub in range(nsub)],
                             dtype=np.double)
             ok_isubs = list(d.ok_isubs)
-            models, model_index = self._models(d, ok_isubs, False, quiet)
+            self._datafile = datafile
+            try:
+                models, model_index = self._models(d, ok_isubs, False, quiet)
+            except _SkipArchive:
+                continue
+            # channels the archive template gives no weight are not fitted
+            # (pptoas.py:1041-1042, which indexes the tscrunched template's
+            # weights by the data's sub-int and so fails past sub-int 0;
+            # the template's one sub-int is meant)
+            mwts = None
+            if self.is_FITS_model:
+                mwts = np.asarray(self._archive_template()[0].weights)[0]
+                if len(mwts) == 1:
+                    mwts = np.repeat(mwts, nchan)
             # every (sub-int, usable channel) row of the archive
             rows_s, rows_c, midx = [], [], []
             for j, isub in enumerate(ok_isubs):
                 for ichan in d.ok_ichans[isub]:
+                    if mwts is not None and mwts[int(ichan)] == 0:
+                        continue
                     rows_s.append(isub)
                     rows_c.append(int(ichan))
                     midx.append(model_index[j] * nchan + int(ichan))
@@ -1731,8 +1829,6 @@ class GetTOAs(object):
         """The unscaled (scattered) model portrait of show_fit
         (pptoas.py:1415-1459) for one sub-integration.  Un-scattered models
         depend only on the channel frequencies and are cached per archive."""
-        if self.is_FITS_model:
-            raise NotImplementedError("FITS (archive) templates need PSRCHIVE")
         if not self._response_on():
             return self._plain_fit_model(data, ifile, isub, quiet, cache)
         # pptoas.py:1446-1452: the response of ALL the channels' freqs and
@@ -1765,6 +1861,8 @@ class GetTOAs(object):
         key = freqs.tobytes()
         if tau == 0.0 and cache is not None and key in cache:
             return cache[key]
+        if self.is_FITS_model:
+            return self._archive_fit_model(data, ifile, isub, cache)
         model_name, ngauss, model = read_model(
             self.modelfile, data.phases, freqs, data.Ps.mean(), quiet=quiet)
         if tau != 0.0:
@@ -1787,6 +1885,36 @@ class GetTOAs(object):
         elif cache is not None:
             cache[key] = (model_name, model)
         return model_name, model
+
+    def _archive_fit_model(self, data, ifile, isub, cache=None):
+        """_plain_fit_model for an archive template (pptoas.py:1420-1430,
+        1453-1459): the template's portrait (tiled from one channel), with the
+        fitted scattering kernel on it when tau != 0, on the host as the
+        reference does it."""
+        ckey = ("fits", data.nchan)
+        if cache is not None and ckey in cache:
+            model = cache[ckey]
+        else:
+            model = self._archive_portrait(data.nchan)[1]
+            if model is None:
+                raise ValueError("Model nchan %d != data nchan %d" % (
+                    self._archive_template()[0].nchan, data.nchan))
+            model = model.cpu().numpy()
+            if cache is not None:
+                cache[ckey] = model
+        tau = self.taus[ifile][isub]
+        if tau != 0.0:
+            if self.log10_tau:
+                tau = 10 ** tau
+            taus = _pplib.scattering_times(tau, self.alphas[ifile][isub],
+                                           data.freqs[isub],
+                                           self.nu_refs[ifile][isub][2])
+            model = np.fft.irfft(
+                _pplib.scattering_portrait_FT(taus, data.nbin) *
+                np.fft.rfft(model, axis=1), n=data.nbin, axis=1)
+        elif cache is not None:
+            cache[data.freqs[isub].tobytes()] = (self.modelfile, model)
+        return self.modelfile, model
 
     def _fit_phases(self, data, ifile, isub):
         """Per-channel rotation of show_fit's rotate_portrait_full call

@@ -15,8 +15,10 @@ ppf_noise_batch).  The archive's rows stay in HBM for the fit.
 This module is the FITS side: a minimal reader of the primary header and the
 SUBINT / POLYCO binary tables (FITS 4.0 standard: 2880-byte blocks, 80-byte
 header cards, big-endian binary tables), and a writer of the same subset
-(tests, bench).  Fold-mode (OBS_MODE PSR/CAL) archives only; search-mode
-data, FITS templates and PSRCHIVE's other formats stay with PSRCHIVE.
+(tests, bench, and pplib.write_archive / unload_new_archive through
+write_archive_rows, which digitises float rows on the device).  Fold-mode
+(OBS_MODE PSR/CAL) archives only; search-mode data and PSRCHIVE's other
+formats stay with PSRCHIVE.
 
 What is restated from PSRCHIVE's documented behaviour and NOT pinned to a
 PSRCHIVE run (PSRCHIVE is absent from this image and the reference holds no
@@ -485,6 +487,91 @@ def write_psrfits_rows(filename, data, scl, offs, freqs, weights, periods,
             fh.write(data[i])
         fh.write(b"\0" * (-(nsub * rowbytes) % BLOCK))
     return filename
+
+
+def archive_meta(filename):
+    """What pplib.unload_new_archive copies from an archive, read from the
+    file's headers and the SUBINT columns other than DATA (no device): a dict
+    with load_data's keys telescope, frontend, backend, source, DM, nu0, bw,
+    backend_delay, freqs [nsub, nchan], weights [nsub, nchan], Ps [nsub],
+    epochs (pplib.MJD per sub-int), subtimes [nsub], parallactic_angles
+    [nsub], nsub, npol, nchan, nbin, plus pol_type, ra and dec (None when the
+    primary header has no such card)."""
+    from . import pplib
+    f = PSRFITS(filename)
+    try:
+        p, h, t = f.primary, f.subint.header, f.subint
+        imjd, frac = f.epochs()
+        tsub = t.column("TSUBINT")[:, 0].astype(float) \
+            if t.has("TSUBINT") else np.zeros(f.nsub)
+        par = t.column("PAR_ANG")[:, 0].astype(float) \
+            if t.has("PAR_ANG") else np.zeros(f.nsub)
+        freqs = f.freqs()
+        return dict(
+            nsub=f.nsub, npol=f.npol, nchan=f.nchan, nbin=f.nbin,
+            pol_type=f.pol_type, telescope=str(p.get("TELESCOP", "")).strip(),
+            frontend=str(p.get("FRONTEND", "")).strip(),
+            backend=str(p.get("BACKEND", "")).strip(),
+            source=str(p.get("SRC_NAME", "")).strip(),
+            DM=float(h.get("DM", p.get("CHAN_DM", 0.0))),
+            nu0=float(p.get("OBSFREQ", freqs.mean())),
+            bw=float(p.get("OBSBW", 0.0)),
+            backend_delay=float(p.get("BE_DELAY", 0.0)),
+            ra=p.get("RA"), dec=p.get("DEC"), freqs=np.array(freqs),
+            weights=np.array(f.weights()), Ps=np.array(f.periods()),
+            epochs=[pplib.MJD(int(i), float(x)) for i, x in zip(imjd, frac)],
+            subtimes=list(tsub), parallactic_angles=par)
+    finally:
+        f.close()
+
+
+def check_finite(data):
+    """ValueError if data (a NumPy array or a torch tensor) holds a NaN or an
+    Inf: a profile's DAT_SCL / DAT_OFFS come from its minimum and maximum,
+    so one such sample would spoil its whole row."""
+    if hasattr(data, "detach"):                      # a torch tensor
+        import torch
+        ok = bool(torch.isfinite(data).all())
+    else:
+        ok = bool(np.isfinite(np.asarray(data, dtype=np.float64)).all())
+    if not ok:
+        raise ValueError("the data hold non-finite values (NaN or Inf)")
+
+
+def write_archive_rows(filename, data, freqs, weights, periods, offs_sub,
+                       tsubint, stt_imjd=56000, stt_smjd=0, stt_offs=0.0,
+                       pol_type="AA+BB", telescope="GBT", frontend="Rcvr1_2",
+                       backend="GUPPI", source="J1234+5678", dm=0.0,
+                       be_delay=0.0, par_ang=None, obsfreq=None, obsbw=None,
+                       ra=None, dec=None, elem="I", dev=None):
+    """write_psrfits_rows for float data: data [nsub, npol, nchan, nbin]
+    (float32 or float64, a NumPy array or a device tensor) is digitised on the
+    device (engine.pack_rows: elem "I", 16-bit samples with per-profile
+    DAT_SCL / DAT_OFFS as psrfits.quantize gives them, or "E", float32
+    samples), and only the file's DATA bytes come back to the host (through
+    the page-locked buffer of engine.dev_to_host_view).  The metadata
+    arguments are write_psrfits_rows'.  Non-finite data raises ValueError
+    before anything is launched."""
+    from . import engine
+    if elem not in ("I", "E"):
+        raise ValueError("elem must be 'I' or 'E'")
+    if len(data.shape) != 4:
+        raise ValueError("data must be [nsub, npol, nchan, nbin]")
+    nsub, npol, nchan, nbin = (int(n) for n in data.shape)
+    if np.asarray(freqs).shape != (nsub, nchan):
+        raise ValueError("freqs must be [nsub, nchan] = [%d, %d]"
+                         % (nsub, nchan))
+    check_finite(data)
+    raw, scl, offs = engine.pack_rows(data, elem=elem, dev=dev)
+    scl = engine.dev_to_host(scl).reshape(nsub, npol * nchan)
+    offs = engine.dev_to_host(offs).reshape(nsub, npol * nchan)
+    return write_psrfits_rows(
+        filename, engine.dev_to_host_view(raw.reshape(nsub, -1)), scl, offs,
+        freqs, weights, periods, offs_sub, tsubint, nbin, stt_imjd=stt_imjd,
+        stt_smjd=stt_smjd, stt_offs=stt_offs, npol=npol, pol_type=pol_type,
+        telescope=telescope, frontend=frontend, backend=backend,
+        source=source, dm=dm, be_delay=be_delay, par_ang=par_ang,
+        obsfreq=obsfreq, obsbw=obsbw, ra=ra, dec=dec, elem=elem)
 
 
 def quantize(rows, npol=1):
