@@ -50,7 +50,8 @@ extern "C" {
  * queries), ppf_align_phases, PPF_OPT_SPIN_WAIT; ppf_fit_batch /
  * ppf_gauss_portrait_batch / ppf_phase_shift_batch accept nbin past the LDS
  * transforms (even > 8192, odd > 4095) on the long transforms.
- * ppf_inst_response_batch and ppf_pack_psrfits_batch were added later without
+ * ppf_inst_response_batch, ppf_pack_psrfits_batch and
+ * ppf_unpack_psrfits_pol_batch were added later without
  * a bump (purely additive: no structure or existing signature changed). */
 #define PPF_ABI_VERSION 6
 
@@ -495,6 +496,40 @@ int ppf_unpack_psrfits_batch(ppf_ctx *ctx, int32_t nsub, int32_t npol, int32_t n
                              int32_t rm_baseline, float *out, double *stats, double *total,
                              int32_t *wstart, void *workspace, size_t workspace_bytes,
                              void *stream);
+
+/* ppf_unpack_psrfits_batch for all four polarisations of an npol = 4 file
+ * (added within ABI 6: purely additive): every sub-int block of raw holds
+ * [4][nchan][nbin] samples (elem as above; elem 3: native float32 rows, the
+ * statistics pass of a polarised load), scl / offs are [nsub][4*nchan].  Per
+ * sample the four values DATA * DAT_SCL + DAT_OFFS (float32, two roundings)
+ * are converted in float32, one rounded operation per output:
+ *   conv 0  keep (Stokes)            I, Q, U, V                 total = pol 0
+ *   conv 1  keep (Coherence)         AA, BB, CR, CI             pol 0 + pol 1
+ *   conv 2  Coherence -> Stokes LIN  AA+BB, AA-BB, 2CR, 2CI     pol 0
+ *   conv 3  Coherence -> Stokes CIRC AA+BB, 2CR, 2CI, AA-BB     pol 0
+ *   conv 4  Stokes -> Coherence LIN  (I+Q)/2, (I-Q)/2, U/2, V/2 pol 0 + pol 1
+ *   conv 5  Stokes -> Coherence CIRC (I+V)/2, (I-V)/2, Q/2, U/2 pol 0 + pol 1
+ * (PSRCHIVE's conventions as documented, not pinned to a PSRCHIVE run).
+ * out: [nsub][4][nchan][nbin]; the baseline window of a sub-int is found on
+ * the weighted total intensity (last column: formed in float32 from the
+ * output rows) exactly as ppf_unpack_psrfits_batch finds it, and applies to
+ * all four of its polarisations; stats: [nsub][4][nchan][3]; total, wstart,
+ * wts, rm_baseline, workspace (ppf_unpack_workspace_bytes(nsub, nchan, nbin))
+ * as there.  Rows with nbin % 4 == 0 whose raw, sub_stride, out and
+ * workspace are aligned for it take 4 bins per lane with 8-byte loads
+ * (16-bit samples; 4 / 16 bytes for 8-bit / float32) and 16-byte stores,
+ * every other shape element-wide accesses: the same bits either way.
+ * PPF_EINVAL, before any launch: a NULL ctx, nsub < 0, nchan < 1, nbin < 2,
+ * elem outside 0..3, conv outside 0..5, sub_stride below 4 nchan nbin
+ * elements, raw or sub_stride not multiples of the element size; then
+ * nsub == 0 returns PPF_OK; then a NULL array (PPF_EINVAL), a short
+ * workspace (PPF_ENOMEM). */
+int ppf_unpack_psrfits_pol_batch(ppf_ctx *ctx, int32_t nsub, int32_t nchan, int32_t nbin,
+                                 int32_t elem, const void *raw, int64_t sub_stride,
+                                 const float *scl, const float *offs, const float *wts,
+                                 int32_t conv, int32_t rm_baseline, float *out, double *stats,
+                                 double *total, int32_t *wstart, void *workspace,
+                                 size_t workspace_bytes, void *stream);
 
 /* The inverse of ppf_unpack_psrfits_batch (added within ABI 6: purely
  * additive, a library without the symbol is a stale build): float rows on

@@ -156,6 +156,11 @@ SIGNATURES = {
                                                 _vp, _vp, _vp, _i32, _i32,
                                                 _vp, _vp, _vp, _vp, _vp,
                                                 ctypes.c_size_t, _vp]),
+    "ppf_unpack_psrfits_pol_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32,
+                                                    _i32, _vp, ctypes.c_int64,
+                                                    _vp, _vp, _vp, _i32, _i32,
+                                                    _vp, _vp, _vp, _vp, _vp,
+                                                    ctypes.c_size_t, _vp]),
     "ppf_pack_psrfits_batch": (ctypes.c_int, [_vp, ctypes.c_int64, _i32, _i32,
                                               _vp, _i32, _vp, _vp, _vp, _vp]),
     "ppf_copy_from_pinned": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64,

@@ -1409,6 +1409,43 @@ int ppf_unpack_psrfits_batch(ppf_ctx *ctx, int32_t nsub, int32_t npol, int32_t n
     return PPF_OK;
 }
 
+int ppf_unpack_psrfits_pol_batch(ppf_ctx *ctx, int32_t nsub, int32_t nchan, int32_t nbin,
+                                 int32_t elem, const void *raw, int64_t sub_stride,
+                                 const float *scl, const float *offs, const float *wts,
+                                 int32_t conv, int32_t rm_baseline, float *out, double *stats,
+                                 double *total, int32_t *wstart, void *workspace,
+                                 size_t workspace_bytes, void *stream) {
+    if (!ctx) return PPF_EINVAL;
+    if (nsub < 0 || nchan < 1 || nbin < 2 || elem < 0 || elem > 3 || conv < 0 || conv > 5)
+        return fail(ctx, PPF_EINVAL, "bad unpack arguments (nchan=%d nbin=%d elem=%d conv=%d)",
+                    nchan, nbin, elem, conv);
+    const int64_t esize = elem == 0 ? 2 : (elem == 1 ? 1 : 4);
+    if (sub_stride < (int64_t)4 * nchan * nbin * esize)
+        return fail(ctx, PPF_EINVAL, "sub_stride %lld < the four polarisation blocks of a sub-int",
+                    (long long)sub_stride);
+    if (sub_stride % esize || (uintptr_t)raw % (uintptr_t)esize)
+        return fail(ctx, PPF_EINVAL, "raw and sub_stride must be multiples of the %lld-byte element",
+                    (long long)esize);
+    if (nsub == 0) return PPF_OK;
+    if (!raw || !scl || !offs || !out || !stats || !total || !wstart || !workspace)
+        return fail(ctx, PPF_EINVAL, "null unpack pointer");
+    if (workspace_bytes < ppf_unpack_workspace_bytes(nsub, nchan, nbin))
+        return fail(ctx, PPF_ENOMEM, "unpack workspace %zu < %zu", workspace_bytes,
+                    ppf_unpack_workspace_bytes(nsub, nchan, nbin));
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
+    ppf::UnpackArgs a{};
+    a.nsub = nsub; a.npol = 4; a.nchan = nchan; a.nbin = nbin; a.elem = elem;
+    a.rm_baseline = rm_baseline ? 1 : 0;
+    a.win = std::min(nbin - 1, std::max(1, (int)std::lrint(0.15 * nbin)));
+    a.raw = (const uint8_t *)raw; a.sub_stride = sub_stride;
+    a.scl = scl; a.offs = offs; a.wts = wts; a.out = out;
+    a.part = (double *)workspace; a.total = total; a.wstart = wstart; a.stats = stats;
+    if ((e = ppf::launch_unpack_pol(a, conv, (hipStream_t)stream)) != hipSuccess)
+        return hip_fail(ctx, e, "k_unpack_pol");
+    return PPF_OK;
+}
+
 int ppf_pack_psrfits_batch(ppf_ctx *ctx, int64_t nrow, int32_t nbin, int32_t in_dtype,
                            const void *rows, int32_t elem, void *raw, float *scl, float *offs,
                            void *stream) {

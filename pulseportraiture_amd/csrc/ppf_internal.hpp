@@ -378,6 +378,9 @@ struct UnpackArgs {
     double *stats;               // [nsub][nchan][3]: off mean, off sigma, S/N
 };
 hipError_t launch_unpack(const UnpackArgs &a, hipStream_t st);
+// full polarisation: npol = 4, out [nsub][4][nchan][nbin], stats
+// [nsub][4][nchan][3]; conv 0..5 (include/ppfit.h); pol_mode is not read
+hipError_t launch_unpack_pol(const UnpackArgs &a, int conv, hipStream_t st);
 hipError_t launch_copy_host(const void *src_dev, void *dst, int64_t nbytes, hipStream_t st);
 size_t unpack_partials(int nsub, int nchan, int nbin);
 

@@ -801,6 +801,41 @@ def unpack_psrfits(raw, elem, npol, nchan, nbin, scl, offs, wts=None,
                 _keep=(scl_t, offs_t, wts_t, ws, raw))
 
 
+def unpack_psrfits_pol(raw, elem, nchan, nbin, scl, offs, wts=None, conv=0,
+                       rm_baseline=True, dev=None):
+    """ppf_unpack_psrfits_pol_batch: raw DATA bytes [nsub, >= 4 nchan nbin
+    esize] of a four-polarisation file (device uint8 tensor, one row per
+    sub-int) -> dict(rows float32 [nsub, 4, nchan, nbin] in the state conv
+    asks for (0 / 1: as stored, Stokes / Coherence; 2 / 3: Coherence ->
+    Stokes for linear / circular feeds; 4 / 5: Stokes -> Coherence), stats
+    float64 [nsub, 4, nchan, 3] (off-pulse mean, sigma, S/N; the window of
+    the sub-int's total intensity), total float64 [nsub, nbin], wstart int32
+    [nsub]), all on the device."""
+    dev = device(dev)
+    nsub = raw.shape[0]
+    f32 = torch.float32
+    scl_t = to_dev(scl, dev, f32).reshape(nsub, 4 * nchan).contiguous()
+    offs_t = to_dev(offs, dev, f32).reshape(nsub, 4 * nchan).contiguous()
+    wts_t = None if wts is None else \
+        to_dev(wts, dev, f32).reshape(nsub, nchan).contiguous()
+    rows = torch.empty((nsub, 4, nchan, nbin), dtype=f32, device=dev)
+    stats = torch.empty((nsub, 4, nchan, 3), dtype=torch.float64, device=dev)
+    total = torch.empty((nsub, nbin), dtype=torch.float64, device=dev)
+    wstart = torch.empty(nsub, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    wsb = int(lib.ppf_unpack_workspace_bytes(nsub, nchan, nbin))
+    ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
+    ctx = _lib.context(dev.index)
+    rc = lib.ppf_unpack_psrfits_pol_batch(
+        ctx, nsub, nchan, nbin, int(elem), _p(raw), int(raw.stride(0)),
+        _p(scl_t), _p(offs_t), None if wts_t is None else _p(wts_t),
+        int(conv), int(bool(rm_baseline)), _p(rows), _p(stats), _p(total),
+        _p(wstart), _p(ws), wsb, _stream(dev))
+    _lib.check(rc, ctx)
+    return dict(rows=rows, stats=stats, total=total, wstart=wstart,
+                _keep=(scl_t, offs_t, wts_t, ws, raw))
+
+
 def pack_rows(rows, elem="I", dev=None):
     """ppf_pack_psrfits_batch, the inverse of unpack_psrfits: float rows ->
     (raw, scl, offs), all on the device.  rows: a NumPy array or a device

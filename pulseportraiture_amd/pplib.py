@@ -1121,7 +1121,8 @@ def _pol_type(npol, state):
 def write_archive(data, ephemeris, freqs, nu0=None, bw=None,
                   outfile="pparchive.fits", tsub=1.0, start_MJD=None,
                   weights=None, dedispersed=False, state="Stokes",
-                  telescope="GBT", quiet=False, elem="I", dev=None):
+                  telescope="GBT", quiet=False, elem="I", dev=None,
+                  fd_poln=None):
     """pplib.py:3189-3299 without PSRCHIVE: data [nsub, npol, nchan, nbin]
     (a NumPy array or a device tensor) becomes one fold-mode PSRFITS file.
     The samples are digitised on the device (psrfits.write_archive_rows,
@@ -1130,7 +1131,9 @@ def write_archive(data, ephemeris, freqs, nu0=None, bw=None,
     The arguments are the reference's, with its defaults for nu0 (the mean
     of freqs) and bw (the span of freqs plus one channel spacing), plus elem
     ("I": 16-bit samples with per-profile DAT_SCL / DAT_OFFS, "E": float32
-    samples) and dev.  freqs: [nchan], or [nsub, nchan].  Departures:
+    samples), dev and fd_poln (the feed basis, "LIN" or "CIRC": the FD_POLN
+    card, written only when given).  freqs: [nchan], or [nsub, nchan].
+    Departures:
       - the ephemeris, the epochs and the folding periods are
         make_fake_pulsar's (fake.read_par, fake.fake_epochs): start_MJD
         defaults to PEPOCH, and sub-int i is centred tsub / 2 + i tsub
@@ -1176,21 +1179,25 @@ def write_archive(data, ephemeris, freqs, nu0=None, bw=None,
         ep.offs_sub, np.full(nsub, float(tsub)), stt_imjd=ep.stt_imjd,
         stt_smjd=ep.stt_smjd, stt_offs=ep.stt_offs, pol_type=pol_type,
         telescope=telescope, source=par.PSR, dm=par.DM, obsfreq=float(nu0),
-        obsbw=float(bw), ra=par.RAJ, dec=DECJ, elem=elem, dev=dev)
+        obsbw=float(bw), ra=par.RAJ, dec=DECJ, elem=elem, dev=dev,
+        fd_poln=fd_poln)
     if not quiet:
         print("\nUnloaded %s.\n" % outfile)
 
 
 def unload_new_archive(data, arch, outfile, DM=None, dmc=0, weights=None,
-                       quiet=False, elem="I", dev=None):
+                       quiet=False, elem="I", dev=None, fd_poln=None):
     """pplib.py:3146-3186 without PSRCHIVE: a copy of an archive with new
     amplitudes.  arch stands in for the PSRCHIVE object: the name of a
     fold-mode PSRFITS file, or a DataBunch from psrfits.load_data.
     Telescope, frontend, backend, source, centre frequency, bandwidth,
     channel frequencies, periods, epochs, sub-int lengths, parallactic
     angles, weights and DM are copied from it; DM and weights ([nsub,
-    nchan]) override when given.  data: [nsub, npol, nchan, nbin] of arch's
-    shape (a DataBunch from load_data is total intensity: npol 1), a NumPy
+    nchan]) override when given.  The feed basis (the FD_POLN card) is
+    written when fd_poln is given or arch's is CIRC (LIN, what a file
+    without the card reads as, writes none).  data: [nsub,
+    npol, nchan, nbin] of arch's shape (a DataBunch from load_data is total
+    intensity, npol 1, or a polarised load's npol 4 in its state), a NumPy
     array or a device tensor, digitised on the device
     (psrfits.write_archive_rows; elem "I" or "E").
 
@@ -1216,6 +1223,8 @@ def unload_new_archive(data, arch, outfile, DM=None, dmc=0, weights=None,
     if weights.shape != (nsub, nchan):
         raise ValueError("weights must be [nsub, nchan] = [%d, %d]"
                          % (nsub, nchan))
+    if fd_poln is None and m.get("fd_poln") == "CIRC":
+        fd_poln = "CIRC"
     psrfits.check_finite(data)
     # the start of the first sub-int, whose epoch is its centre; OFFS_SUB
     # counts from there to every centre
@@ -1237,7 +1246,7 @@ def unload_new_archive(data, arch, outfile, DM=None, dmc=0, weights=None,
         be_delay=float(m.get("backend_delay", 0.0)),
         par_ang=m.get("parallactic_angles"), obsfreq=float(m["nu0"]),
         obsbw=float(m["bw"]), ra=m.get("ra"), dec=m.get("dec"), elem=elem,
-        dev=dev)
+        dev=dev, fd_poln=fd_poln)
     if not quiet:
         print("\nUnloaded %s.\n" % outfile)
 

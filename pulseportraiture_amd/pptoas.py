@@ -452,7 +452,7 @@ class GetTOAs(object):
                            refresh_arch=False, return_arch=False, quiet=True)
             mask = np.asarray(md.masks[0, 0], dtype=np.float64)
             rows = getattr(md.subints, "device_rows", None)
-            if rows is not None:
+            if rows is not None and rows.dim() == 3:
                 # (finish() has waited for the loader's stream)
                 model = torch.as_tensor(mask, device=rows.device) * \
                     rows[0].double()
@@ -919,7 +919,10 @@ class GetTOAs(object):
         first, count = _dist.shard(nok, rank, world)
         sel = ok_isubs[first:first + count]
         dev_rows = getattr(d.subints, "device_rows", None)
-        if dev_rows is not None:
+        # (a polarised bunch's device rows are [nsub, 4, nchan, nbin]: such a
+        # bunch takes the host route, pol 0)
+        if dev_rows is not None and dev_rows.dim() == 3 and \
+                getattr(d, "npol", 1) == 1:
             # PSRFITS fast path: the rows were unpacked on the device by
             # load_data (psrfits.load_data); no host copy, no second upload
             staged = _OnDevice(dev_rows, d.subints.event, sel, nchan, nbin)

@@ -34,7 +34,13 @@ PSRFITS fixture):
     over a window of 15 % of the turn on the total profile of the sub-int,
     subtracted from every channel);
   * S/N per channel: the baseline-subtracted profile's sum over the
-    on-pulse bins (outside the baseline window) / (sigma_off sqrt(n_on)).
+    on-pulse bins (outside the baseline window) / (sigma_off sqrt(n_on));
+  * full polarisation (npol = 4 files, load_data(pscrunch=False)): the
+    conversion between the coherency products AA BB CR CI and the Stokes
+    parameters (linear feeds: I = AA + BB, Q = AA - BB, U = 2 CR, V = 2 CI;
+    circular feeds: Q = 2 CR, U = 2 CI, V = AA - BB), the feed basis from
+    the primary header's FD_POLN card, LIN when it is absent, and the
+    baseline window of the total intensity applied to all four.
 """
 import mmap
 import os
@@ -189,6 +195,10 @@ class PSRFITS(object):
         self.nsub = self.subint.nrows
         self.pol_type = str(h.get("POL_TYPE", "AA+BB" if self.npol == 1
                                   else "AABBCRCI")).strip()
+        # the feed basis (primary header FD_POLN): LIN or CIRC; LIN when the
+        # card is absent
+        fd = str(self.primary.get("FD_POLN", "LIN")).strip().upper()
+        self.fd_poln = "CIRC" if fd.startswith("CIRC") else "LIN"
 
     def close(self):
         try:
@@ -364,6 +374,66 @@ def unpack_host(raw, dtype, scl, offs, npol, nchan, nbin):
     return v[:, 0] if npol == 1 else v[:, 0] + v[:, 1]
 
 
+# ppf_unpack_psrfits_pol_batch's conv for (the file's state, the state asked
+# for, FD_POLN); None keeps the file's state
+STATE_OF_POL_TYPE = {"IQUV": "Stokes", "AABBCRCI": "Coherence"}
+
+
+def pol_conv(file_state, state, fd_poln="LIN"):
+    """conv of engine.unpack_psrfits_pol: 0 / 1 keep Stokes / Coherence, 2 / 3
+    Coherence -> Stokes for linear / circular feeds, 4 / 5 Stokes ->
+    Coherence."""
+    circ = int(str(fd_poln).upper().startswith("CIRC"))
+    if state in (None, file_state):
+        return 0 if file_state == "Stokes" else 1
+    return (2 if state == "Stokes" else 4) + circ
+
+
+def unpack_host_pol(raw, dtype, scl, offs, nchan, nbin, conv):
+    """NumPy restatement of the device's full-polarisation unpack
+    (k_unpack_pol; tests): the four polarisations' float32 DATA * DAT_SCL +
+    DAT_OFFS (two roundings, as unpack_host), then the state conversion in
+    float32, one rounded operation per output, in the kernel's order:
+      conv 0, 1  as stored (I Q U V; AA BB CR CI)
+      conv 2     AA+BB, AA-BB, 2 CR, 2 CI        (Coherence -> Stokes, LIN)
+      conv 3     AA+BB, 2 CR, 2 CI, AA-BB        (... CIRC)
+      conv 4     (I+Q)/2, (I-Q)/2, U/2, V/2      (Stokes -> Coherence, LIN)
+      conv 5     (I+V)/2, (I-V)/2, Q/2, U/2      (... CIRC)
+    raw: [nsub, 4 * nchan * nbin] file bytes (dtype "<f4": native rows);
+    returns float32 [nsub, 4, nchan, nbin]."""
+    if conv not in range(6):
+        raise ValueError("conv must be 0..5")
+    nsub = raw.shape[0]
+    x = np.ascontiguousarray(raw).view(dtype).reshape(nsub, 4, nchan, nbin)
+    x = x.astype(np.float32)
+    s = scl.reshape(nsub, 4, nchan, 1).astype(np.float32)
+    o = offs.reshape(nsub, 4, nchan, 1).astype(np.float32)
+    v = (x * s).astype(np.float32) + o
+    two, half = np.float32(2.0), np.float32(0.5)
+    if conv in (0, 1):
+        out = [v[:, 0], v[:, 1], v[:, 2], v[:, 3]]
+    elif conv == 2:
+        out = [v[:, 0] + v[:, 1], v[:, 0] - v[:, 1], two * v[:, 2],
+               two * v[:, 3]]
+    elif conv == 3:
+        out = [v[:, 0] + v[:, 1], two * v[:, 2], two * v[:, 3],
+               v[:, 0] - v[:, 1]]
+    elif conv == 4:
+        out = [half * (v[:, 0] + v[:, 1]), half * (v[:, 0] - v[:, 1]),
+               half * v[:, 2], half * v[:, 3]]
+    else:
+        out = [half * (v[:, 0] + v[:, 3]), half * (v[:, 0] - v[:, 3]),
+               half * v[:, 1], half * v[:, 2]]
+    return np.stack(out, axis=1).astype(np.float32)
+
+
+def total_intensity_host(rows, conv):
+    """The total intensity the baseline window of a polarised unpack is
+    found on: pol 0 of rows [nsub, 4, nchan, nbin] (Stokes outputs: conv 0,
+    2, 3), else pol 0 + pol 1 in float32 (Coherence outputs)."""
+    return rows[:, 0] + rows[:, 1] if conv in (1, 4, 5) else rows[:, 0]
+
+
 # ------------------------------------------------------------------ writer --
 def _card(key, value, comment=""):
     if isinstance(value, bool):
@@ -390,7 +460,7 @@ def write_psrfits(filename, data, scl, offs, freqs, weights, periods,
                   offs_sub, tsubint, stt_imjd=56000, stt_smjd=0, stt_offs=0.0,
                   npol=1, pol_type="AA+BB", telescope="GBT", frontend="Rcvr1_2",
                   backend="GUPPI", source="J1234+5678", dm=0.0, be_delay=0.0,
-                  par_ang=None):
+                  par_ang=None, fd_poln=None):
     """Write a minimal fold-mode PSRFITS file (primary header + SUBINT
     binary table).  data: int16 [nsub, npol, nchan, nbin]; scl, offs:
     float32 [nsub, npol * nchan]; freqs, weights: [nsub, nchan]; periods,
@@ -404,7 +474,7 @@ def write_psrfits(filename, data, scl, offs, freqs, weights, periods,
         nbin, stt_imjd=stt_imjd, stt_smjd=stt_smjd, stt_offs=stt_offs,
         npol=npol, pol_type=pol_type, telescope=telescope, frontend=frontend,
         backend=backend, source=source, dm=dm, be_delay=be_delay,
-        par_ang=par_ang)
+        par_ang=par_ang, fd_poln=fd_poln)
 
 
 def write_psrfits_rows(filename, data, scl, offs, freqs, weights, periods,
@@ -412,7 +482,7 @@ def write_psrfits_rows(filename, data, scl, offs, freqs, weights, periods,
                        stt_offs=0.0, npol=1, pol_type="AA+BB", telescope="GBT",
                        frontend="Rcvr1_2", backend="GUPPI", source="J1234+5678",
                        dm=0.0, be_delay=0.0, par_ang=None, obsfreq=None,
-                       obsbw=None, ra=None, dec=None, elem="I"):
+                       obsbw=None, ra=None, dec=None, elem="I", fd_poln=None):
     """write_psrfits for DATA rows already in file byte order (the output of
     engine.fake_subints(quantized=True)): data is a uint8 array [nsub, npol *
     nchan * nbin * 2] of big-endian int16 in the DATA layout [npol][nchan]
@@ -420,7 +490,9 @@ def write_psrfits_rows(filename, data, scl, offs, freqs, weights, periods,
     host.  obsfreq / obsbw (default: the mean of freqs[0] and the channel
     spacing times nchan) and the RA / DEC cards can be given.  elem: the
     FITS sample type of DATA, "I" (big-endian int16), "B" (uint8: 1 byte
-    per sample) or "E" (big-endian float32: 4)."""
+    per sample) or "E" (big-endian float32: 4).  fd_poln: the feed basis,
+    "LIN" or "CIRC", written as the primary header's FD_POLN card when given
+    (a file without the card reads as LIN)."""
     data = np.asarray(data)
     freqs = np.asarray(freqs, dtype=float)
     nsub, nchan = freqs.shape
@@ -460,6 +532,10 @@ def write_psrfits_rows(filename, data, scl, offs, freqs, weights, periods,
             ("HDRVER", "6.1"), ("FITSTYPE", "PSRFITS"), ("OBS_MODE", "PSR"),
             ("TELESCOP", telescope), ("FRONTEND", frontend),
             ("BACKEND", backend), ("SRC_NAME", source)]
+    if fd_poln is not None:
+        if fd_poln not in ("LIN", "CIRC"):
+            raise ValueError("fd_poln must be 'LIN' or 'CIRC'")
+        prim.append(("FD_POLN", fd_poln))
     if ra is not None:
         prim.append(("RA", ra))
     if dec is not None:
@@ -495,8 +571,9 @@ def archive_meta(filename):
     with load_data's keys telescope, frontend, backend, source, DM, nu0, bw,
     backend_delay, freqs [nsub, nchan], weights [nsub, nchan], Ps [nsub],
     epochs (pplib.MJD per sub-int), subtimes [nsub], parallactic_angles
-    [nsub], nsub, npol, nchan, nbin, plus pol_type, ra and dec (None when the
-    primary header has no such card)."""
+    [nsub], nsub, npol, nchan, nbin, plus pol_type, fd_poln (LIN when the
+    file has no FD_POLN card), ra and dec (None when the primary header has
+    no such card)."""
     from . import pplib
     f = PSRFITS(filename)
     try:
@@ -509,7 +586,8 @@ def archive_meta(filename):
         freqs = f.freqs()
         return dict(
             nsub=f.nsub, npol=f.npol, nchan=f.nchan, nbin=f.nbin,
-            pol_type=f.pol_type, telescope=str(p.get("TELESCOP", "")).strip(),
+            pol_type=f.pol_type, fd_poln=f.fd_poln,
+            telescope=str(p.get("TELESCOP", "")).strip(),
             frontend=str(p.get("FRONTEND", "")).strip(),
             backend=str(p.get("BACKEND", "")).strip(),
             source=str(p.get("SRC_NAME", "")).strip(),
@@ -543,7 +621,7 @@ def write_archive_rows(filename, data, freqs, weights, periods, offs_sub,
                        pol_type="AA+BB", telescope="GBT", frontend="Rcvr1_2",
                        backend="GUPPI", source="J1234+5678", dm=0.0,
                        be_delay=0.0, par_ang=None, obsfreq=None, obsbw=None,
-                       ra=None, dec=None, elem="I", dev=None):
+                       ra=None, dec=None, elem="I", dev=None, fd_poln=None):
     """write_psrfits_rows for float data: data [nsub, npol, nchan, nbin]
     (float32 or float64, a NumPy array or a device tensor) is digitised on the
     device (engine.pack_rows: elem "I", 16-bit samples with per-profile
@@ -571,7 +649,8 @@ def write_archive_rows(filename, data, freqs, weights, periods, offs_sub,
         stt_smjd=stt_smjd, stt_offs=stt_offs, npol=npol, pol_type=pol_type,
         telescope=telescope, frontend=frontend, backend=backend,
         source=source, dm=dm, be_delay=be_delay, par_ang=par_ang,
-        obsfreq=obsfreq, obsbw=obsbw, ra=ra, dec=dec, elem=elem)
+        obsfreq=obsfreq, obsbw=obsbw, ra=ra, dec=dec, elem=elem,
+        fd_poln=fd_poln)
 
 
 def quantize(rows, npol=1):
@@ -627,13 +706,18 @@ def _window_snr(prof, frac=0.15):
 class DeviceRows(object):
     """load_data's `subints` on the fast path: the float32 rows live in HBM
     ([nsub, nchan, nbin], `.device_rows`); host code that indexes it or
-    takes np.asarray gets [nsub, 1, nchan, nbin] (copied back once)."""
+    takes np.asarray gets [nsub, 1, nchan, nbin] (copied back once).  A
+    polarised load's rows are [nsub, 4, nchan, nbin] on the device and on
+    the host alike."""
 
     def __init__(self, rows, event):
         self.device_rows, self.event = rows, event
         self._host = None
-        n, c, b = rows.shape
-        self.shape = (n, 1, c, b)
+        if rows.dim() == 3:
+            n, c, b = rows.shape
+            self.shape = (n, 1, c, b)
+        else:
+            self.shape = tuple(int(v) for v in rows.shape)
         self.dtype = np.float32
         self.ndim = 4
 
@@ -641,7 +725,8 @@ class DeviceRows(object):
         if self._host is None:
             if self.event is not None:
                 self.event.synchronize()
-            self._host = self.device_rows.cpu().numpy()[:, None]
+            h = self.device_rows.cpu().numpy()
+            self._host = h[:, None] if h.ndim == 3 else h
         return self._host
 
     def __array__(self, dtype=None, copy=None):
@@ -660,21 +745,25 @@ class _Masks(object):
     without materialising nsub nchan nbin doubles per archive (537 MB at
     64 x 512 x 2048): indexing builds only the rows asked for."""
 
-    def __init__(self, weights_norm, nbin):
-        self.wn, self.nbin = weights_norm, nbin
-        self.shape = (weights_norm.shape[0], 1, weights_norm.shape[1], nbin)
+    def __init__(self, weights_norm, nbin, npol=1):
+        self.wn, self.nbin, self.npol = weights_norm, nbin, npol
+        self.shape = (weights_norm.shape[0], npol, weights_norm.shape[1],
+                      nbin)
         self.ndim = 4
 
     def _full(self):
-        return np.einsum("ij,k", self.wn, np.ones(self.nbin))[:, None]
+        a = np.einsum("ij,k", self.wn, np.ones(self.nbin))[:, None]
+        return a if self.npol == 1 else np.repeat(a, self.npol, axis=1)
 
     def __array__(self, dtype=None, copy=None):
         a = self._full()
         return a if dtype is None else a.astype(dtype)
 
     def __getitem__(self, idx):
+        # (the mask of a channel is the same in every polarisation)
         if isinstance(idx, tuple) and len(idx) == 2 and \
-                np.isscalar(idx[0]) and idx[1] == 0:
+                np.isscalar(idx[0]) and np.isscalar(idx[1]) and \
+                0 <= idx[1] < self.npol:
             return np.repeat(self.wn[idx[0]][:, None], self.nbin, axis=1)
         return self._full()[idx]
 
@@ -711,8 +800,25 @@ def load_data(filename, state=None, dedisperse=False, dededisperse=False,
     dispersion constant, epoch and period conventions) is unpinned here:
     PSRCHIVE is absent and the reference holds no PSRFITS fixture.  A file
     whose data are already dedispersed is not recognised (dmc = 0 on load);
-    dededisperse is a no-op.  fscrunch and other polarisation states raise
-    NotImplementedError.
+    dededisperse is a no-op.  fscrunch raises NotImplementedError.
+
+    Full polarisation: a file of npol = 4 (POL_TYPE IQUV or AABBCRCI) loaded
+    with pscrunch false and state None, "Stokes" or "Coherence" keeps its
+    four polarisations (ppf_unpack_psrfits_pol_batch; all four blocks are
+    uploaded).  state None keeps the file's state; otherwise the coherency
+    products and the Stokes parameters are converted into one another on the
+    device, by the feed basis of the primary header's FD_POLN card (LIN, also
+    when absent, or CIRC).  npol = 4, state, fd_poln; subints and masks
+    [nsub, 4, nchan, nbin]; noise_stds and SNRs [nsub, 4, nchan]; the
+    baseline window of a sub-int is that of its total intensity, for all
+    four; prof, prof_SNR and prof_noise are the total intensity's.
+    dedisperse and tscrunch act on every polarisation alike.  pscrunch=True
+    (it overrides state) and state="Intensity" give total intensity as
+    before.  A polarised state asked of an npol = 1 file raises IndexError
+    (the reference's convert_state failure, which ppalign catches); npol = 2
+    files and other POL_TYPEs of npol = 4 raise NotImplementedError.  The
+    conversion conventions are PSRCHIVE's as documented, not pinned to a
+    PSRCHIVE run.
 
     defer=True returns a _Pending whose finish() gives the DataBunch: the
     read is done and the device work queued, but nothing waits for the
@@ -724,7 +830,7 @@ def load_data(filename, state=None, dedisperse=False, dededisperse=False,
     if fscrunch:
         raise NotImplementedError("load_data(fscrunch) needs PSRCHIVE; the "
                                   "PSRFITS fast path keeps every channel")
-    if state not in (None, "Intensity"):
+    if state not in (None, "Intensity", "Stokes", "Coherence"):
         raise NotImplementedError("state=%r needs PSRCHIVE" % state)
     pend = _Pending(filename, pscrunch, state, rm_baseline, quiet, dev,
                     dedisperse=bool(dedisperse), tscrunch=bool(tscrunch))
@@ -819,11 +925,32 @@ class _Pending(object):
         with span("load.open"):
             f = self.f = PSRFITS(filename)
             nsub, npol, nchan, nbin = f.nsub, f.npol, f.nchan, f.nbin
-            if npol > 1 and not (pscrunch or state == "Intensity"):
-                raise NotImplementedError("the PSRFITS fast path returns total "
-                                          "intensity (pscrunch=True) only")
             pt = f.pol_type.upper()
-            if npol == 1 or pt.startswith("IQUV") or pt == "INTEN":
+            # full polarisation: exactly an npol = 4 file, not pscrunched
+            pol = npol == 4 and not pscrunch and state != "Intensity"
+            self.conv = None
+            if pol:
+                fstate = STATE_OF_POL_TYPE.get(pt)
+                if fstate is None:
+                    raise NotImplementedError(
+                        "POL_TYPE %s with npol = 4: IQUV and AABBCRCI files "
+                        "load polarised" % f.pol_type)
+                self.conv = pol_conv(fstate, state, f.fd_poln)
+                self.state = fstate if state is None else state
+            elif state in ("Stokes", "Coherence") and npol == 1 and \
+                    not pscrunch:
+                raise IndexError("%s has npol = 1: no state %s"
+                                 % (filename, state))
+            elif state in ("Stokes", "Coherence") and npol != 4:
+                raise NotImplementedError("state=%r needs PSRCHIVE" % state)
+            elif npol > 1 and not (pscrunch or state == "Intensity"):
+                raise NotImplementedError("the PSRFITS fast path returns total "
+                                          "intensity (pscrunch=True), or all "
+                                          "four polarisations of an npol = 4 "
+                                          "file")
+            if pol:
+                pol_mode = 0                              # (not read)
+            elif npol == 1 or pt.startswith("IQUV") or pt == "INTEN":
                 pol_mode = 0
             elif pt.startswith("AABB") or pt.startswith("AA+BB"):
                 pol_mode = 1
@@ -837,7 +964,9 @@ class _Pending(object):
             # only the polarisations total intensity needs cross PCIe: DATA
             # is [npol][nchan][nbin] per sub-int, so AA and BB are its first
             # two npol blocks (2 B / sample / pol for 16-bit data)
-            nbytes = (2 if pol_mode == 1 else 1) * nchan * nbin * edt.itemsize
+            # (a polarised load takes all four)
+            nbytes = (4 if pol else 2 if pol_mode == 1 else 1) * nchan * \
+                nbin * edt.itemsize
             scl, offs = f.scales_offsets()
             self.weights = f.weights()
             dev = engine.device(dev)
@@ -967,14 +1096,24 @@ class _Pending(object):
                     st.wait_event(up)
                     # with dedisperse the baseline is removed after the
                     # rotation (pplib.py:2786-2791)
-                    out = engine.unpack_psrfits(
-                        raw_d, elem, npol, nchan, nbin, aux_d[:nsc],
-                        aux_d[nsc:2 * nsc], wts=aux_d[2 * nsc:],
-                        pol_mode=pol_mode,
-                        rm_baseline=rm_baseline and not dedisperse, dev=dev)
+                    if self.conv is not None:
+                        out = engine.unpack_psrfits_pol(
+                            raw_d, elem, nchan, nbin, aux_d[:nsc],
+                            aux_d[nsc:2 * nsc], wts=aux_d[2 * nsc:],
+                            conv=self.conv,
+                            rm_baseline=rm_baseline and not dedisperse,
+                            dev=dev)
+                    else:
+                        out = engine.unpack_psrfits(
+                            raw_d, elem, npol, nchan, nbin, aux_d[:nsc],
+                            aux_d[nsc:2 * nsc], wts=aux_d[2 * nsc:],
+                            pol_mode=pol_mode,
+                            rm_baseline=rm_baseline and not dedisperse,
+                            dev=dev)
                     if dedisperse or tscrunch:
-                        out = self._transform(out, aux_d[2 * nsc:],
-                                              rm_baseline, f, dev)
+                        tr = self._transform if self.conv is None else \
+                            self._transform_pol
+                        out = tr(out, aux_d[2 * nsc:], rm_baseline, f, dev)
                     noise = engine.noise_rows(out["rows"], dev=dev)
                     # one download: stats [nsub, nchan, 3], total [nsub,
                     # nbin], noise [nsub, nchan] (all float64)
@@ -1053,6 +1192,54 @@ class _Pending(object):
                         wsum.float()[None].contiguous(), False)
         return out
 
+    def _transform_pol(self, out, wts, rm_baseline, f, dev):
+        """_transform for the four polarisations of a polarised load: every
+        polarisation of a channel rotated by the channel's phase, tscrunched
+        by the same weights; the statistics pass keeps the state (native
+        rows through ppf_unpack_psrfits_pol_batch, elem 3, conv 0 or 1)."""
+        import torch
+        from . import engine, pplib
+        nsub, nchan, nbin = f.nsub, f.nchan, f.nbin
+        rows = out["rows"]                        # [nsub, 4, nchan, nbin]
+        keep = 0 if self.state == "Stokes" else 1
+        ones = torch.ones((nsub, 4 * nchan), dtype=torch.float32, device=dev)
+        zeros = torch.zeros((nsub, 4 * nchan), dtype=torch.float32,
+                            device=dev)
+
+        def stats(rows, w, rm):
+            n = rows.shape[0]
+            return engine.unpack_psrfits_pol(
+                rows.reshape(n, 4 * nchan * nbin).view(torch.uint8), 3, nchan,
+                nbin, ones[:n], zeros[:n], wts=w, conv=keep, rm_baseline=rm,
+                dev=dev)
+        if self.dedisperse:
+            p, h = f.primary, f.subint.header
+            DM = float(h.get("DM", p.get("CHAN_DM", 0.0)))
+            nu0 = float(p.get("OBSFREQ", self.freqs.mean()))
+            D = pplib.Dconst * DM / (np.ones(nsub) * self.Ps)
+            ph = D[:, None] * (self.freqs ** -2.0 - nu0 ** -2.0)
+            ph = np.repeat(ph[:, None, :], 4, axis=1)
+            rows = engine.rotate_rows(rows, ph, dev=dev).float()
+            out = stats(rows, wts, rm_baseline)
+            rows = out["rows"]
+        if self.tscrunch:
+            acc = torch.zeros((4, nchan, nbin), dtype=torch.float64,
+                              device=dev)
+            wsum = torch.zeros(nchan, dtype=torch.float64, device=dev)
+            zero_ph = torch.zeros((nsub, nchan), dtype=torch.float64,
+                                  device=dev)
+            w64 = wts.reshape(nsub, nchan).double()
+            for ipol in range(4):
+                # (the weight sum once; the other pols' into a scratch)
+                w = wsum if ipol == 0 else torch.zeros_like(wsum)
+                engine.align_accum(rows[:, ipol], zero_ph, w64, acc[ipol], w,
+                                   dev=dev)
+            mean = acc / torch.where(wsum > 0, wsum,
+                                     torch.ones_like(wsum))[None, :, None]
+            out = stats(mean.float()[None].contiguous(),
+                        wsum.float()[None].contiguous(), False)
+        return out
+
     def finish(self):
         from .timeline import span
         with span("load.read"):
@@ -1072,6 +1259,9 @@ class _Pending(object):
         from . import pplib
         f, filename, weights = self.f, self.filename, self.weights
         nsub, nchan, nbin = f.nsub, f.nchan, f.nbin
+        # (a polarised load: four polarisations in the state asked for)
+        npol, state = (1, "Intensity") if self.conv is None else \
+            (4, self.state)
         prof_norm = max(1.0, float(np.count_nonzero(weights)))
         imjd, frac, Ps, freqs = self.imjd, self.frac, self.Ps, self.freqs
         tsub, par = self.tsub, self.par
@@ -1106,12 +1296,13 @@ class _Pending(object):
             flux_prof=np.array([]),
             freqs=freqs, frontend=str(p.get("FRONTEND", "")).strip(),
             integration_length=float(tsub.sum()),
-            masks=_Masks(weights_norm, nbin), nbin=nbin, nchan=nchan,
-            npol=1, nsub=nsub,
+            fd_poln=f.fd_poln,
+            masks=_Masks(weights_norm, nbin, npol=npol), nbin=nbin,
+            nchan=nchan, npol=npol, nsub=nsub,
             nu0=float(p.get("OBSFREQ", self.freqs.mean())),
             ok_ichans=ok_ichans, ok_isubs=ok_isubs, parallactic_angles=par,
             phases=pplib.get_bin_centers(nbin), Ps=Ps,
-            source=str(p.get("SRC_NAME", "")).strip(), state="Intensity",
+            source=str(p.get("SRC_NAME", "")).strip(), state=state,
             subtimes=[float(tsub.sum())] if self.tscrunch else list(tsub),
             telescope=telescope, telescope_code=_telescope_code(telescope),
             weights=weights)
@@ -1122,18 +1313,20 @@ class _Pending(object):
         nsub, prof_norm = m.pop("_nsub"), m.pop("_prof_norm")
         nchan, nbin = m["nchan"], m["nbin"]
         packed = self.packed_h.numpy()
-        n1, n2 = nsub * nchan * 3, nsub * nbin
-        stats = packed[:n1].reshape(nsub, nchan, 3)
+        npol = m["npol"]
+        n1, n2 = nsub * npol * nchan * 3, nsub * nbin
+        stats = packed[:n1].reshape(nsub, npol, nchan, 3)
         total = packed[n1:n1 + n2].reshape(nsub, nbin)
         # (copies: the page-locked buffer goes back to its pool)
-        noise = packed[n1 + n2:n1 + n2 + nsub * nchan].reshape(nsub, nchan)
+        noise = packed[n1 + n2:n1 + n2 + nsub * npol * nchan].reshape(
+            nsub, npol, nchan)
         prof = total.sum(axis=0)
         prof_SNR, prof_noise = _window_snr(prof)
         if not self.quiet:
             print("\nReading data from %s on source %s (PSRFITS fast "
                   "path)..." % (self.filename, m["source"]))
         return pplib.DataBunch(
-            noise_stds=noise[:, None, :].copy(), prof=prof / prof_norm,
+            noise_stds=noise.copy(), prof=prof / prof_norm,
             prof_noise=prof_noise, prof_SNR=prof_SNR,
-            SNRs=stats[:, None, :, 2].copy(),
+            SNRs=stats[..., 2].copy(),
             subints=DeviceRows(self.rows, self.ev), **m)
