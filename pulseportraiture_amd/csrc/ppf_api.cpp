@@ -1372,20 +1372,17 @@ size_t ppf_unpack_workspace_bytes(int32_t nsub, int32_t nchan, int32_t nbin) {
     return ppf::unpack_partials(nsub, nchan, nbin) * sizeof(double) + 256;
 }
 
-int ppf_unpack_psrfits_batch(ppf_ctx *ctx, int32_t nsub, int32_t npol, int32_t nchan, int32_t nbin,
-                             int32_t elem, const void *raw, int64_t sub_stride, const float *scl,
-                             const float *offs, const float *wts, int32_t pol_mode,
-                             int32_t rm_baseline, float *out, double *stats, double *total,
-                             int32_t *wstart, void *workspace, size_t workspace_bytes,
-                             void *stream) {
-    if (!ctx) return PPF_EINVAL;
-    if (nsub < 0 || npol < 1 || nchan < 1 || nbin < 2 || elem < 0 || elem > 3 || pol_mode < 0 ||
-        pol_mode > 1 || (pol_mode == 1 && npol < 2))
-        return fail(ctx, PPF_EINVAL, "bad unpack arguments (npol=%d nchan=%d nbin=%d elem=%d "
-                    "pol_mode=%d)", npol, nchan, nbin, elem, pol_mode);
-    const int64_t esize = elem == 0 ? 2 : (elem == 1 ? 1 : 4);
-    if (sub_stride < (int64_t)(pol_mode == 1 ? 2 : 1) * nchan * nbin * esize)
-        return fail(ctx, PPF_EINVAL, "sub_stride %lld < one sub-int's DATA", (long long)sub_stride);
+static int64_t unpack_esize(int32_t elem) { return elem == 0 ? 2 : (elem == 1 ? 1 : 4); }
+
+// The two unpack entries past their own checks (mode, sub_stride against the
+// blocks they read): npol_out 1 with pol_mode, or npol_out 4 with conv
+static int unpack_batch(ppf_ctx *ctx, int32_t nsub, int32_t npol, int32_t nchan, int32_t nbin,
+                        int32_t elem, const void *raw, int64_t sub_stride, const float *scl,
+                        const float *offs, const float *wts, int32_t npol_out, int32_t pol_mode,
+                        int32_t conv, int32_t rm_baseline, float *out, double *stats,
+                        double *total, int32_t *wstart, void *workspace, size_t workspace_bytes,
+                        void *stream) {
+    const int64_t esize = unpack_esize(elem);
     // the kernel loads whole elements: every sub-int block starts on one
     if (sub_stride % esize || (uintptr_t)raw % (uintptr_t)esize)
         return fail(ctx, PPF_EINVAL, "raw and sub_stride must be multiples of the %lld-byte element",
@@ -1400,13 +1397,32 @@ int ppf_unpack_psrfits_batch(ppf_ctx *ctx, int32_t nsub, int32_t npol, int32_t n
     if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
     ppf::UnpackArgs a{};
     a.nsub = nsub; a.npol = npol; a.nchan = nchan; a.nbin = nbin; a.elem = elem;
-    a.pol_mode = pol_mode; a.rm_baseline = rm_baseline ? 1 : 0;
+    a.npol_out = npol_out; a.pol_mode = pol_mode; a.conv = conv;
+    a.rm_baseline = rm_baseline ? 1 : 0;
     a.win = std::min(nbin - 1, std::max(1, (int)std::lrint(0.15 * nbin)));
     a.raw = (const uint8_t *)raw; a.sub_stride = sub_stride;
     a.scl = scl; a.offs = offs; a.wts = wts; a.out = out;
     a.part = (double *)workspace; a.total = total; a.wstart = wstart; a.stats = stats;
     if ((e = ppf::launch_unpack(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e, "k_unpack");
     return PPF_OK;
+}
+
+int ppf_unpack_psrfits_batch(ppf_ctx *ctx, int32_t nsub, int32_t npol, int32_t nchan, int32_t nbin,
+                             int32_t elem, const void *raw, int64_t sub_stride, const float *scl,
+                             const float *offs, const float *wts, int32_t pol_mode,
+                             int32_t rm_baseline, float *out, double *stats, double *total,
+                             int32_t *wstart, void *workspace, size_t workspace_bytes,
+                             void *stream) {
+    if (!ctx) return PPF_EINVAL;
+    if (nsub < 0 || npol < 1 || nchan < 1 || nbin < 2 || elem < 0 || elem > 3 || pol_mode < 0 ||
+        pol_mode > 1 || (pol_mode == 1 && npol < 2))
+        return fail(ctx, PPF_EINVAL, "bad unpack arguments (npol=%d nchan=%d nbin=%d elem=%d "
+                    "pol_mode=%d)", npol, nchan, nbin, elem, pol_mode);
+    if (sub_stride < (int64_t)(pol_mode == 1 ? 2 : 1) * nchan * nbin * unpack_esize(elem))
+        return fail(ctx, PPF_EINVAL, "sub_stride %lld < one sub-int's DATA", (long long)sub_stride);
+    return unpack_batch(ctx, nsub, npol, nchan, nbin, elem, raw, sub_stride, scl, offs, wts, 1,
+                        pol_mode, 0, rm_baseline, out, stats, total, wstart, workspace,
+                        workspace_bytes, stream);
 }
 
 int ppf_unpack_psrfits_pol_batch(ppf_ctx *ctx, int32_t nsub, int32_t nchan, int32_t nbin,
@@ -1419,31 +1435,12 @@ int ppf_unpack_psrfits_pol_batch(ppf_ctx *ctx, int32_t nsub, int32_t nchan, int3
     if (nsub < 0 || nchan < 1 || nbin < 2 || elem < 0 || elem > 3 || conv < 0 || conv > 5)
         return fail(ctx, PPF_EINVAL, "bad unpack arguments (nchan=%d nbin=%d elem=%d conv=%d)",
                     nchan, nbin, elem, conv);
-    const int64_t esize = elem == 0 ? 2 : (elem == 1 ? 1 : 4);
-    if (sub_stride < (int64_t)4 * nchan * nbin * esize)
+    if (sub_stride < (int64_t)4 * nchan * nbin * unpack_esize(elem))
         return fail(ctx, PPF_EINVAL, "sub_stride %lld < the four polarisation blocks of a sub-int",
                     (long long)sub_stride);
-    if (sub_stride % esize || (uintptr_t)raw % (uintptr_t)esize)
-        return fail(ctx, PPF_EINVAL, "raw and sub_stride must be multiples of the %lld-byte element",
-                    (long long)esize);
-    if (nsub == 0) return PPF_OK;
-    if (!raw || !scl || !offs || !out || !stats || !total || !wstart || !workspace)
-        return fail(ctx, PPF_EINVAL, "null unpack pointer");
-    if (workspace_bytes < ppf_unpack_workspace_bytes(nsub, nchan, nbin))
-        return fail(ctx, PPF_ENOMEM, "unpack workspace %zu < %zu", workspace_bytes,
-                    ppf_unpack_workspace_bytes(nsub, nchan, nbin));
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
-    ppf::UnpackArgs a{};
-    a.nsub = nsub; a.npol = 4; a.nchan = nchan; a.nbin = nbin; a.elem = elem;
-    a.rm_baseline = rm_baseline ? 1 : 0;
-    a.win = std::min(nbin - 1, std::max(1, (int)std::lrint(0.15 * nbin)));
-    a.raw = (const uint8_t *)raw; a.sub_stride = sub_stride;
-    a.scl = scl; a.offs = offs; a.wts = wts; a.out = out;
-    a.part = (double *)workspace; a.total = total; a.wstart = wstart; a.stats = stats;
-    if ((e = ppf::launch_unpack_pol(a, conv, (hipStream_t)stream)) != hipSuccess)
-        return hip_fail(ctx, e, "k_unpack_pol");
-    return PPF_OK;
+    return unpack_batch(ctx, nsub, 4, nchan, nbin, elem, raw, sub_stride, scl, offs, wts, 4, 0,
+                        conv, rm_baseline, out, stats, total, wstart, workspace, workspace_bytes,
+                        stream);
 }
 
 int ppf_pack_psrfits_batch(ppf_ctx *ctx, int64_t nrow, int32_t nbin, int32_t in_dtype,

@@ -361,26 +361,26 @@ struct ScalesArgs {
 hipError_t launch_scales(const ScalesArgs &a, hipStream_t st);
 
 // PSRFITS fast path (ppf_psrfits.hip): raw SUBINT DATA bytes -> float32
-// total-intensity rows, baseline window, per-row statistics
+// rows (total intensity, or all four polarisations), baseline window,
+// per-row statistics
 struct UnpackArgs {
     int nsub, npol, nchan, nbin;
     int elem;                    // 0 big-endian int16, 1 uint8, 2 big-endian float32
-    int pol_mode;                // 0: pol 0 (npol 1, IQUV); 1: AA + BB
+    int npol_out;                // 1: total intensity; 4: full polarisation (npol = 4)
+    int pol_mode;                // npol_out 1.  0: pol 0 (npol 1, IQUV); 1: AA + BB
+    int conv;                    // npol_out 4.  0..5 (include/ppfit.h)
     int rm_baseline, win;        // subtract the off-pulse mean; window bins
     const uint8_t *raw;          // [nsub] blocks of sub_stride bytes
     int64_t sub_stride;
     const float *scl, *offs;     // [nsub][npol * nchan]
     const float *wts;            // [nsub][nchan] or null
-    float *out;                  // [nsub][nchan][nbin]
+    float *out;                  // [nsub][npol_out][nchan][nbin]
     double *part;                // [nsub][nblk][nbin] workspace
     double *total;               // [nsub][nbin]
     int32_t *wstart;             // [nsub]
-    double *stats;               // [nsub][nchan][3]: off mean, off sigma, S/N
+    double *stats;               // [nsub][npol_out][nchan][3]: off mean, off sigma, S/N
 };
 hipError_t launch_unpack(const UnpackArgs &a, hipStream_t st);
-// full polarisation: npol = 4, out [nsub][4][nchan][nbin], stats
-// [nsub][4][nchan][3]; conv 0..5 (include/ppfit.h); pol_mode is not read
-hipError_t launch_unpack_pol(const UnpackArgs &a, int conv, hipStream_t st);
 hipError_t launch_copy_host(const void *src_dev, void *dst, int64_t nbytes, hipStream_t st);
 size_t unpack_partials(int nsub, int nchan, int nbin);
 

@@ -1,26 +1,41 @@
 // ppf_psrfits.hip -- device side of the PSRCHIVE-free PSRFITS fast path
 // (pulseportraiture_amd/psrfits.py): the raw DATA bytes of
 // a fold-mode SUBINT table arrive as they sit in the file and are turned
-// into the float32 total-intensity rows load_data would hand get_TOAs
-// (pplib.py:2749-2915 with pscrunch=True, rm_baseline=True), plus the
-// per-profile baseline statistics and S/N.
+// into the float32 rows load_data would hand get_TOAs (pplib.py:2749-2915):
+// total intensity (pscrunch=True) or all four polarisations in the state
+// asked for, plus the per-profile baseline statistics and S/N.
 //
-//   k_unpack      WG = (sub-int, block of kUnpackChans channels), thread =
-//                 bin pairs: big-endian int16 / uint8 / float32 samples (or
-//                 native float32 rows: load_data's statistics pass after
-//                 dedispersion / tscrunch, DAT_SCL = 1, DAT_OFFS = 0) ->
-//                 DATA * DAT_SCL + DAT_OFFS in float32 arithmetic (two
-//                 roundings, no fma: PSRCHIVE's loader) -> total intensity
-//                 (npol 1: itself; AA+BB / AABBCRCI: AA + BB; IQUV: I) ->
-//                 rows [nsub][nchan][nbin]; the weighted channel sum of the
-//                 block (fixed channel order) -> partials [nsub][nblk][nbin]
+//   k_unpack      WG = (sub-int, block of kUnpackChans channels), threads
+//                 along the bins.  Per sample: big-endian int16 / uint8 /
+//                 float32 (or native float32 rows: load_data's statistics
+//                 pass after dedispersion / tscrunch, DAT_SCL = 1, DAT_OFFS =
+//                 0) -> DATA * DAT_SCL + DAT_OFFS in float32 arithmetic (two
+//                 roundings, no fma: PSRCHIVE's loader) of the NPR
+//                 polarisation blocks the instantiation reads, then
+//                   NPR 1  total intensity = the block itself (npol 1, IQUV's I)
+//                   NPR 2  total intensity = AA + BB (AA+BB / AABBCRCI)
+//                   NPR 4  the state conversion `conv` in float32 (sums,
+//                          differences and exact scalings by 2 or 1/2:
+//                          nothing for an fma to contract)
+//                 -> rows [nsub][nchan][nbin] (NPR 1, 2) or [nsub][4][nchan]
+//                 [nbin] (NPR 4); the weighted channel sum of the block's
+//                 total intensity (fixed channel order) -> partials
+//                 [nsub][nblk][nbin].  Blocks past NPR are never touched.
+//                 VEC: a lane takes 4 consecutive bins per polarisation with
+//                 one 8-byte load (int16; 4-byte uint8, 16-byte float32) and
+//                 one 16-byte store; the launch takes it when nbin is a
+//                 multiple of 4 and raw, sub_stride, out and the partials are
+//                 aligned for it.  Both forms run the same per-sample code:
+//                 identical bits.
 //   k_base_window WG per sub-int: total profile = sum of the partials in
 //                 block order; PSRCHIVE's BaselineWindow: the circular window
 //                 of W = rint(0.15 nbin) bins with the smallest sum (first
 //                 minimum) -> window start, total profile out
-//   k_row_stats   wave per row: off-pulse mean over the window (subtracted
-//                 from the row in place when rm_baseline), off-pulse sigma,
-//                 S/N = sum over the on-pulse bins / (sigma sqrt(n_on))
+//   k_row_stats   wave per row (nsub x npol_out * nchan of them, each with
+//                 its sub-int's window): off-pulse mean over the window
+//                 (subtracted from the row in place when rm_baseline),
+//                 off-pulse sigma, S/N = sum over the on-pulse bins /
+//                 (sigma sqrt(n_on))
 // All of it is HBM-streaming integer/byte work (no MFMA): a few bytes per
 // sample against the 2 B per sample that crossed PCIe.
 #include "ppf_device.hpp"
@@ -41,33 +56,114 @@ __device__ __forceinline__ float sample_f32(const uint8_t *p, int elem, int64_t 
     return __uint_as_float(u);
 }
 
+__device__ __forceinline__ void samples4_f32(const uint8_t *p, int elem, int64_t i, float x[4]) {
+    if (elem == 0) {
+        const uint2 u = *reinterpret_cast<const uint2 *>(p + i * 2);
+        x[0] = (float)(int16_t)__builtin_bswap16((uint16_t)(u.x & 0xffffu));
+        x[1] = (float)(int16_t)__builtin_bswap16((uint16_t)(u.x >> 16));
+        x[2] = (float)(int16_t)__builtin_bswap16((uint16_t)(u.y & 0xffffu));
+        x[3] = (float)(int16_t)__builtin_bswap16((uint16_t)(u.y >> 16));
+    } else if (elem == 1) {
+        const uint32_t u = *reinterpret_cast<const uint32_t *>(p + i);
+        for (int k = 0; k < 4; ++k) x[k] = (float)((u >> (8 * k)) & 0xffu);
+    } else if (elem == 3) {
+        const float4 f = *reinterpret_cast<const float4 *>(p + i * 4);
+        x[0] = f.x; x[1] = f.y; x[2] = f.z; x[3] = f.w;
+    } else {
+        const uint4 u = *reinterpret_cast<const uint4 *>(p + i * 4);
+        x[0] = __uint_as_float(__builtin_bswap32(u.x));
+        x[1] = __uint_as_float(__builtin_bswap32(u.y));
+        x[2] = __uint_as_float(__builtin_bswap32(u.z));
+        x[3] = __uint_as_float(__builtin_bswap32(u.w));
+    }
+}
+
+// v: the four scaled polarisations of one sample as stored -> o: the four of
+// the state asked for; returns the total intensity of the sample
+__device__ __forceinline__ float convert_state(int conv, const float v[4], float o[4]) {
+    switch (conv) {
+    case 2:   // AA BB CR CI -> I Q U V, linear feeds
+        o[0] = v[0] + v[1]; o[1] = v[0] - v[1]; o[2] = 2.0f * v[2]; o[3] = 2.0f * v[3];
+        break;
+    case 3:   // ... circular feeds
+        o[0] = v[0] + v[1]; o[1] = 2.0f * v[2]; o[2] = 2.0f * v[3]; o[3] = v[0] - v[1];
+        break;
+    case 4:   // I Q U V -> AA BB CR CI, linear feeds
+        o[0] = 0.5f * (v[0] + v[1]); o[1] = 0.5f * (v[0] - v[1]);
+        o[2] = 0.5f * v[2]; o[3] = 0.5f * v[3];
+        break;
+    case 5:   // ... circular feeds
+        o[0] = 0.5f * (v[0] + v[3]); o[1] = 0.5f * (v[0] - v[3]);
+        o[2] = 0.5f * v[1]; o[3] = 0.5f * v[2];
+        break;
+    default:  // 0, 1: as stored
+        o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
+    }
+    return (conv == 1 || conv >= 4) ? o[0] + o[1] : o[0];
+}
+
+// DATA * DAT_SCL + DAT_OFFS rounds twice, as PSRCHIVE's (and NumPy's) float32
+// arithmetic does: the product is pinned in a register before the add, so
+// the compiler cannot fuse them (-ffp-contract=fast)
+__device__ __forceinline__ float scaled_f32(float x, float scl, float off) {
+    float prod = x * scl;
+    asm volatile("" : "+v"(prod));      // rounded product: no fma
+    return prod + off;
+}
+
+// NPR: polarisation blocks read (1, 2 or 4); POL: four rows per channel are
+// written (NPR 4), else the one of the total intensity
+template <int NPR, bool POL, bool VEC>
 __global__ __launch_bounds__(256) void k_unpack(UnpackArgs a) {
-    // DATA * DAT_SCL + DAT_OFFS rounds twice, as PSRCHIVE's (and NumPy's)
-    // float32 arithmetic does: the product is pinned in a register before
-    // the add, so the compiler cannot fuse them (-ffp-contract=fast)
+    static_assert(POL ? NPR == 4 : NPR <= 2, "intensity reads 1 or 2 blocks, full polarisation 4");
+    constexpr int NB = VEC ? 4 : 1;     // bins per lane and trip
+    constexpr int NPO = POL ? 4 : 1;    // rows written per channel
     const int nblk = (a.nchan + kUnpackChans - 1) / kUnpackChans;
     const int s = blockIdx.x / nblk, blk = blockIdx.x % nblk;
     const uint8_t *raw = a.raw + (int64_t)s * a.sub_stride;
     const float *scl = a.scl + (int64_t)s * a.npol * a.nchan;
     const float *off = a.offs + (int64_t)s * a.npol * a.nchan;
     const int n0 = blk * kUnpackChans, n1 = min(a.nchan, n0 + kUnpackChans);
-    const int npol_used = a.pol_mode == 1 ? 2 : 1;
-    for (int b = threadIdx.x; b < a.nbin; b += blockDim.x) {
-        double part = 0.0;
+    for (int b = threadIdx.x * NB; b < a.nbin; b += blockDim.x * NB) {
+        double part[NB];
+        for (int k = 0; k < NB; ++k) part[k] = 0.0;
         for (int n = n0; n < n1; ++n) {
-            float v = 0.0f;
-            for (int p = 0; p < npol_used; ++p) {
+            float x[NPR][NB];
+            for (int p = 0; p < NPR; ++p) {
                 const int64_t i = ((int64_t)p * a.nchan + n) * a.nbin + b;
-                float prod = sample_f32(raw, a.elem, i) * scl[p * a.nchan + n];
-                asm volatile("" : "+v"(prod));      // rounded product: no fma
-                const float x = prod + off[p * a.nchan + n];
-                v = p == 0 ? x : v + x;
+                if (VEC) samples4_f32(raw, a.elem, i, x[p]);
+                else x[p][0] = sample_f32(raw, a.elem, i);
             }
-            a.out[((int64_t)s * a.nchan + n) * a.nbin + b] = v;
+            float o[NPO][NB];
             const double w = a.wts ? (double)a.wts[(int64_t)s * a.nchan + n] : 1.0;
-            if (w != 0.0) part += w * (double)v;
+            for (int k = 0; k < NB; ++k) {
+                float v[NPR], t;
+                for (int p = 0; p < NPR; ++p)
+                    v[p] = scaled_f32(x[p][k], scl[p * a.nchan + n], off[p * a.nchan + n]);
+                if constexpr (POL) {
+                    float c[4];
+                    t = convert_state(a.conv, v, c);
+                    for (int p = 0; p < 4; ++p) o[p][k] = c[p];
+                } else {
+                    if constexpr (NPR == 1) t = v[0];
+                    else t = v[0] + v[1];
+                    o[0][k] = t;
+                }
+                if (w != 0.0) part[k] = fma(w, (double)t, part[k]);
+            }
+            for (int p = 0; p < NPO; ++p) {
+                float *row = a.out + (((int64_t)s * NPO + p) * a.nchan + n) * a.nbin + b;
+                if (VEC) *reinterpret_cast<float4 *>(row) = make_float4(o[p][0], o[p][1], o[p][2], o[p][3]);
+                else row[0] = o[p][0];
+            }
         }
-        a.part[((int64_t)s * nblk + blk) * a.nbin + b] = part;
+        double *pt = a.part + ((int64_t)s * nblk + blk) * a.nbin + b;
+        if (VEC) {
+            reinterpret_cast<double2 *>(pt)[0] = make_double2(part[0], part[1]);
+            reinterpret_cast<double2 *>(pt)[1] = make_double2(part[2], part[3]);
+        } else {
+            pt[0] = part[0];
+        }
     }
 }
 
@@ -169,150 +265,29 @@ static hipError_t launch_base_window(const UnpackArgs &a, hipStream_t st) {
     return hipGetLastError();
 }
 
+template <int NPR, bool POL>
+static void launch_k_unpack(const UnpackArgs &a, bool vec, hipStream_t st) {
+    const int nblk = (a.nchan + kUnpackChans - 1) / kUnpackChans;
+    const dim3 grid((unsigned)((int64_t)a.nsub * nblk));
+    if (vec) hipLaunchKernelGGL((k_unpack<NPR, POL, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_unpack<NPR, POL, false>), grid, dim3(256), 0, st, a);
+}
+
 hipError_t launch_unpack(const UnpackArgs &a, hipStream_t st) {
-    const int nblk = (a.nchan + kUnpackChans - 1) / kUnpackChans;
-    hipLaunchKernelGGL(k_unpack, dim3((unsigned)((int64_t)a.nsub * nblk)), dim3(256), 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if ((e = launch_base_window(a, st)) != hipSuccess) return e;
-    const int64_t rows = (int64_t)a.nsub * a.nchan;
-    hipLaunchKernelGGL(k_row_stats, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// Full polarisation (ppf_unpack_psrfits_pol_batch): all four polarisation
-// blocks of every sample, the state converted on the way.
-//
-//   k_unpack_pol  k_unpack's grid (WG = sub-int x block of kUnpackChans
-//                 channels, threads along the bins).  Per sample: the four
-//                 DATA * DAT_SCL + DAT_OFFS values (two roundings each, as in
-//                 k_unpack), the state conversion `conv` in float32 (sums,
-//                 differences and exact scalings by 2 or 1/2: nothing for an
-//                 fma to contract), the four rows of the channel, and the
-//                 weighted channel-block partial of the total intensity in
-//                 k_unpack's layout, so k_base_window runs on it unchanged.
-//                 VEC: a lane takes 4 consecutive bins per polarisation with
-//                 one 8-byte load (int16; 4-byte uint8, 16-byte float32) and
-//                 one 16-byte store; the launch takes it when nbin is a
-//                 multiple of 4 and raw, sub_stride, out and the partials are
-//                 aligned for it.  Both forms run the same per-sample code:
-//                 identical bits.
-// k_row_stats then runs over the nsub x 4 nchan rows (its row -> sub-int map
-// holds with nchan := 4 nchan).
-
-__device__ __forceinline__ void samples4_f32(const uint8_t *p, int elem, int64_t i, float x[4]) {
-    if (elem == 0) {
-        const uint2 u = *reinterpret_cast<const uint2 *>(p + i * 2);
-        x[0] = (float)(int16_t)__builtin_bswap16((uint16_t)(u.x & 0xffffu));
-        x[1] = (float)(int16_t)__builtin_bswap16((uint16_t)(u.x >> 16));
-        x[2] = (float)(int16_t)__builtin_bswap16((uint16_t)(u.y & 0xffffu));
-        x[3] = (float)(int16_t)__builtin_bswap16((uint16_t)(u.y >> 16));
-    } else if (elem == 1) {
-        const uint32_t u = *reinterpret_cast<const uint32_t *>(p + i);
-        for (int k = 0; k < 4; ++k) x[k] = (float)((u >> (8 * k)) & 0xffu);
-    } else if (elem == 3) {
-        const float4 f = *reinterpret_cast<const float4 *>(p + i * 4);
-        x[0] = f.x; x[1] = f.y; x[2] = f.z; x[3] = f.w;
-    } else {
-        const uint4 u = *reinterpret_cast<const uint4 *>(p + i * 4);
-        x[0] = __uint_as_float(__builtin_bswap32(u.x));
-        x[1] = __uint_as_float(__builtin_bswap32(u.y));
-        x[2] = __uint_as_float(__builtin_bswap32(u.z));
-        x[3] = __uint_as_float(__builtin_bswap32(u.w));
-    }
-}
-
-// v: the four scaled polarisations of one sample as stored -> o: the four of
-// the state asked for; returns the total intensity of the sample
-__device__ __forceinline__ float convert_state(int conv, const float v[4], float o[4]) {
-    switch (conv) {
-    case 2:   // AA BB CR CI -> I Q U V, linear feeds
-        o[0] = v[0] + v[1]; o[1] = v[0] - v[1]; o[2] = 2.0f * v[2]; o[3] = 2.0f * v[3];
-        break;
-    case 3:   // ... circular feeds
-        o[0] = v[0] + v[1]; o[1] = 2.0f * v[2]; o[2] = 2.0f * v[3]; o[3] = v[0] - v[1];
-        break;
-    case 4:   // I Q U V -> AA BB CR CI, linear feeds
-        o[0] = 0.5f * (v[0] + v[1]); o[1] = 0.5f * (v[0] - v[1]);
-        o[2] = 0.5f * v[2]; o[3] = 0.5f * v[3];
-        break;
-    case 5:   // ... circular feeds
-        o[0] = 0.5f * (v[0] + v[3]); o[1] = 0.5f * (v[0] - v[3]);
-        o[2] = 0.5f * v[1]; o[3] = 0.5f * v[2];
-        break;
-    default:  // 0, 1: as stored
-        o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3];
-    }
-    return (conv == 1 || conv >= 4) ? o[0] + o[1] : o[0];
-}
-
-__device__ __forceinline__ float scaled_f32(float x, float scl, float off) {
-    float prod = x * scl;
-    asm volatile("" : "+v"(prod));      // rounded product: no fma
-    return prod + off;
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_unpack_pol(UnpackArgs a, int conv) {
-    constexpr int NB = VEC ? 4 : 1;     // bins per lane and trip
-    const int nblk = (a.nchan + kUnpackChans - 1) / kUnpackChans;
-    const int s = blockIdx.x / nblk, blk = blockIdx.x % nblk;
-    const uint8_t *raw = a.raw + (int64_t)s * a.sub_stride;
-    const float *scl = a.scl + (int64_t)s * 4 * a.nchan;
-    const float *off = a.offs + (int64_t)s * 4 * a.nchan;
-    const int n0 = blk * kUnpackChans, n1 = min(a.nchan, n0 + kUnpackChans);
-    for (int b = threadIdx.x * NB; b < a.nbin; b += blockDim.x * NB) {
-        double part[NB];
-        for (int k = 0; k < NB; ++k) part[k] = 0.0;
-        for (int n = n0; n < n1; ++n) {
-            float x[4][NB];
-            for (int p = 0; p < 4; ++p) {
-                const int64_t i = ((int64_t)p * a.nchan + n) * a.nbin + b;
-                if (VEC) samples4_f32(raw, a.elem, i, x[p]);
-                else x[p][0] = sample_f32(raw, a.elem, i);
-            }
-            float o[4][NB];
-            const double w = a.wts ? (double)a.wts[(int64_t)s * a.nchan + n] : 1.0;
-            for (int k = 0; k < NB; ++k) {
-                float v[4], c[4];
-                for (int p = 0; p < 4; ++p)
-                    v[p] = scaled_f32(x[p][k], scl[p * a.nchan + n], off[p * a.nchan + n]);
-                const float t = convert_state(conv, v, c);
-                for (int p = 0; p < 4; ++p) o[p][k] = c[p];
-                if (w != 0.0) part[k] = fma(w, (double)t, part[k]);
-            }
-            for (int p = 0; p < 4; ++p) {
-                float *row = a.out + (((int64_t)s * 4 + p) * a.nchan + n) * a.nbin + b;
-                if (VEC) *reinterpret_cast<float4 *>(row) = make_float4(o[p][0], o[p][1], o[p][2], o[p][3]);
-                else row[0] = o[p][0];
-            }
-        }
-        double *pt = a.part + ((int64_t)s * nblk + blk) * a.nbin + b;
-        if (VEC) {
-            reinterpret_cast<double2 *>(pt)[0] = make_double2(part[0], part[1]);
-            reinterpret_cast<double2 *>(pt)[1] = make_double2(part[2], part[3]);
-        } else {
-            pt[0] = part[0];
-        }
-    }
-}
-
-hipError_t launch_unpack_pol(const UnpackArgs &a, int conv, hipStream_t st) {
-    const int nblk = (a.nchan + kUnpackChans - 1) / kUnpackChans;
     const int64_t esize = a.elem == 0 ? 2 : (a.elem == 1 ? 1 : 4);
     const bool vec = a.nbin % 4 == 0 && a.sub_stride % (4 * esize) == 0 &&
                      (uintptr_t)a.raw % (uintptr_t)(4 * esize) == 0 && (uintptr_t)a.out % 16 == 0 &&
                      (uintptr_t)a.part % 16 == 0;
-    const dim3 grid((unsigned)((int64_t)a.nsub * nblk));
-    if (vec) hipLaunchKernelGGL(k_unpack_pol<true>, grid, dim3(256), 0, st, a, conv);
-    else hipLaunchKernelGGL(k_unpack_pol<false>, grid, dim3(256), 0, st, a, conv);
+    if (a.npol_out == 4) launch_k_unpack<4, true>(a, vec, st);
+    else if (a.pol_mode == 1) launch_k_unpack<2, false>(a, vec, st);
+    else launch_k_unpack<1, false>(a, vec, st);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if ((e = launch_base_window(a, st)) != hipSuccess) return e;
-    // the statistics of all nsub x 4 x nchan rows, each with its sub-int's window
+    // the statistics of all nsub x npol_out x nchan rows, each with its
+    // sub-int's window (k_row_stats' row -> sub-int map, nchan := npol_out nchan)
     UnpackArgs r = a;
-    r.nchan = 4 * a.nchan;
+    r.nchan = a.npol_out * a.nchan;
     const int64_t rows = (int64_t)r.nsub * r.nchan;
     hipLaunchKernelGGL(k_row_stats, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, r);
     return hipGetLastError();

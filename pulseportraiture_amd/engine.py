@@ -769,6 +769,39 @@ def noise_long(row, frac=4, dev=None):
     return float(noise_rows_long(x.reshape(1, -1), frac, dev).cpu()[0])
 
 
+def _unpack(entry, npol_in, npol_out, raw, elem, nchan, nbin, scl, offs, wts,
+            mode, rm_baseline, dev):
+    """The body of unpack_psrfits (npol_out 1, mode = pol_mode) and
+    unpack_psrfits_pol (npol_out 4, mode = conv): npol_in blocks of scl /
+    offs per sub-int; entry is the library function to call."""
+    dev = device(dev)
+    nsub = raw.shape[0]
+    f32 = torch.float32
+    scl_t = to_dev(scl, dev, f32).reshape(nsub, npol_in * nchan).contiguous()
+    offs_t = to_dev(offs, dev, f32).reshape(nsub, npol_in * nchan).contiguous()
+    wts_t = None if wts is None else \
+        to_dev(wts, dev, f32).reshape(nsub, nchan).contiguous()
+    shape = (nsub, nchan) if npol_out == 1 else (nsub, npol_out, nchan)
+    rows = torch.empty(shape + (nbin,), dtype=f32, device=dev)
+    stats = torch.empty(shape + (3,), dtype=torch.float64, device=dev)
+    total = torch.empty((nsub, nbin), dtype=torch.float64, device=dev)
+    wstart = torch.empty(nsub, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    wsb = int(lib.ppf_unpack_workspace_bytes(nsub, nchan, nbin))
+    ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
+    ctx = _lib.context(dev.index)
+    # (the intensity entry takes the file's npol; the polarised one has 4)
+    dims = (npol_in, nchan, nbin) if npol_out == 1 else (nchan, nbin)
+    rc = getattr(lib, entry)(
+        ctx, nsub, *dims, int(elem), _p(raw), int(raw.stride(0)), _p(scl_t),
+        _p(offs_t), None if wts_t is None else _p(wts_t), int(mode),
+        int(bool(rm_baseline)), _p(rows), _p(stats), _p(total), _p(wstart),
+        _p(ws), wsb, _stream(dev))
+    _lib.check(rc, ctx)
+    return dict(rows=rows, stats=stats, total=total, wstart=wstart,
+                _keep=(scl_t, offs_t, wts_t, ws, raw))
+
+
 def unpack_psrfits(raw, elem, npol, nchan, nbin, scl, offs, wts=None,
                    pol_mode=0, rm_baseline=True, dev=None):
     """ppf_unpack_psrfits_batch: raw DATA bytes [nsub, >= npol nchan nbin
@@ -776,29 +809,8 @@ def unpack_psrfits(raw, elem, npol, nchan, nbin, scl, offs, wts=None,
     file) -> dict(rows float32 [nsub, nchan, nbin], stats float64
     [nsub, nchan, 3] (off-pulse mean, sigma, S/N), total float64
     [nsub, nbin], wstart int32 [nsub]), all on the device."""
-    dev = device(dev)
-    nsub = raw.shape[0]
-    f32 = torch.float32
-    scl_t = to_dev(scl, dev, f32).reshape(nsub, npol * nchan).contiguous()
-    offs_t = to_dev(offs, dev, f32).reshape(nsub, npol * nchan).contiguous()
-    wts_t = None if wts is None else \
-        to_dev(wts, dev, f32).reshape(nsub, nchan).contiguous()
-    rows = torch.empty((nsub, nchan, nbin), dtype=f32, device=dev)
-    stats = torch.empty((nsub, nchan, 3), dtype=torch.float64, device=dev)
-    total = torch.empty((nsub, nbin), dtype=torch.float64, device=dev)
-    wstart = torch.empty(nsub, dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    wsb = int(lib.ppf_unpack_workspace_bytes(nsub, nchan, nbin))
-    ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
-    ctx = _lib.context(dev.index)
-    rc = lib.ppf_unpack_psrfits_batch(
-        ctx, nsub, npol, nchan, nbin, int(elem), _p(raw), int(raw.stride(0)),
-        _p(scl_t), _p(offs_t), None if wts_t is None else _p(wts_t),
-        int(pol_mode), int(bool(rm_baseline)), _p(rows), _p(stats), _p(total),
-        _p(wstart), _p(ws), wsb, _stream(dev))
-    _lib.check(rc, ctx)
-    return dict(rows=rows, stats=stats, total=total, wstart=wstart,
-                _keep=(scl_t, offs_t, wts_t, ws, raw))
+    return _unpack("ppf_unpack_psrfits_batch", npol, 1, raw, elem, nchan, nbin,
+                   scl, offs, wts, pol_mode, rm_baseline, dev)
 
 
 def unpack_psrfits_pol(raw, elem, nchan, nbin, scl, offs, wts=None, conv=0,
@@ -811,29 +823,8 @@ def unpack_psrfits_pol(raw, elem, nchan, nbin, scl, offs, wts=None, conv=0,
     float64 [nsub, 4, nchan, 3] (off-pulse mean, sigma, S/N; the window of
     the sub-int's total intensity), total float64 [nsub, nbin], wstart int32
     [nsub]), all on the device."""
-    dev = device(dev)
-    nsub = raw.shape[0]
-    f32 = torch.float32
-    scl_t = to_dev(scl, dev, f32).reshape(nsub, 4 * nchan).contiguous()
-    offs_t = to_dev(offs, dev, f32).reshape(nsub, 4 * nchan).contiguous()
-    wts_t = None if wts is None else \
-        to_dev(wts, dev, f32).reshape(nsub, nchan).contiguous()
-    rows = torch.empty((nsub, 4, nchan, nbin), dtype=f32, device=dev)
-    stats = torch.empty((nsub, 4, nchan, 3), dtype=torch.float64, device=dev)
-    total = torch.empty((nsub, nbin), dtype=torch.float64, device=dev)
-    wstart = torch.empty(nsub, dtype=torch.int32, device=dev)
-    lib = _lib.load()
-    wsb = int(lib.ppf_unpack_workspace_bytes(nsub, nchan, nbin))
-    ws = torch.empty(max(wsb, 8), dtype=torch.uint8, device=dev)
-    ctx = _lib.context(dev.index)
-    rc = lib.ppf_unpack_psrfits_pol_batch(
-        ctx, nsub, nchan, nbin, int(elem), _p(raw), int(raw.stride(0)),
-        _p(scl_t), _p(offs_t), None if wts_t is None else _p(wts_t),
-        int(conv), int(bool(rm_baseline)), _p(rows), _p(stats), _p(total),
-        _p(wstart), _p(ws), wsb, _stream(dev))
-    _lib.check(rc, ctx)
-    return dict(rows=rows, stats=stats, total=total, wstart=wstart,
-                _keep=(scl_t, offs_t, wts_t, ws, raw))
+    return _unpack("ppf_unpack_psrfits_pol_batch", 4, 4, raw, elem, nchan,
+                   nbin, scl, offs, wts, conv, rm_baseline, dev)
 
 
 def pack_rows(rows, elem="I", dev=None):

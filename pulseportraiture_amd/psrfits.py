@@ -359,18 +359,25 @@ class _PolycoRows(object):
         return self._c[name]
 
 
+def _scaled_host(raw, dtype, scl, offs, npol, nchan, nbin):
+    """float32 DATA * DAT_SCL + DAT_OFFS of raw [nsub, npol * nchan * nbin]
+    file bytes, [nsub, npol, nchan, nbin]: two float32 roundings, no fused
+    multiply-add, as PSRCHIVE's loader computes it."""
+    nsub = raw.shape[0]
+    x = np.ascontiguousarray(raw).view(dtype).reshape(nsub, npol, nchan, nbin)
+    x = x.astype(np.float32)
+    s = scl.reshape(nsub, npol, nchan, 1).astype(np.float32)
+    o = offs.reshape(nsub, npol, nchan, 1).astype(np.float32)
+    return (x * s).astype(np.float32) + o
+
+
 def unpack_host(raw, dtype, scl, offs, npol, nchan, nbin):
     """NumPy restatement of the device unpack (tests): float32 value =
     DATA * DAT_SCL + DAT_OFFS (two float32 roundings, no fused
     multiply-add, as PSRCHIVE's loader computes it), then total intensity:
     npol 1 -> itself, AABBCRCI / AA+BB -> AA + BB, IQUV -> I.
     raw: [nsub, npol * nchan * nbin] file bytes; returns [nsub, nchan, nbin]."""
-    nsub = raw.shape[0]
-    x = np.ascontiguousarray(raw).view(dtype).reshape(nsub, npol, nchan, nbin)
-    x = x.astype(np.float32)
-    s = scl.reshape(nsub, npol, nchan, 1).astype(np.float32)
-    o = offs.reshape(nsub, npol, nchan, 1).astype(np.float32)
-    v = (x * s).astype(np.float32) + o
+    v = _scaled_host(raw, dtype, scl, offs, npol, nchan, nbin)
     return v[:, 0] if npol == 1 else v[:, 0] + v[:, 1]
 
 
@@ -389,11 +396,49 @@ def pol_conv(file_state, state, fd_poln="LIN"):
     return (2 if state == "Stokes" else 4) + circ
 
 
+def _unpack_route(npol, pol_type, pscrunch, state, fd_poln="LIN",
+                  filename=""):
+    """How load_data unpacks a file of npol polarisations and POL_TYPE
+    pol_type asked for (pscrunch, state): (the leading polarisation blocks
+    of DATA to upload, pol_mode of engine.unpack_psrfits, conv of
+    engine.unpack_psrfits_pol or None for total intensity, the state of the
+    result).  Raises what load_data raises for what it cannot give."""
+    if state not in (None, "Intensity", "Stokes", "Coherence"):
+        raise NotImplementedError("state=%r needs PSRCHIVE" % state)
+    pt = pol_type.upper()
+    # full polarisation: exactly an npol = 4 file, not pscrunched
+    if npol == 4 and not pscrunch and state != "Intensity":
+        fstate = STATE_OF_POL_TYPE.get(pt)
+        if fstate is None:
+            raise NotImplementedError(
+                "POL_TYPE %s with npol = 4: IQUV and AABBCRCI files "
+                "load polarised" % pol_type)
+        return 4, 0, pol_conv(fstate, state, fd_poln), \
+            fstate if state is None else state
+    if state in ("Stokes", "Coherence") and npol == 1 and not pscrunch:
+        raise IndexError("%s has npol = 1: no state %s" % (filename, state))
+    if state in ("Stokes", "Coherence") and npol != 4:
+        raise NotImplementedError("state=%r needs PSRCHIVE" % state)
+    if npol > 1 and not (pscrunch or state == "Intensity"):
+        raise NotImplementedError("the PSRFITS fast path returns total "
+                                  "intensity (pscrunch=True), or all "
+                                  "four polarisations of an npol = 4 "
+                                  "file")
+    # only the polarisations total intensity needs cross PCIe: DATA is
+    # [npol][nchan][nbin] per sub-int, so AA and BB are its first two blocks
+    if npol == 1 or pt.startswith("IQUV") or pt == "INTEN":
+        return 1, 0, None, "Intensity"
+    if pt.startswith("AABB") or pt.startswith("AA+BB"):
+        return 2, 1, None, "Intensity"
+    raise NotImplementedError("POL_TYPE %s" % pol_type)
+
+
 def unpack_host_pol(raw, dtype, scl, offs, nchan, nbin, conv):
     """NumPy restatement of the device's full-polarisation unpack
-    (k_unpack_pol; tests): the four polarisations' float32 DATA * DAT_SCL +
-    DAT_OFFS (two roundings, as unpack_host), then the state conversion in
-    float32, one rounded operation per output, in the kernel's order:
+    (k_unpack on four blocks; tests): the four polarisations' float32 DATA *
+    DAT_SCL + DAT_OFFS (two roundings, as unpack_host), then the state
+    conversion in float32, one rounded operation per output, in the kernel's
+    order:
       conv 0, 1  as stored (I Q U V; AA BB CR CI)
       conv 2     AA+BB, AA-BB, 2 CR, 2 CI        (Coherence -> Stokes, LIN)
       conv 3     AA+BB, 2 CR, 2 CI, AA-BB        (... CIRC)
@@ -403,12 +448,7 @@ def unpack_host_pol(raw, dtype, scl, offs, nchan, nbin, conv):
     returns float32 [nsub, 4, nchan, nbin]."""
     if conv not in range(6):
         raise ValueError("conv must be 0..5")
-    nsub = raw.shape[0]
-    x = np.ascontiguousarray(raw).view(dtype).reshape(nsub, 4, nchan, nbin)
-    x = x.astype(np.float32)
-    s = scl.reshape(nsub, 4, nchan, 1).astype(np.float32)
-    o = offs.reshape(nsub, 4, nchan, 1).astype(np.float32)
-    v = (x * s).astype(np.float32) + o
+    v = _scaled_host(raw, dtype, scl, offs, 4, nchan, nbin)
     two, half = np.float32(2.0), np.float32(0.5)
     if conv in (0, 1):
         out = [v[:, 0], v[:, 1], v[:, 2], v[:, 3]]
@@ -925,48 +965,16 @@ class _Pending(object):
         with span("load.open"):
             f = self.f = PSRFITS(filename)
             nsub, npol, nchan, nbin = f.nsub, f.npol, f.nchan, f.nbin
-            pt = f.pol_type.upper()
-            # full polarisation: exactly an npol = 4 file, not pscrunched
-            pol = npol == 4 and not pscrunch and state != "Intensity"
-            self.conv = None
-            if pol:
-                fstate = STATE_OF_POL_TYPE.get(pt)
-                if fstate is None:
-                    raise NotImplementedError(
-                        "POL_TYPE %s with npol = 4: IQUV and AABBCRCI files "
-                        "load polarised" % f.pol_type)
-                self.conv = pol_conv(fstate, state, f.fd_poln)
-                self.state = fstate if state is None else state
-            elif state in ("Stokes", "Coherence") and npol == 1 and \
-                    not pscrunch:
-                raise IndexError("%s has npol = 1: no state %s"
-                                 % (filename, state))
-            elif state in ("Stokes", "Coherence") and npol != 4:
-                raise NotImplementedError("state=%r needs PSRCHIVE" % state)
-            elif npol > 1 and not (pscrunch or state == "Intensity"):
-                raise NotImplementedError("the PSRFITS fast path returns total "
-                                          "intensity (pscrunch=True), or all "
-                                          "four polarisations of an npol = 4 "
-                                          "file")
-            if pol:
-                pol_mode = 0                              # (not read)
-            elif npol == 1 or pt.startswith("IQUV") or pt == "INTEN":
-                pol_mode = 0
-            elif pt.startswith("AABB") or pt.startswith("AA+BB"):
-                pol_mode = 1
-            else:
-                raise NotImplementedError("POL_TYPE %s" % f.pol_type)
+            nblocks, pol_mode, self.conv, self.state = _unpack_route(
+                npol, f.pol_type, pscrunch, state, f.fd_poln, filename)
             raw, edt = f.data_bytes()
             elem = {np.dtype(">i2"): 0, np.dtype("u1"): 1,
                     np.dtype(">f4"): 2}.get(edt)
             if elem is None:
                 raise NotImplementedError("DATA element type %s" % edt)
-            # only the polarisations total intensity needs cross PCIe: DATA
-            # is [npol][nchan][nbin] per sub-int, so AA and BB are its first
-            # two npol blocks (2 B / sample / pol for 16-bit data)
-            # (a polarised load takes all four)
-            nbytes = (4 if pol else 2 if pol_mode == 1 else 1) * nchan * \
-                nbin * edt.itemsize
+            # only the polarisation blocks the load needs cross PCIe (2 B /
+            # sample / pol for 16-bit data)
+            nbytes = nblocks * nchan * nbin * edt.itemsize
             scl, offs = f.scales_offsets()
             self.weights = f.weights()
             dev = engine.device(dev)
@@ -1096,24 +1104,13 @@ class _Pending(object):
                     st.wait_event(up)
                     # with dedisperse the baseline is removed after the
                     # rotation (pplib.py:2786-2791)
-                    if self.conv is not None:
-                        out = engine.unpack_psrfits_pol(
-                            raw_d, elem, nchan, nbin, aux_d[:nsc],
-                            aux_d[nsc:2 * nsc], wts=aux_d[2 * nsc:],
-                            conv=self.conv,
-                            rm_baseline=rm_baseline and not dedisperse,
-                            dev=dev)
-                    else:
-                        out = engine.unpack_psrfits(
-                            raw_d, elem, npol, nchan, nbin, aux_d[:nsc],
-                            aux_d[nsc:2 * nsc], wts=aux_d[2 * nsc:],
-                            pol_mode=pol_mode,
-                            rm_baseline=rm_baseline and not dedisperse,
-                            dev=dev)
+                    out = self._unpack(
+                        engine, raw_d, elem, npol, aux_d[:nsc],
+                        aux_d[nsc:2 * nsc], aux_d[2 * nsc:], pol_mode,
+                        self.conv, rm_baseline and not dedisperse, dev)
                     if dedisperse or tscrunch:
-                        tr = self._transform if self.conv is None else \
-                            self._transform_pol
-                        out = tr(out, aux_d[2 * nsc:], rm_baseline, f, dev)
+                        out = self._transform(out, aux_d[2 * nsc:],
+                                              rm_baseline, f, dev)
                     noise = engine.noise_rows(out["rows"], dev=dev)
                     # one download: stats [nsub, nchan, 3], total [nsub,
                     # nbin], noise [nsub, nchan] (all float64)
@@ -1150,23 +1147,42 @@ class _Pending(object):
             P = np.array([float(np.sum(self.Ps * w) / np.sum(w))])
         return i1, f1, P
 
+    def _unpack(self, engine, raw, elem, npol, scl, offs, wts, pol_mode, conv,
+                rm_baseline, dev):
+        """The unpack / statistics pass of this load: engine.unpack_psrfits
+        for total intensity, engine.unpack_psrfits_pol for a polarised load
+        (conv: the state conversion)."""
+        nchan, nbin = self.f.nchan, self.f.nbin
+        if self.conv is None:
+            return engine.unpack_psrfits(
+                raw, elem, npol, nchan, nbin, scl, offs, wts=wts,
+                pol_mode=pol_mode, rm_baseline=rm_baseline, dev=dev)
+        return engine.unpack_psrfits_pol(
+            raw, elem, nchan, nbin, scl, offs, wts=wts, conv=conv,
+            rm_baseline=rm_baseline, dev=dev)
+
     def _transform(self, out, wts, rm_baseline, f, dev):
         """Dedispersion and / or tscrunch of the unpacked rows (on the copy
-        stream), then the statistics pass over the result (the native
-        float32 rows through ppf_unpack_psrfits_batch, elem 3)."""
+        stream), every polarisation of a channel rotated by the channel's
+        phase and tscrunched by the same weights, then the statistics pass
+        over the result (the native float32 rows through the load's unpack
+        entry, elem 3; a polarised load keeps its state: conv 0 or 1)."""
         import torch
         from . import engine, pplib
         nsub, nchan, nbin = f.nsub, f.nchan, f.nbin
-        rows = out["rows"]
-        ones = torch.ones((nsub, nchan), dtype=torch.float32, device=dev)
-        zeros = torch.zeros((nsub, nchan), dtype=torch.float32, device=dev)
+        npol = 1 if self.conv is None else 4
+        rows = out["rows"].reshape(nsub, npol, nchan, nbin)
+        keep = 0 if self.state == "Stokes" else 1
+        ones = torch.ones((nsub, npol * nchan), dtype=torch.float32,
+                          device=dev)
+        zeros = torch.zeros((nsub, npol * nchan), dtype=torch.float32,
+                            device=dev)
 
         def stats(rows, w, rm):
             n = rows.shape[0]
-            return engine.unpack_psrfits(
-                rows.reshape(n, nchan * nbin).view(torch.uint8), 3, 1, nchan,
-                nbin, ones[:n], zeros[:n], wts=w, pol_mode=0, rm_baseline=rm,
-                dev=dev)
+            return self._unpack(
+                engine, rows.reshape(n, npol * nchan * nbin).view(torch.uint8),
+                3, 1, ones[:n], zeros[:n], w, 0, keep, rm, dev)
         if self.dedisperse:
             # rotate_data(rows, 0, DM, Ps, freqs, nu0) (pplib.py:2427-2515):
             # the phases as it forms them
@@ -1175,61 +1191,18 @@ class _Pending(object):
             nu0 = float(p.get("OBSFREQ", self.freqs.mean()))
             D = pplib.Dconst * DM / (np.ones(nsub) * self.Ps)
             ph = D[:, None] * (self.freqs ** -2.0 - nu0 ** -2.0)
+            ph = np.repeat(ph[:, None, :], npol, axis=1)
             rows = engine.rotate_rows(rows, ph, dev=dev).float()
             out = stats(rows, wts, rm_baseline)
-            rows = out["rows"]
+            rows = out["rows"].reshape(nsub, npol, nchan, nbin)
         if self.tscrunch:
-            acc = torch.zeros((nchan, nbin), dtype=torch.float64, device=dev)
-            wsum = torch.zeros(nchan, dtype=torch.float64, device=dev)
-            engine.align_accum(rows, torch.zeros((nsub, nchan),
-                                                 dtype=torch.float64,
-                                                 device=dev),
-                               wts.reshape(nsub, nchan).double(), acc, wsum,
-                               dev=dev)
-            mean = acc / torch.where(wsum > 0, wsum,
-                                     torch.ones_like(wsum))[:, None]
-            out = stats(mean.float()[None].contiguous(),
-                        wsum.float()[None].contiguous(), False)
-        return out
-
-    def _transform_pol(self, out, wts, rm_baseline, f, dev):
-        """_transform for the four polarisations of a polarised load: every
-        polarisation of a channel rotated by the channel's phase, tscrunched
-        by the same weights; the statistics pass keeps the state (native
-        rows through ppf_unpack_psrfits_pol_batch, elem 3, conv 0 or 1)."""
-        import torch
-        from . import engine, pplib
-        nsub, nchan, nbin = f.nsub, f.nchan, f.nbin
-        rows = out["rows"]                        # [nsub, 4, nchan, nbin]
-        keep = 0 if self.state == "Stokes" else 1
-        ones = torch.ones((nsub, 4 * nchan), dtype=torch.float32, device=dev)
-        zeros = torch.zeros((nsub, 4 * nchan), dtype=torch.float32,
-                            device=dev)
-
-        def stats(rows, w, rm):
-            n = rows.shape[0]
-            return engine.unpack_psrfits_pol(
-                rows.reshape(n, 4 * nchan * nbin).view(torch.uint8), 3, nchan,
-                nbin, ones[:n], zeros[:n], wts=w, conv=keep, rm_baseline=rm,
-                dev=dev)
-        if self.dedisperse:
-            p, h = f.primary, f.subint.header
-            DM = float(h.get("DM", p.get("CHAN_DM", 0.0)))
-            nu0 = float(p.get("OBSFREQ", self.freqs.mean()))
-            D = pplib.Dconst * DM / (np.ones(nsub) * self.Ps)
-            ph = D[:, None] * (self.freqs ** -2.0 - nu0 ** -2.0)
-            ph = np.repeat(ph[:, None, :], 4, axis=1)
-            rows = engine.rotate_rows(rows, ph, dev=dev).float()
-            out = stats(rows, wts, rm_baseline)
-            rows = out["rows"]
-        if self.tscrunch:
-            acc = torch.zeros((4, nchan, nbin), dtype=torch.float64,
+            acc = torch.zeros((npol, nchan, nbin), dtype=torch.float64,
                               device=dev)
             wsum = torch.zeros(nchan, dtype=torch.float64, device=dev)
             zero_ph = torch.zeros((nsub, nchan), dtype=torch.float64,
                                   device=dev)
             w64 = wts.reshape(nsub, nchan).double()
-            for ipol in range(4):
+            for ipol in range(npol):
                 # (the weight sum once; the other pols' into a scratch)
                 w = wsum if ipol == 0 else torch.zeros_like(wsum)
                 engine.align_accum(rows[:, ipol], zero_ph, w64, acc[ipol], w,
@@ -1260,8 +1233,7 @@ class _Pending(object):
         f, filename, weights = self.f, self.filename, self.weights
         nsub, nchan, nbin = f.nsub, f.nchan, f.nbin
         # (a polarised load: four polarisations in the state asked for)
-        npol, state = (1, "Intensity") if self.conv is None else \
-            (4, self.state)
+        npol, state = 1 if self.conv is None else 4, self.state
         prof_norm = max(1.0, float(np.count_nonzero(weights)))
         imjd, frac, Ps, freqs = self.imjd, self.frac, self.Ps, self.freqs
         tsub, par = self.tsub, self.par

@@ -154,6 +154,23 @@ def test_same_call_twice_is_bitwise():
     _same(_run(c, True), _run(c, True))
 
 
+@pytest.mark.parametrize("npol,pol_mode", [(1, 0), (2, 1)])
+@pytest.mark.parametrize("en,pad", [("i16", 2), ("nat", 4)])
+def test_padded_stride_takes_element_accesses_bitwise(en, pad, npol, pol_mode):
+    """Total intensity from one block and from AA + BB, on samples whose
+    layout admits the 4-bins-per-lane form and on the same samples behind a
+    sub_stride of whole elements that is no multiple of 8 bytes (the
+    element-wide form): every output the same bits."""
+    name = "pad-%s-p%d" % (en, npol)
+    kw = dict(npol=npol, pol_mode=pol_mode, nsub=3, nchan=17, nbin=64)
+    v = U._random(name, U.ELEMS[en], **kw)
+    c = U._random(name, U.ELEMS[en], pad=pad, **kw)
+    assert c["raw"].shape[1] % 8 and v["raw"].shape[1] % 8 == 0
+    np.testing.assert_array_equal(c["raw"][:, :v["raw"].shape[1]], v["raw"])
+    for rm in (False, True):
+        _same(_run(c, rm), _run(v, rm), name)
+
+
 def test_profile_past_the_lds():
     """32768 bins (256 KB of float64): k_base_window reads the total
     profile back from `total`; the window is exact, wrapped ones too."""

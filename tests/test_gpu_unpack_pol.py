@@ -1,5 +1,5 @@
-"""ppf_unpack_psrfits_pol_batch (k_unpack_pol, then k_base_window and
-k_row_stats over all four polarisations) against the NumPy restatement of
+"""ppf_unpack_psrfits_pol_batch (k_unpack on four blocks, then k_base_window
+and k_row_stats over all four polarisations) against the NumPy restatement of
 tests/unpackpolcases.py (psrfits.unpack_host_pol + unpackcases.baseline):
 every conv on every sample type, profile lengths on both sides of the
 4-bins-per-lane path and of the 256-thread bin loop, one full and one ragged

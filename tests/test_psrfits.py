@@ -111,6 +111,72 @@ def test_unpack_host_restatement(tmp_path):
     f.close()
 
 
+# What load_data does with a file of (npol, POL_TYPE), one column per
+# (pscrunch, state) in the order of _ROUTE_ASKS.  I1 / I2: total intensity
+# from one block / from AA + BB; S<conv> / C<conv>: all four blocks, Stokes /
+# Coherence out through that conv (linear feeds); N: NotImplementedError; X:
+# IndexError.
+_ROUTE_ASKS = [(p, s) for p in (False, True)
+               for s in (None, "Intensity", "Stokes", "Coherence", "PPQQ")]
+_ROUTE_TABLE = """
+1 INTEN     I1 I1 X  X  N   I1 I1 N  N  N
+1 AA+BB     I1 I1 X  X  N   I1 I1 N  N  N
+1 AABB      I1 I1 X  X  N   I1 I1 N  N  N
+1 AABBCRCI  I1 I1 X  X  N   I1 I1 N  N  N
+1 IQUV      I1 I1 X  X  N   I1 I1 N  N  N
+1 XXYY      I1 I1 X  X  N   I1 I1 N  N  N
+2 INTEN     N  I1 N  N  N   I1 I1 N  N  N
+2 AA+BB     N  I2 N  N  N   I2 I2 N  N  N
+2 AABB      N  I2 N  N  N   I2 I2 N  N  N
+2 AABBCRCI  N  I2 N  N  N   I2 I2 N  N  N
+2 IQUV      N  I1 N  N  N   I1 I1 N  N  N
+2 XXYY      N  N  N  N  N   N  N  N  N  N
+4 INTEN     N  I1 N  N  N   I1 I1 I1 I1 N
+4 AA+BB     N  I2 N  N  N   I2 I2 I2 I2 N
+4 AABB      N  I2 N  N  N   I2 I2 I2 I2 N
+4 AABBCRCI  C1 I2 S2 C1 N   I2 I2 I2 I2 N
+4 IQUV      S0 I1 S0 C4 N   I1 I1 I1 I1 N
+4 XXYY      N  N  N  N  N   N  N  N  N  N
+"""
+_ROUTE_CODES = {"I1": (1, 0, None, "Intensity"), "I2": (2, 1, None, "Intensity"),
+                "S0": (4, 0, 0, "Stokes"), "S2": (4, 0, 2, "Stokes"),
+                "C1": (4, 0, 1, "Coherence"), "C4": (4, 0, 4, "Coherence"),
+                "N": NotImplementedError, "X": IndexError}
+
+
+def test_unpack_route_table():
+    """(blocks to upload, pol_mode, conv, state) or the exception of every
+    npol x POL_TYPE x pscrunch x state; FD_POLN CIRC moves conv 2 / 4 to
+    3 / 5 and nothing else."""
+    rows = [ln.split() for ln in _ROUTE_TABLE.strip().splitlines()]
+    assert len(rows) == 18 and all(len(r) == 12 for r in rows)
+    for r in rows:
+        npol, pol_type = int(r[0]), r[1]
+        for (pscrunch, state), code in zip(_ROUTE_ASKS, r[2:]):
+            want = _ROUTE_CODES[code]
+            args = (npol, pol_type, pscrunch, state, "LIN", "a.fits")
+            if isinstance(want, tuple):
+                assert PF._unpack_route(*args) == want, args
+            else:
+                with pytest.raises(want):
+                    PF._unpack_route(*args)
+    for pol_type, state, want in (
+            ("AABBCRCI", "Stokes", (4, 0, 3, "Stokes")),
+            ("IQUV", "Coherence", (4, 0, 5, "Coherence")),
+            ("AABBCRCI", None, (4, 0, 1, "Coherence")),
+            ("IQUV", "Stokes", (4, 0, 0, "Stokes"))):
+        assert PF._unpack_route(4, pol_type, False, state, "CIRC",
+                                "a.fits") == want
+    assert PF._unpack_route(4, "AABBCRCI", True, "Stokes", "CIRC",
+                            "a.fits") == (2, 1, None, "Intensity")
+    with pytest.raises(IndexError, match="a.fits has npol = 1: no state Stokes"):
+        PF._unpack_route(1, "AA+BB", False, "Stokes", "LIN", "a.fits")
+    with pytest.raises(NotImplementedError, match="POL_TYPE XXYY with npol = 4"):
+        PF._unpack_route(4, "XXYY", False, None, "LIN", "a.fits")
+    with pytest.raises(NotImplementedError, match="^POL_TYPE XXYY$"):
+        PF._unpack_route(2, "XXYY", True, None, "LIN", "a.fits")
+
+
 def test_mjd_arithmetic():
     from pulseportraiture_amd.pplib import MJD
     m = MJD(57000, 0.999999) + MJD(0.5 / 86400.0 * 86400.0 / 86400.0)

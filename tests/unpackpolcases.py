@@ -1,5 +1,6 @@
-"""Cases for ppf_unpack_psrfits_pol_batch (k_unpack_pol, then k_base_window
-and k_row_stats over all four polarisations) and their NumPy reference, in
+"""Cases for ppf_unpack_psrfits_pol_batch (k_unpack on four blocks, then
+k_base_window and k_row_stats over all four polarisations) and their NumPy
+reference, in
 the manner of tests/unpackcases.py, whose builders and baseline restatement
 they use.  Seeded, no file I/O.  The host side: tests/test_unpack_pol_host.py;
 the device side: tests/test_gpu_unpack_pol.py.
