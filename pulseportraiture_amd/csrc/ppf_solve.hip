@@ -1103,9 +1103,21 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 // MFMA f64 16x16x4: A = Y (16 channels x 4 harmonics; one wave = 16
 // channels), B = u^m (4 harmonics x 16 moments), two B tiles (m < 16, m >=
 // 16) and separate real / imaginary A.  The harmonic sum is the MFMA K loop.
-// (measured, C2 per 10k sub-ints, same call: KU = 8 6.12 vs 5.76 ms; the
-// loop unrolled by two over two buffers, so that no batch waits for loads it
-// has just issued, 5.77 at KU = 4 and 5.91 at KU = 2: no latency to hide.
+// The K loop (round 11): two buffers of one batch (16 harmonics) each; a
+// loop body is four batches -- mm(xa) ld(xa) mm(xb) ld(xb), twice -- in ONE
+// basic block, the re-seed of the phasor a compile-time flag of its first
+// batch, and the remaining one to four batches sit in nested uniform
+// branches behind the loop.  In that shape the compiler counts the loads in
+// flight: every batch waits vmcnt(7) .. (4) (tiled: (6), (4)), down to the
+// other buffer's four loads and never to 0, at the loop head and in the
+// remainder too, in both instantiations and both read paths.  The shape it
+// replaces (re-seed on kb & 63, a uniform `if` round the second batch: several
+// blocks per iteration) compiled to one vmcnt(0) per iteration, placed behind
+// the other buffer's loads.  Worth 4.1 vs 4.2-4.3 ms per 10k at C2 once the
+// blocks rotate (below); nothing before that.
+// Earlier measurements, all on the unrotated blocks, where nothing in the
+// loop showed (C2 per 10k sub-ints, same call): KU = 8 6.12 vs 5.76 ms;
+// the loop unrolled by two over two buffers 5.77 at KU = 4 and 5.91 at KU = 2.
 // Round 5, with the loads unconditional: KU = 2 / 8 5.61-5.77 / 5.70-5.97
 // vs 5.68-5.83 ms; the first two batches requested before the dphi / cutoff
 // loads, 5.83-5.85 vs 5.61-5.65 ms, and with the mask / dphi / cutoff loads
@@ -1122,7 +1134,18 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 template <bool M16>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) void k_moments(SolveArgs a) {
     const int nblk = (a.nchan + kMomChans - 1) / kMomChans;
-    const int s = blockIdx.x / nblk, blk = blockIdx.x % nblk;
+    // Which of the sub-int's channel blocks this workgroup takes rotates with
+    // the sub-int.  Workgroups go to the XCDs in turn (blockIdx % 8), and a
+    // block's reads repeat at the tile-row stride (nchan x 128 B: 64 KB at
+    // 512 channels), so with blk = blockIdx % nblk and nblk = 8 every XCD
+    // read one 8-KB window of each 64 KB for the whole launch -- 5.6-5.8 ms
+    // per 10k at C2 against 4.2-4.3 with the rotation, the loop unchanged
+    // (profiles/r11/ab_r11_explore.txt).  The rotation advances once per
+    // round of the XCDs: with every sub-int where a sub-int has 8 blocks or
+    // more, every 8 / nblk sub-ints below that.
+    const int s = blockIdx.x / nblk;
+    const int rot = (int)(((int64_t)s * (nblk < 8 ? nblk : 8)) >> 3);
+    const int blk = (int)((blockIdx.x % nblk + (unsigned)rot) % nblk);
     const TRState &S = a.state[s];
     if (!S.mmode || !S.need_mom) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1217,13 +1240,15 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
         return cmk(dpp_d<0xB1, 0xf>(snd.x), dpp_d<0xB1, 0xf>(snd.y));   // quad_perm [1,0,3,2]
     };
     auto keep = [&](int k) { return valid && k < kend; };
-    auto mm = [&](const double2 (&xv)[KU], int kb, auto tl) {
+    auto mm = [&](const double2 (&xv)[KU], int kb, auto tl, auto seed) {
 #pragma unroll
         for (int t = 0; t < KU; ++t) {
             const int k = kb + 4 * t + kk;
-            // phasor by recurrence, re-seeded exactly every 64 harmonics
-            // (kb is a multiple of 16: only t = 0 can re-seed)
-            if (t == 0 && (kb & 63) == 0) E = cexp2pi((double)k * phin);
+            // phasor by recurrence, re-seeded exactly every 64 harmonics:
+            // at K-step 0 of the batches with kb a multiple of 64, which the
+            // caller names at compile time (seed) so that a loop body stays
+            // one basic block
+            if (t == 0 && decltype(seed)::value) E = cexp2pi((double)k * phin);
             else E = cmul(E, W4);
             const double2 Et = E;
             double2 xt;
@@ -1247,17 +1272,49 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
     // two batches in flight, the buffers alternating (no register copy, so
     // no wait for the batch just issued)
     auto run = [&](auto tl) {
+        // The batch's loads stay where they are written, between the two
+        // batches of MFMAs: left alone, the scheduler moves them down among
+        // the next batch's instructions (its wait then covers them too), and
+        // the optimiser sinks a remainder batch's loads into the branch that
+        // uses them, behind the MFMAs they were to overlap.
         auto ldx = [&](double2 (&xv)[KU], int kb) {
+            __builtin_amdgcn_sched_barrier(0);
             if constexpr (decltype(tl)::value) ldt(xv, kb);
             else ld(xv, kb);
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
         };
+        constexpr int B = 4 * KU;                      // harmonics per batch
+        constexpr std::true_type seed{};
+        constexpr std::false_type step{};
         ldx(xa, 0);
-        ldx(xb, 4 * KU);
-        for (int kb = 0; kb < kend; kb += 8 * KU) {
-            mm(xa, kb, tl);
-            ldx(xa, kb + 8 * KU);
-            if (kb + 4 * KU < kend) mm(xb, kb + 4 * KU, tl);    // (uniform)
-            ldx(xb, kb + 12 * KU);
+        ldx(xb, B);
+        int kb = 0;
+        // whole bodies of four batches (64 harmonics, one re-seed), one
+        // basic block each
+        for (; kb + 4 * B <= kend; kb += 4 * B) {
+            mm(xa, kb, tl, seed);
+            ldx(xa, kb + 2 * B);
+            mm(xb, kb + B, tl, step);
+            ldx(xb, kb + 3 * B);
+            mm(xa, kb + 2 * B, tl, step);
+            ldx(xa, kb + 4 * B);
+            mm(xb, kb + 3 * B, tl, step);
+            ldx(xb, kb + 5 * B);
+        }
+        // the remaining one to four batches (the last one partial), nested
+        // so that every block has one predecessor and keeps its count
+        if (kb < kend) {                               // (uniform, all of them)
+            mm(xa, kb, tl, seed);
+            if (kb + B < kend) {
+                ldx(xa, kb + 2 * B);
+                mm(xb, kb + B, tl, step);
+                if (kb + 2 * B < kend) {
+                    ldx(xb, kb + 3 * B);
+                    mm(xa, kb + 2 * B, tl, step);
+                    if (kb + 3 * B < kend) mm(xb, kb + 3 * B, tl, step);
+                }
+            }
         }
     };
     if (tiled) run(std::true_type{});                  // (uniform)
