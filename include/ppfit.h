@@ -425,6 +425,46 @@ int ppf_noise_long(ppf_ctx *ctx, int64_t nrows, int64_t nbin, int32_t in_dtype,
                    const void *in, int32_t frac, double *out, void *workspace,
                    size_t workspace_bytes, void *stream);
 
+/* Fitted noise floor: pplib.get_noise_fit (pplib.py:2341-2373) and the
+ * find_kc it calls (pplib.py:1530-1561), added within ABI 6.  With pows =
+ * |rfft(x)|^2 / nbin (N = nbin / 2 + 1 harmonics) and d = log10(pows),
+ * find_kc minimises chi^2(a, b, dc) = sum_k ((d_k - dc - b e_k(a)) / errs_k)^2
+ * over scipy.optimize.brute's 20 x 20 x 20 grid (np.mgrid[lo:hi:20j]) --
+ * b over [0, max d - min d], dc over [min d, max d]; fn 0 (exp_dc):
+ * e_k = exp(-a k), a over [1/N, 1]; fn 1 (half_tri): e_k = 1 - k / floor(a)
+ * below floor(a), 0 from there, a over [1, N] -- and takes the first minimum
+ * in C order (the first NaN if there is one; a NaN or zero-power harmonic
+ * makes every row of the grid NaN: index 0).  kc depends on the winning a
+ * alone, so the caller supplies both tables, HOST arrays read during the
+ * call: a_grid[20], and kc_table[20], the kc of each of its values (>= 0).
+ * get_noise_fit then has k_crit = fact * kc, lowered to min(int(0.99 N),
+ * k_crit) when k_crit >= N, and noise = sqrt(mean(pows[int(k_crit):])).
+ *
+ * ppf_noise_fit_batch: the row lengths of ppf_noise_batch (fn 0, errs 1);
+ * in: [nrows][nbin]; noise_out, kc_out: [nrows] device.
+ * ppf_noise_fit_long: any length ppf_noise_long takes with nbin >= 3, on its
+ * transforms; workspace: ppf_noise_fit_long_workspace_bytes(nrows, nbin)
+ * bytes of device scratch (0: unsupported).
+ * ppf_find_kc_batch: find_kc of power spectra pows [nrows][nharm] (device
+ * f64, nharm >= 2); errs: NULL (errs = 1) or a DEVICE array of errs_len = 1
+ * or nharm doubles shared by the rows; kc_out: [nrows] device.
+ * Codes: PPF_EUNSUP for an unsupported length; PPF_EINVAL for a NULL array
+ * or context, a bad in_dtype or fn, a fact that is not finite and positive,
+ * errs_len other than 1 or nharm, a short workspace. */
+int ppf_noise_fit_batch(ppf_ctx *ctx, int64_t nrows, int32_t nbin, int32_t in_dtype,
+                        const void *in, double fact, const double *a_grid,
+                        const int32_t *kc_table, double *noise_out, int32_t *kc_out,
+                        void *stream);
+size_t ppf_noise_fit_long_workspace_bytes(int64_t nrows, int64_t nbin);
+int ppf_noise_fit_long(ppf_ctx *ctx, int64_t nrows, int64_t nbin, int32_t in_dtype,
+                       const void *in, double fact, const double *a_grid,
+                       const int32_t *kc_table, double *noise_out, int32_t *kc_out,
+                       void *workspace, size_t workspace_bytes, void *stream);
+int ppf_find_kc_batch(ppf_ctx *ctx, int64_t nrows, int64_t nharm, const double *pows,
+                      const double *errs, int64_t errs_len, int32_t fn,
+                      const double *a_grid, const int32_t *kc_table, int32_t *kc_out,
+                      void *stream);
+
 /* rotate_data's rotation of rows of ANY length (round 6, ABI 6): rows the
  * LDS transforms of ppf_rotate_batch do not take (even nbin > 8192, odd
  * nbin > 4095), as Bluestein transforms both ways (up to 2^23 complex

@@ -108,6 +108,18 @@ SIGNATURES = {
     "ppf_noise_long": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64,
                                       _i32, _vp, _i32, _vp, _vp,
                                       ctypes.c_size_t, _vp]),
+    "ppf_noise_fit_batch": (ctypes.c_int, [_vp, ctypes.c_int64, _i32, _i32,
+                                           _vp, ctypes.c_double, _vp, _vp,
+                                           _vp, _vp, _vp]),
+    "ppf_noise_fit_long_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64,
+                                                             ctypes.c_int64]),
+    "ppf_noise_fit_long": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64,
+                                          _i32, _vp, ctypes.c_double, _vp,
+                                          _vp, _vp, _vp, _vp, ctypes.c_size_t,
+                                          _vp]),
+    "ppf_find_kc_batch": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64,
+                                         _vp, _vp, ctypes.c_int64, _i32, _vp,
+                                         _vp, _vp, _vp]),
     "ppf_resid_chi2_batch": (ctypes.c_int, [_vp, ctypes.c_int64, _i32, _i32,
                                             _vp, _vp, _vp, _vp, _vp, _vp,
                                             ctypes.c_double, _vp, _vp]),

@@ -1249,6 +1249,121 @@ int ppf_noise_long(ppf_ctx *ctx, int64_t nrows, int64_t nbin, int32_t in_dtype, 
     return PPF_OK;
 }
 
+// get_noise_fit / find_kc (ppf_noisefit.hip)
+namespace {
+// the checks the three entries share, and the tables into the launch's args
+int noise_fit_args(ppf_ctx *ctx, int32_t fn, const double *a_grid, const int32_t *kc_table,
+                   ppf::NoiseFitArgs &a) {
+    if (fn != 0 && fn != 1) return fail(ctx, PPF_EINVAL, "fn=%d: 0 (exp_dc) or 1 (half_tri)", fn);
+    if (!a_grid || !kc_table) return fail(ctx, PPF_EINVAL, "a_grid / kc_table is NULL");
+    a = ppf::NoiseFitArgs{};
+    a.fn = fn;
+    for (int i = 0; i < ppf::kNfGrid; ++i) {
+        if (kc_table[i] < 0) return fail(ctx, PPF_EINVAL, "kc_table[%d] = %d < 0", i, kc_table[i]);
+        a.a_grid[i] = a_grid[i];
+        a.kc_table[i] = kc_table[i];
+    }
+    return PPF_OK;
+}
+bool fact_ok(double fact) { return fact > 0.0 && fact <= ppf::kDblMax; }
+size_t fit_long_pows_bytes(const LongPlan &p) {
+    return align256((size_t)p.rows_c * (size_t)p.a.nharm * sizeof(double));
+}
+}  // namespace
+
+int ppf_noise_fit_batch(ppf_ctx *ctx, int64_t nrows, int32_t nbin, int32_t in_dtype, const void *in,
+                        double fact, const double *a_grid, const int32_t *kc_table, double *noise_out,
+                        int32_t *kc_out, void *stream) {
+    // every argument check on the host, before the context or any launch
+    if (!nbin_supported(nbin)) return fail(ctx, PPF_EUNSUP, "nbin=%d unsupported", nbin);
+    if (nrows < 0 || !fact_ok(fact) || (nrows > 0 && (!in || !noise_out || !kc_out)))
+        return fail(ctx, PPF_EINVAL, "bad noise_fit arguments");
+    if (in_dtype != PPF_F32 && in_dtype != PPF_F64) return fail(ctx, PPF_EINVAL, "in_dtype");
+    ppf::NoiseFitArgs a;
+    int rc = noise_fit_args(ctx, 0, a_grid, kc_table, a);
+    if (rc) return rc;
+    if (!ctx) return PPF_EINVAL;
+    if (nrows == 0) return PPF_OK;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = twiddles(ctx, nbin, st, &a.T, &a.T2))) return rc;
+    a.nbin = nbin; a.dtype = in_dtype; a.in = in; a.nharm = nbin / 2 + 1; a.fact = fact;
+    a.noise_out = noise_out; a.kc_out = kc_out;
+    if ((e = ppf::launch_noise_fit(a, nrows, st)) != hipSuccess) return hip_fail(ctx, e, "k_noise_fit");
+    return PPF_OK;
+}
+
+size_t ppf_noise_fit_long_workspace_bytes(int64_t nrows, int64_t nbin) {
+    LongPlan p;
+    if (nbin < 3 || !long_plan(nrows, nbin, 4, p)) return 0;
+    return p.bytes + fit_long_pows_bytes(p);
+}
+
+int ppf_noise_fit_long(ppf_ctx *ctx, int64_t nrows, int64_t nbin, int32_t in_dtype, const void *in,
+                       double fact, const double *a_grid, const int32_t *kc_table, double *noise_out,
+                       int32_t *kc_out, void *workspace, size_t workspace_bytes, void *stream) {
+    if (nrows < 0 || nbin < 1 || !fact_ok(fact) || (nrows > 0 && (!in || !noise_out || !kc_out)))
+        return fail(ctx, PPF_EINVAL, "bad noise_fit arguments");
+    if (in_dtype != PPF_F32 && in_dtype != PPF_F64) return fail(ctx, PPF_EINVAL, "in_dtype");
+    ppf::NoiseFitArgs f;
+    int rc = noise_fit_args(ctx, 0, a_grid, kc_table, f);
+    if (rc) return rc;
+    LongPlan p;
+    if (nbin < 3 || !long_plan(nrows, nbin, 4, p))
+        return fail(ctx, PPF_EUNSUP, "nbin=%lld: fewer than 2 harmonics, or a transform longer than 2^24 points",
+                    (long long)nbin);
+    if (!ctx) return PPF_EINVAL;
+    if (nrows == 0) return PPF_OK;
+    const size_t need = p.bytes + fit_long_pows_bytes(p);
+    if (!workspace || workspace_bytes < need)
+        return fail(ctx, PPF_EINVAL, "workspace %zu < %zu bytes", workspace_bytes, need);
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
+    hipStream_t st = (hipStream_t)stream;
+    const double2 *T1, *T2, *unused;
+    if ((rc = twiddles(ctx, (int)(2 * p.a.M1), st, &T1, &unused))) return rc;
+    if ((rc = twiddles(ctx, (int)(2 * p.a.M2), st, &T2, &unused))) return rc;
+    char *ws = (char *)workspace;
+    double2 *Bf = (double2 *)ws;
+    if (p.a.bluestein && (e = ppf::launch_chirp_ft(p.a, Bf, Bf + p.a.M, T1, T2, st)) != hipSuccess)
+        return hip_fail(ctx, e, "k_lf_chirp");
+    p.a.in_dtype = in_dtype;
+    p.a.in = in;
+    double *pows = (double *)(ws + p.bytes);
+    f.nharm = p.a.nharm; f.pows = pows; f.fact = fact; f.noise_out = noise_out; f.kc_out = kc_out;
+    for (int64_t r0 = 0; r0 < nrows; r0 += p.rows_c) {
+        p.a.row0 = r0;
+        f.row0 = r0;
+        const int64_t nr = nrows - r0 < p.rows_c ? nrows - r0 : p.rows_c;
+        e = ppf::launch_pows_long(p.a, nr, (double2 *)(ws + p.off_A), (double2 *)(ws + p.off_Y), Bf, pows, T1,
+                                  T2, st);
+        if (e != hipSuccess) return hip_fail(ctx, e, "k_lf");
+        if ((e = ppf::launch_spec_fit(f, nr, st)) != hipSuccess) return hip_fail(ctx, e, "k_spec_fit");
+    }
+    return PPF_OK;
+}
+
+int ppf_find_kc_batch(ppf_ctx *ctx, int64_t nrows, int64_t nharm, const double *pows, const double *errs,
+                      int64_t errs_len, int32_t fn, const double *a_grid, const int32_t *kc_table,
+                      int32_t *kc_out, void *stream) {
+    if (nrows < 0 || nharm < 2 || nharm > ((int64_t)1 << 30) || (nrows > 0 && (!pows || !kc_out)))
+        return fail(ctx, PPF_EINVAL, "bad find_kc arguments");
+    if (errs && errs_len != 1 && errs_len != nharm)
+        return fail(ctx, PPF_EINVAL, "errs_len=%lld: 1 or nharm=%lld", (long long)errs_len, (long long)nharm);
+    ppf::NoiseFitArgs a;
+    int rc = noise_fit_args(ctx, fn, a_grid, kc_table, a);
+    if (rc) return rc;
+    if (!ctx) return PPF_EINVAL;
+    if (nrows == 0) return PPF_OK;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
+    a.nharm = nharm; a.pows = pows; a.errs = errs; a.errs_len = errs_len; a.kc_out = kc_out;
+    if ((e = ppf::launch_spec_fit(a, nrows, (hipStream_t)stream)) != hipSuccess)
+        return hip_fail(ctx, e, "k_spec_fit");
+    return PPF_OK;
+}
+
 // ppf_rotate_long's plans and workspace: Bluestein transforms both ways
 namespace {
 bool bluestein_plan(int64_t nbin, int64_t n, bool packed, ppf::LongNoiseArgs &a) {

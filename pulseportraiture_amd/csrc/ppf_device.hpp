@@ -656,6 +656,40 @@ __device__ __forceinline__ double2 rfft_bin(const double2 *buf, int N, const dou
     return cmk(e.x + wo.y, e.y - wo.x);
 }
 
+// ===========================================================================
+// common row loading: z_j = x_{2j} + i x_{2j+1} (even nbin); z_j = x_j + 0 i
+// (odd nbin, rfft_len)
+// ===========================================================================
+__device__ __forceinline__ void load_row(double2 *buf, const void *src, int dtype, int64_t row,
+                                         int nbin) {
+    const int N = nbin >> 1;
+    if (nbin & 1) {
+        if (dtype == 0) {
+            const float *s = reinterpret_cast<const float *>(src) + row * (int64_t)nbin;
+            for (int j = threadIdx.x; j < nbin; j += kBlock) buf[j] = cmk((double)s[j], 0.0);
+        } else {
+            const double *s = reinterpret_cast<const double *>(src) + row * (int64_t)nbin;
+            for (int j = threadIdx.x; j < nbin; j += kBlock) buf[j] = cmk(s[j], 0.0);
+        }
+        return;
+    }
+    if (dtype == 0) {
+        const float2 *s = reinterpret_cast<const float2 *>(src) + row * (int64_t)N;
+        for (int j = threadIdx.x; j < N; j += kBlock) {
+            float2 v = s[j];
+            buf[j] = cmk((double)v.x, (double)v.y);
+        }
+    } else {
+        const double2 *s = reinterpret_cast<const double2 *>(src) + row * (int64_t)N;
+        for (int j = threadIdx.x; j < N; j += kBlock) buf[j] = s[j];
+    }
+}
+
+// X_k (k <= nbin / 2) of the row load_row + lds_fft_n(rfft_len(nbin)) left in buf
+__device__ __forceinline__ double2 rbin(const double2 *buf, int nbin, const double2 *__restrict__ T2, int k) {
+    return (nbin & 1) ? buf[k] : rfft_bin(buf, nbin >> 1, T2, k);
+}
+
 // Inverse real FFT pre-pass: Z_k (k < N) from X_0..X_N (imaginary parts of
 // X_0 and X_N ignored, as numpy.fft.irfft does).  Xk, XNk = X_k, X_{N-k}.
 __device__ __forceinline__ double2 irfft_prebin(double2 Xk, double2 XNk, double2 w /*T2[k]*/) {

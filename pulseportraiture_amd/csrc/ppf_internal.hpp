@@ -264,6 +264,26 @@ struct NoiseArgs {
     double *out;
 };
 
+// get_noise_fit / find_kc (ppf_noisefit.hip): the brute-grid fit of the
+// noise floor to the log10 power spectrum of each row
+constexpr int kNfGrid = 20;     // scipy.optimize.brute's Ns (pplib.py:1550)
+struct NoiseFitArgs {
+    int nbin, dtype;            // k_noise_fit: the rows and their length
+    const void *in;
+    const double2 *T, *T2;
+    int64_t nharm;              // k_spec_fit: power spectra [rows][nharm] f64
+    const double *pows;
+    const double *errs;         // nullptr: errs = 1; else [errs_len], errs_len 1 or nharm
+    int64_t errs_len;
+    int fn;                     // 0 exp_dc, 1 half_tri
+    double fact;                // get_noise_fit's factor on kc
+    double a_grid[kNfGrid];     // the width grid and the kc of each of its values
+    int32_t kc_table[kNfGrid];
+    double *noise_out;          // [rows] or nullptr (find_kc)
+    int32_t *kc_out;            // [rows]
+    int64_t row0;               // first output row of this launch
+};
+
 // get_noise_PS of long rows (ppf_longfft.hip): the plan of one call
 struct LongNoiseArgs {
     int64_t nbin;               // real samples per row
@@ -567,6 +587,14 @@ hipError_t launch_rotate_long(const LongRotArgs &r, int64_t nrows, double2 *A, d
 hipError_t launch_noise_long(const LongNoiseArgs &a, int64_t nrows, double2 *A, double2 *Y,
                              const double2 *Bf, double *part, double *out, const double2 *T1,
                              const double2 *T2, hipStream_t st);
+// the power spectra |F_k|^2 / nbin, k < nharm, of the rows launch_noise_long
+// would reduce -> pows [nrows][nharm] (ppf_noise_fit_long)
+hipError_t launch_pows_long(const LongNoiseArgs &a, int64_t nrows, double2 *A, double2 *Y,
+                            const double2 *Bf, double *pows, const double2 *T1, const double2 *T2,
+                            hipStream_t st);
+// get_noise_fit per row in LDS (k_noise_fit) / from power spectra (k_spec_fit)
+hipError_t launch_noise_fit(const NoiseFitArgs &a, int64_t nrows, hipStream_t st);
+hipError_t launch_spec_fit(const NoiseFitArgs &a, int64_t nrows, hipStream_t st);
 // wave-per-row noise (k_noise_w) for N = nbin/2 = 128..1024
 bool noise_wave_supported(int log2N);
 hipError_t launch_noise_wave(const NoiseArgs &a, int64_t nrows, hipStream_t st);

@@ -21,39 +21,8 @@
 
 namespace ppf {
 
-// ===========================================================================
-// common row loading: z_j = x_{2j} + i x_{2j+1} (even nbin); z_j = x_j + 0 i
-// (odd nbin, rfft_len)
-// ===========================================================================
-__device__ __forceinline__ void load_row(double2 *buf, const void *src, int dtype, int64_t row,
-                                         int nbin) {
-    const int N = nbin >> 1;
-    if (nbin & 1) {
-        if (dtype == 0) {
-            const float *s = reinterpret_cast<const float *>(src) + row * (int64_t)nbin;
-            for (int j = threadIdx.x; j < nbin; j += kBlock) buf[j] = cmk((double)s[j], 0.0);
-        } else {
-            const double *s = reinterpret_cast<const double *>(src) + row * (int64_t)nbin;
-            for (int j = threadIdx.x; j < nbin; j += kBlock) buf[j] = cmk(s[j], 0.0);
-        }
-        return;
-    }
-    if (dtype == 0) {
-        const float2 *s = reinterpret_cast<const float2 *>(src) + row * (int64_t)N;
-        for (int j = threadIdx.x; j < N; j += kBlock) {
-            float2 v = s[j];
-            buf[j] = cmk((double)v.x, (double)v.y);
-        }
-    } else {
-        const double2 *s = reinterpret_cast<const double2 *>(src) + row * (int64_t)N;
-        for (int j = threadIdx.x; j < N; j += kBlock) buf[j] = s[j];
-    }
-}
-
-// X_k (k <= nbin / 2) of the row load_row + lds_fft_n(rfft_len(nbin)) left in buf
-__device__ __forceinline__ double2 rbin(const double2 *buf, int nbin, const double2 *__restrict__ T2, int k) {
-    return (nbin & 1) ? buf[k] : rfft_bin(buf, nbin >> 1, T2, k);
-}
+// (load_row and rbin, the row loading and the rFFT bin every block-FFT kernel
+// starts from, are in ppf_device.hpp: ppf_noisefit.hip takes them too)
 // odd nbin: Y_k (k <= nbin / 2) into the Hermitian full-length buffer of the
 // inverse transform, whose real part is then the row (the imaginary part of
 // Y_0 drops out, as numpy.fft.irfft ignores it)

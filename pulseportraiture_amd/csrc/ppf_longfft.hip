@@ -105,33 +105,37 @@ __global__ __launch_bounds__(kBlock) void k_lf_mul(LongNoiseArgs a, double2 *A, 
         A[r * a.M + i] = cscale(cmul(A[r * a.M + i], Bf[i]), s);
 }
 
-// block partials of sum_{k >= kc} |F_k|^2 / nbin, F the real row's rFFT
-__global__ __launch_bounds__(kBlock) void k_lf_pow(LongNoiseArgs a, const double2 *A, double *part) {
-    __shared__ double red[kWaves];
-    const int64_t r = blockIdx.y;
-    const double2 *Z = A + r * a.M;
+// |F_k|^2 / nbin, F the rFFT of the real row whose transform is Z
+__device__ __forceinline__ double lf_power(const LongNoiseArgs &a, const double2 *Z, int64_t k) {
     // the complex transform's bin k (k = n wraps to 0)
     auto zk = [&](int64_t k) -> double2 {
         if (k >= a.n) k -= a.n;
         if (a.bluestein) return cmul(Z[k], chirp(k, a.n));
         return Z[(k & (a.M1 - 1)) * a.M2 + (k >> a.log2M1)];   // X[k1 + M1 k2] at k1 M2 + k2
     };
+    double2 F;
+    if (a.packed) {
+        // F_k = (Z_k + conj Z_{n-k}) / 2 - i e^{-2 pi i k / nbin} (Z_k - conj Z_{n-k}) / 2
+        const double2 z1 = zk(k), z2 = cconj(zk(a.n - k));
+        const double2 e = cscale(cadd(z1, z2), 0.5), o = cscale(csub(z1, z2), 0.5);
+        const double2 w = phasor_pi(2 * k, a.nbin, -1.0);
+        const double2 wo = cmul(w, o);
+        F = cmk(e.x + wo.y, e.y - wo.x);
+    } else {
+        F = zk(k);
+    }
+    return (F.x * F.x + F.y * F.y) / (double)a.nbin;
+}
+
+// block partials of sum_{k >= kc} |F_k|^2 / nbin
+__global__ __launch_bounds__(kBlock) void k_lf_pow(LongNoiseArgs a, const double2 *A, double *part) {
+    __shared__ double red[kWaves];
+    const int64_t r = blockIdx.y;
+    const double2 *Z = A + r * a.M;
     double acc[1] = {0.0};
     for (int64_t k = a.kc + (int64_t)blockIdx.x * kBlock + threadIdx.x; k < a.nharm;
-         k += (int64_t)gridDim.x * kBlock) {
-        double2 F;
-        if (a.packed) {
-            // F_k = (Z_k + conj Z_{n-k}) / 2 - i e^{-2 pi i k / nbin} (Z_k - conj Z_{n-k}) / 2
-            const double2 z1 = zk(k), z2 = cconj(zk(a.n - k));
-            const double2 e = cscale(cadd(z1, z2), 0.5), o = cscale(csub(z1, z2), 0.5);
-            const double2 w = phasor_pi(2 * k, a.nbin, -1.0);
-            const double2 wo = cmul(w, o);
-            F = cmk(e.x + wo.y, e.y - wo.x);
-        } else {
-            F = zk(k);
-        }
-        acc[0] += (F.x * F.x + F.y * F.y) / (double)a.nbin;
-    }
+         k += (int64_t)gridDim.x * kBlock)
+        acc[0] += lf_power(a, Z, k);
     block_sum<1>(acc, red);
     if (threadIdx.x == 0) part[r * gridDim.x + blockIdx.x] = acc[0];
 }
@@ -143,6 +147,15 @@ __global__ __launch_bounds__(kBlock) void k_lf_fin(LongNoiseArgs a, const double
     for (int i = threadIdx.x; i < nblk; i += kBlock) acc[0] += part[r * nblk + i];
     block_sum<1>(acc, red);
     if (threadIdx.x == 0) out[a.row0 + r] = sqrt(acc[0] / (double)(a.nharm - a.kc));
+}
+
+// the whole power spectrum of each row -> pows [nrows][nharm] (the input of
+// get_noise_fit's grid fit, k_spec_fit)
+__global__ __launch_bounds__(kBlock) void k_lf_pows(LongNoiseArgs a, const double2 *A, double *pows) {
+    const int64_t r = blockIdx.y;
+    const double2 *Z = A + r * a.M;
+    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < a.nharm; k += (int64_t)gridDim.x * kBlock)
+        pows[r * a.nharm + k] = lf_power(a, Z, k);
 }
 
 int lf_pow_blocks(const LongNoiseArgs &a) {
@@ -208,6 +221,23 @@ hipError_t launch_noise_long(const LongNoiseArgs &a, int64_t nrows, double2 *A, 
     hipLaunchKernelGGL(k_lf_pow, dim3((unsigned)nb, (unsigned)nrows), dim3(kBlock), 0, st, a, A, part);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(k_lf_fin, dim3((unsigned)nrows), dim3(kBlock), 0, st, a, part, nb, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_pows_long(const LongNoiseArgs &a, int64_t nrows, double2 *A, double2 *Y,
+                            const double2 *Bf, double *pows, const double2 *T1, const double2 *T2,
+                            hipStream_t st) {
+    hipError_t e;
+    hipLaunchKernelGGL(k_lf_load, dim3(stride_blocks(a.M), (unsigned)nrows), dim3(kBlock), 0, st, a, A);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = four_step(a, nrows, A, Y, false, T1, T2, st)) != hipSuccess) return e;
+    if (a.bluestein) {
+        hipLaunchKernelGGL(k_lf_mul, dim3(stride_blocks(a.M), (unsigned)nrows), dim3(kBlock), 0, st, a, A, Bf);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = four_step(a, nrows, A, Y, true, T1, T2, st)) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_lf_pows, dim3(stride_blocks(a.nharm), (unsigned)nrows), dim3(kBlock), 0, st, a, A,
+                       pows);
     return hipGetLastError();
 }
 

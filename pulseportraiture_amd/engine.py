@@ -7,6 +7,7 @@ returns device tensors; the drop-in modules (pplib / pptoaslib / pptoas)
 convert to the reference's numpy/DataBunch forms.
 """
 import ctypes
+import functools
 import os
 import threading
 import warnings
@@ -767,6 +768,91 @@ def noise_long(row, frac=4, dev=None):
     x = to_dev(row, device(dev), None if isinstance(row, torch.Tensor)
                else torch.float64)
     return float(noise_rows_long(x.reshape(1, -1), frac, dev).cpu()[0])
+
+
+FIND_KC_FN = {"exp_dc": 0, "half_tri": 1}
+
+
+@functools.lru_cache(maxsize=64)
+def find_kc_tables(nharm, fn="exp_dc"):
+    """The width grid of find_kc (pplib.py:1541-1551) for a power spectrum of
+    nharm harmonics, and the kc each of its 20 values stands for
+    (pplib.py:1553-1559): (a_grid float64 [20], kc_table int32 [20]).  Both
+    depend on nharm alone, so they are formed here (once per nharm: cached,
+    read-only) with NumPy as the reference forms them -- scipy.optimize.brute's grid is
+    np.mgrid[lo:hi:20j] -- and no device exp decides a kc."""
+    n = int(nharm)
+    if fn == "exp_dc":
+        a = np.mgrid[slice(n ** -1, 1.0, complex(20))]
+        kc = np.empty(20, dtype=np.int32)
+        for i, ai in enumerate(a):
+            below = np.where(np.exp(-ai * np.arange(n)) < 0.005)[0]
+            kc[i] = below.min() if len(below) else n - 1
+    elif fn == "half_tri":
+        a = np.mgrid[slice(1, n, complex(20))]
+        kc = np.floor(a).astype(np.int32)
+    else:
+        raise KeyError(fn)
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    a.setflags(write=False)                # cached: shared by every caller
+    kc.setflags(write=False)
+    return a, kc
+
+
+def noise_fit_rows(rows, fact=1.1, dev=None):
+    """get_noise_fit per row of rows [..., nbin] (pplib.py:2341-2364) ->
+    (noise float64 [...], kc int32 [...]) on the device: ppf_noise_fit_batch
+    at the lengths of its LDS transforms, ppf_noise_fit_long past them."""
+    dev = device(dev)
+    r = to_dev(rows, dev, _data_dtype(rows))
+    shape = r.shape
+    r2 = r.reshape(-1, shape[-1]).contiguous()
+    nrows, nbin = r2.shape
+    lib = _lib.load()
+    long_rows = not _noise_batch_len_ok(nbin)
+    if long_rows:
+        nb = lib.ppf_noise_fit_long_workspace_bytes(nrows, nbin)
+        if nb == 0:
+            raise NotImplementedError(
+                "get_noise_fit of %d-sample rows: fewer than 2 harmonics, or "
+                "past the 2^24-point transform" % nbin)
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    a_grid, kc_table = find_kc_tables(nbin // 2 + 1)
+    noise = torch.empty(nrows, dtype=torch.float64, device=dev)
+    kc = torch.empty(nrows, dtype=torch.int32, device=dev)
+    dt = _lib.PPF_F32 if r2.dtype == torch.float32 else _lib.PPF_F64
+    ctx = _lib.context(dev.index)
+    if long_rows:
+        rc = lib.ppf_noise_fit_long(
+            ctx, nrows, nbin, dt, _p(r2), float(fact), a_grid.ctypes.data,
+            kc_table.ctypes.data, _p(noise), _p(kc), _p(ws), nb, _stream(dev))
+    else:
+        rc = lib.ppf_noise_fit_batch(
+            ctx, nrows, nbin, dt, _p(r2), float(fact), a_grid.ctypes.data,
+            kc_table.ctypes.data, _p(noise), _p(kc), _stream(dev))
+    _lib.check(rc, ctx)
+    return noise.reshape(shape[:-1]), kc.reshape(shape[:-1])
+
+
+def find_kc_rows(pows, errs=1.0, fn="exp_dc", dev=None):
+    """find_kc (pplib.py:1530-1561) of each power spectrum in pows
+    [..., nharm] -> kc int32 [...] on the device (ppf_find_kc_batch).  errs:
+    a scalar or [nharm] uncertainties of log10(pows), shared by the rows."""
+    dev = device(dev)
+    p = to_dev(pows, dev, torch.float64)
+    shape = p.shape
+    p2 = p.reshape(-1, shape[-1]).contiguous()
+    nrows, nharm = p2.shape
+    a_grid, kc_table = find_kc_tables(nharm, fn)
+    e = to_dev(np.atleast_1d(np.asarray(errs, dtype=np.float64)), dev,
+               torch.float64).contiguous()
+    kc = torch.empty(nrows, dtype=torch.int32, device=dev)
+    ctx = _lib.context(dev.index)
+    rc = _lib.load().ppf_find_kc_batch(
+        ctx, nrows, nharm, _p(p2), _p(e), e.numel(), FIND_KC_FN[fn],
+        a_grid.ctypes.data, kc_table.ctypes.data, _p(kc), _stream(dev))
+    _lib.check(rc, ctx)
+    return kc.reshape(shape[:-1])
 
 
 def _unpack(entry, npol_in, npol_out, raw, elem, nchan, nbin, scl, offs, wts,

@@ -478,10 +478,80 @@ def get_noise(data, method=default_noise_method, **kwargs):
     if method == "PS":
         return get_noise_PS(data, **kwargs)
     if method == "fit":
-        raise NotImplementedError("get_noise_fit is outside the accelerated "
-                                  "path (SURVEY.md section 2, row 6)")
+        return get_noise_fit(data, **kwargs)
     print("Unknown get_noise method.")
     return 0
+
+
+def get_noise_fit(data, fact=1.1, chans=False):
+    """pplib.py:2341-2373 on the GPU (ppf_noise_fit_batch; the flattened
+    portrait of chans=False, or rows past the LDS transforms, on
+    ppf_noise_fit_long)."""
+    data = np.asarray(data)
+    if chans:
+        return engine.noise_fit_rows(np.atleast_2d(data), fact)[0] \
+            .cpu().numpy()
+    noise = engine.noise_fit_rows(data.ravel()[None, :], fact)[0]
+    return np.float64(noise.cpu().numpy()[0])
+
+
+def find_kc(pows, errs=1.0, fn="exp_dc"):
+    """pplib.py:1530-1561 on the GPU (ppf_find_kc_batch): the cutoff harmonic
+    where the noise floor of the power spectrum pows begins."""
+    if fn not in engine.FIND_KC_FN:
+        return 0
+    pows = np.asarray(pows, dtype=np.float64)
+    return int(engine.find_kc_rows(pows[None, :], errs, fn).cpu().numpy()[0])
+
+
+def half_triangle_function(a, b, dc, N):
+    """pplib.py:1496-1506: N points of the baseline dc carrying a half
+    triangle that falls from b at index 0 to zero at its base floor(a)."""
+    base = int(np.floor(a))
+    out = np.zeros(N) + dc
+    out[:base] += b - (np.float64(b) / base) * np.arange(base)
+    return out
+
+
+def find_kc_function(params, data, errs=1.0, fn="exp_dc"):
+    """pplib.py:1509-1527: the (weighted) chi-squared find_kc minimises over
+    params = (a, b, dc); 0.0 for an unknown fn."""
+    a, b, dc = params[:3]
+    nharm = len(data)
+    if fn == "half_tri":
+        model = half_triangle_function(a, b, dc, nharm)
+    elif fn == "exp_dc":
+        model = b * np.exp(-a * np.arange(nharm)) + dc
+    else:
+        return 0.0
+    return np.sum(((data - model) / errs) ** 2.0)
+
+
+def brickwall_filter(N, kc):
+    """pplib.py:1468-1476: N points, ones before index kc and zeros from
+    it."""
+    wall = np.zeros(N)
+    wall[:kc] = 1.0
+    return wall
+
+
+def wiener_filter(prof, noise):
+    """pplib.py:1450-1464 (marked under construction in the reference, whose
+    behaviour is kept): pows / (pows + noise**2) of the profile's power
+    spectrum."""
+    spec = np.fft.rfft(prof)
+    pows = np.real(spec * np.conj(spec)) / len(prof)
+    return pows / (pows + noise ** 2)
+
+
+def fit_brickwall(prof, noise):
+    """pplib.py:1479-1493 (under construction in the reference, kept as it
+    is): the kc whose brickwall lies nearest the Wiener filter."""
+    wf = wiener_filter(prof, noise)
+    nharm = len(wf)
+    dist = [np.sum((wf - brickwall_filter(nharm, kc)) ** 2)
+            for kc in range(nharm)]
+    return np.array(dist).argmin()
 
 
 def get_noise_PS(data, frac=4, chans=False):
