@@ -683,6 +683,53 @@ int ppf_gauss_lsq_batch(ppf_ctx *ctx, int32_t nfit, int32_t nchan, int32_t nbin,
                         const double *inv_errs, double *gram, void *workspace,
                         size_t workspace_bytes, void *stream);
 
+/* The joined Gaussian model (added within ABI 6): several archives of one
+ * pulsar under one model, each archive with a phase and a DM offset of its
+ * own (gen_gaussian_portrait's join_ichans, pplib.py:956-962; the join
+ * parameters of fit_gaussian_portrait, pplib.py:2073-2098).  The arguments
+ * of ppf_gauss_portrait_batch / ppf_gauss_lsq_batch, plus
+ *   njoin                  archives
+ *   join_id  [n][nchan]    int32, HOST (as free_idx: checked here, copied by
+ *                          the call): the archive of each channel, -1 for a
+ *                          channel in none
+ *   join_params [n][2 njoin]  f64, device: phase [rot], DM per archive
+ *   P        [n]           f64, device: period [s]
+ * (n = nport or nfit).  A row of archive a is rotated by
+ *     rot = phi_a + (Dconst DM_a / P) (nu^-2 - nu_ref^-2)
+ * as rotate_data does (pplib.py:2447-2512), in the row's one transform round
+ * trip: harmonic k is multiplied by B_k e^{2 pi i k rot}, B_k the scattering
+ * factor or 1, the imaginary parts of the DC and Nyquist bins dropped before
+ * the phasor as the reference's intermediate irfft drops them.  A row of an
+ * archive takes this path at rot = 0 too; a row of no archive is built by
+ * the unrotated code and has the bits ppf_gauss_portrait_batch gives it.
+ * In ppf_gauss_lsq_join_batch the extended parameter vector free_idx indexes
+ * is [0, npar) params, [npar, npar + 2 njoin) join_params, npar + 2 njoin
+ * the scattering index (the reference's lmfit order; today's layout at
+ * njoin = 0).  A column that perturbs a join parameter of archive a is
+ * exact zeros over the channels outside a: no row is built or read there.
+ * The workspace is that of ppf_gauss_lsq_workspace_bytes.
+ * With njoin = 0 both calls are the unjoined ones, bit for bit.  With
+ * njoin > 0 they keep the device copy of join_id in the context's scratch
+ * and return after the stream has finished.
+ * PPF_EUNSUP: nbin odd or outside [32, 8192] (the reference cannot rotate an
+ * odd-length model either: its irfft returns nbin - 1 bins).  PPF_EINVAL: a
+ * join_id outside [-1, njoin), njoin < 0, a NULL array, and what the
+ * unjoined calls refuse.  All checked on the host before any launch. */
+int ppf_gauss_portrait_join_batch(ppf_ctx *ctx, int32_t nport, int32_t nchan, int32_t nbin,
+                                  int32_t ngauss, const char *model_code, const double *params,
+                                  const double *scattering_index, const double *freqs,
+                                  const double *nu_ref, int32_t njoin, const int32_t *join_id,
+                                  const double *join_params, const double *P, double *out,
+                                  void *stream);
+int ppf_gauss_lsq_join_batch(ppf_ctx *ctx, int32_t nfit, int32_t nchan, int32_t nbin, int32_t ngauss,
+                             const char *model_code, const double *params,
+                             const double *scattering_index, const double *freqs,
+                             const double *nu_ref, int32_t njoin, const int32_t *join_id,
+                             const double *join_params, const double *P, int32_t nfree,
+                             const int32_t *free_idx, const double *delta, int32_t in_dtype,
+                             const void *data, const double *inv_errs, double *gram,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
 /* Stationary-wavelet denoise-and-score engine (added within ABI 6): the
  * search of pplib.smart_smooth (pplib.py:1740-1838) over decomposition level
  * and threshold factor.  The transform is the undecimated 'db8' transform of

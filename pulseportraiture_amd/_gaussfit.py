@@ -12,7 +12,9 @@ the normal equations, because that is what the device returns: an evaluator
     evaluator(p_ext, free_idx, delta) -> Gram matrix [nfree + 1, nfree + 1]
 
 gives, for the extended parameter vector p_ext (the model parameters with the
-scattering index appended), the Gram matrix of the columns
+scattering index appended; a joined fit has the (phase, DM) pairs of its
+archives between the two: [params, join params, index]), the Gram matrix of
+the columns
 ((m(p + delta_j e_j) - m(p)) / delta_j) / errs (j over free_idx) and
 (data - m(p)) / errs: J^T J, J^T r and chi^2 in one call, chi^2 alone with
 no free index.  engine.GaussLsqEvaluator is the device one
@@ -63,12 +65,13 @@ def to_internal(p, lo, hi):
     return x
 
 
-def portrait_bounds(nparam):
-    """(lo, hi) of the 2 + 6 ngauss portrait parameters plus the scattering
-    index, the reference's limits (pplib.py:2041-2101): tau >= 0,
+def portrait_bounds(nparam, njoin=0):
+    """(lo, hi) of the 2 + 6 ngauss portrait parameters, the 2 njoin join
+    parameters (phase, DM per archive; unbounded) and the scattering index
+    last, the reference's limits (pplib.py:2041-2101): tau >= 0,
     0 <= wid <= wid_max, amp >= 0, everything else free."""
-    lo = np.full(nparam + 1, np.nan)
-    hi = np.full(nparam + 1, np.nan)
+    lo = np.full(nparam + 2 * njoin + 1, np.nan)
+    hi = np.full(nparam + 2 * njoin + 1, np.nan)
     lo[1] = 0.0
     lo[4:nparam:6] = 0.0
     hi[4:nparam:6] = WID_MAX

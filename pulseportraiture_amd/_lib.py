@@ -145,6 +145,17 @@ SIGNATURES = {
                                            _vp, _i32, _vp, _vp, _i32, _vp,
                                            _vp, _vp, _vp, ctypes.c_size_t,
                                            _vp]),
+    "ppf_gauss_portrait_join_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32,
+                                                     _i32, ctypes.c_char_p,
+                                                     _vp, _vp, _vp, _vp, _i32,
+                                                     _vp, _vp, _vp, _vp,
+                                                     _vp]),
+    "ppf_gauss_lsq_join_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32,
+                                                ctypes.c_char_p, _vp, _vp,
+                                                _vp, _vp, _i32, _vp, _vp,
+                                                _vp, _i32, _vp, _vp, _i32,
+                                                _vp, _vp, _vp, _vp,
+                                                ctypes.c_size_t, _vp]),
     "ppf_swt_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32]),
     "ppf_swt_analyse_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _vp,
                                              _vp, _vp, ctypes.c_size_t, _vp]),

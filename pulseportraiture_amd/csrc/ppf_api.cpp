@@ -1771,6 +1771,70 @@ int ppf_gauss_portrait_batch(ppf_ctx *ctx, int32_t nport, int32_t nchan, int32_t
 }
 
 namespace {
+// the join arguments of the joined Gaussian entry points, checked on the
+// host: PPF_OK or the error set
+int check_join(ppf_ctx *ctx, int64_t nrow, int32_t njoin, const int32_t *join_id, const double *join_params,
+               const double *P) {
+    if (njoin < 0) return fail(ctx, PPF_EINVAL, "njoin=%d", njoin);
+    if (nrow > 0 && (!join_id || !P || (njoin > 0 && !join_params)))
+        return fail(ctx, PPF_EINVAL, "join_id / join_params / P is NULL");
+    for (int64_t i = 0; i < nrow; ++i)
+        if (join_id[i] < -1 || join_id[i] >= njoin)
+            return fail(ctx, PPF_EINVAL, "join_id[%lld] = %d: -1 or an archive in [0, %d)", (long long)i,
+                        join_id[i], njoin);
+    return PPF_OK;
+}
+}  // namespace
+
+int ppf_gauss_portrait_join_batch(ppf_ctx *ctx, int32_t nport, int32_t nchan, int32_t nbin,
+                                  int32_t ngauss, const char *model_code, const double *params,
+                                  const double *scattering_index, const double *freqs,
+                                  const double *nu_ref, int32_t njoin, const int32_t *join_id,
+                                  const double *join_params, const double *P, double *out,
+                                  void *stream) {
+    // the rotation needs the even-length LDS transforms (the reference's
+    // irfft returns nbin - 1 bins at odd nbin: it cannot rotate those either)
+    if ((nbin & 1) || nbin < 32 || nbin > 8192 || !nbin_supported(nbin))
+        return fail(ctx, PPF_EUNSUP, "nbin=%d: even lengths in [32, 8192] (the LDS row transforms)", nbin);
+    if (nport < 0 || nchan < 1 || ngauss < 0 ||
+        (nport > 0 && (!params || !scattering_index || !freqs || !nu_ref || !out)))
+        return fail(ctx, PPF_EINVAL, "bad gauss_portrait arguments");
+    int rc;
+    if ((rc = check_join(ctx, (int64_t)(nport > 0 ? nport : 0) * nchan, njoin, join_id, join_params, P))) return rc;
+    if (njoin == 0 || nport == 0)
+        return ppf_gauss_portrait_batch(ctx, nport, nchan, nbin, ngauss, model_code, params, scattering_index,
+                                        freqs, nu_ref, out, stream);
+    if (!ctx) return PPF_EINVAL;
+    if (!model_code) return fail(ctx, PPF_EINVAL, "model_code is NULL");
+    ppf::GaussArgs a{};
+    for (int i = 0; i < 3; ++i) {
+        const char c = model_code[i];
+        if (c != '0' && c != '1')
+            return fail(ctx, PPF_EINVAL, "model_code '%.3s': digit %d must be '0' or '1'", model_code, i);
+        a.code[i] = c - '0';
+    }
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = twiddles(ctx, nbin, st, &a.T, &a.T2))) return rc;
+    a.nport = nport; a.nchan = nchan; a.nbin = nbin; a.log2N = rfft_log2(nbin);
+    a.ngauss = ngauss; a.npar = 2 + 6 * ngauss;
+    a.params = params; a.scat_index = scattering_index; a.freqs = freqs; a.nu_ref = nu_ref;
+    a.out = out; a.Te = a.T; a.T2e = a.T2;
+    // the device copy of join_id in the context's scratch: a synchronous call
+    const size_t jb = sizeof(int32_t) * (size_t)nport * nchan;
+    std::lock_guard<std::mutex> lk(ctx->lscr_mu);
+    if ((rc = lscr_reserve(ctx, align256(jb)))) return rc;
+    if ((e = hipMemcpyAsync(ctx->lscr, join_id, jb, hipMemcpyHostToDevice, st)) != hipSuccess)
+        return hip_fail(ctx, e, "hipMemcpyAsync(join_id)");
+    ppf::GaussJoin j{};
+    j.njoin = njoin; j.join_id = (const int32_t *)ctx->lscr; j.join_params = join_params; j.P = P;
+    if ((e = ppf::launch_gauss_port_join(a, j, st)) != hipSuccess) return hip_fail(ctx, e, "k_gauss_port_join");
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(ctx, e, "hipStreamSynchronize");
+    return PPF_OK;
+}
+
+namespace {
 // workspace of ppf_gauss_lsq_batch: the model rows, the partial tiles and the
 // device copies of free_idx / delta
 struct GaussLsqLayout {
@@ -1800,12 +1864,15 @@ size_t ppf_gauss_lsq_workspace_bytes(int32_t nfit, int32_t nchan, int32_t nbin, 
     return gauss_lsq_layout(nfit, nchan, nbin, nfree, L) ? L.bytes : 0;
 }
 
-int ppf_gauss_lsq_batch(ppf_ctx *ctx, int32_t nfit, int32_t nchan, int32_t nbin, int32_t ngauss,
-                        const char *model_code, const double *params, const double *scattering_index,
-                        const double *freqs, const double *nu_ref, int32_t nfree,
-                        const int32_t *free_idx, const double *delta, int32_t in_dtype,
-                        const void *data, const double *inv_errs, double *gram, void *workspace,
-                        size_t workspace_bytes, void *stream) {
+namespace {
+// ppf_gauss_lsq_batch (jn == nullptr) and ppf_gauss_lsq_join_batch
+int gauss_lsq_run(ppf_ctx *ctx, int32_t nfit, int32_t nchan, int32_t nbin, int32_t ngauss,
+                  const char *model_code, const double *params, const double *scattering_index,
+                  const double *freqs, const double *nu_ref, const ppf::GaussJoin *jn,
+                  const int32_t *join_id, int32_t nfree,
+                  const int32_t *free_idx, const double *delta, int32_t in_dtype,
+                  const void *data, const double *inv_errs, double *gram, void *workspace,
+                  size_t workspace_bytes, void *stream) {
     // every argument check on the host, before the context or any launch
     if ((nbin & 1) || nbin < 32 || nbin > 8192 || !nbin_supported(nbin))
         return fail(ctx, PPF_EUNSUP, "nbin=%d: even lengths in [32, 8192] (the LDS row transforms)", nbin);
@@ -1823,10 +1890,14 @@ int ppf_gauss_lsq_batch(ppf_ctx *ctx, int32_t nfit, int32_t nchan, int32_t nbin,
         a.code[i] = c - '0';
     }
     const int npar = 2 + 6 * ngauss;
+    const int njoin = jn ? jn->njoin : 0, next = npar + 2 * njoin;   // the scattering index's entry
+    int rc;
+    if (jn && (rc = check_join(ctx, (int64_t)(nfit > 0 ? nfit : 0) * nchan, njoin, join_id, jn->join_params, jn->P)))
+        return rc;
     if (nfree > 0 && (!free_idx || (nfit > 0 && !delta))) return fail(ctx, PPF_EINVAL, "free_idx / delta is NULL");
     for (int j = 0; j < nfree; ++j) {
-        if (free_idx[j] < 0 || free_idx[j] > npar || (j > 0 && free_idx[j] <= free_idx[j - 1]))
-            return fail(ctx, PPF_EINVAL, "free_idx[%d] = %d: strictly increasing in [0, %d]", j, free_idx[j], npar);
+        if (free_idx[j] < 0 || free_idx[j] > next || (j > 0 && free_idx[j] <= free_idx[j - 1]))
+            return fail(ctx, PPF_EINVAL, "free_idx[%d] = %d: strictly increasing in [0, %d]", j, free_idx[j], next);
         for (int f = 0; f < nfit; ++f) {
             const double d = delta[(size_t)f * nfree + j];
             if (!(d != 0.0) || !std::isfinite(d))
@@ -1844,7 +1915,6 @@ int ppf_gauss_lsq_batch(ppf_ctx *ctx, int32_t nfit, int32_t nchan, int32_t nbin,
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
     hipStream_t st = (hipStream_t)stream;
-    int rc;
     if ((rc = twiddles(ctx, nbin, st, &a.T, &a.T2))) return rc;
     char *ws = (char *)workspace;
     if (nfree > 0) {
@@ -1860,8 +1930,48 @@ int ppf_gauss_lsq_batch(ppf_ctx *ctx, int32_t nfit, int32_t nchan, int32_t nbin,
     a.free_idx = (const int32_t *)(ws + L.fidx); a.delta = (const double *)(ws + L.delta);
     a.data = data; a.inv_errs = inv_errs;
     a.rows = (double *)(ws + L.rows); a.part = (double *)(ws + L.part); a.gram = gram;
+    if (njoin > 0) {
+        // the device copy of join_id in the context's scratch: a synchronous call
+        const size_t jb = sizeof(int32_t) * (size_t)nfit * nchan;
+        std::lock_guard<std::mutex> lk(ctx->lscr_mu);
+        if ((rc = lscr_reserve(ctx, align256(jb)))) return rc;
+        if ((e = hipMemcpyAsync(ctx->lscr, join_id, jb, hipMemcpyHostToDevice, st)) != hipSuccess)
+            return hip_fail(ctx, e, "hipMemcpyAsync(join_id)");
+        ppf::GaussJoin j = *jn;
+        j.join_id = (const int32_t *)ctx->lscr;
+        if ((e = ppf::launch_gauss_lsq_join(a, j, st)) != hipSuccess)
+            return hip_fail(ctx, e, "k_gauss_rows_join / k_gauss_gram_join");
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(ctx, e, "hipStreamSynchronize");
+        return PPF_OK;
+    }
     if ((e = ppf::launch_gauss_lsq(a, st)) != hipSuccess) return hip_fail(ctx, e, "k_gauss_rows / k_gauss_gram");
     return PPF_OK;
+}
+}  // namespace
+
+int ppf_gauss_lsq_batch(ppf_ctx *ctx, int32_t nfit, int32_t nchan, int32_t nbin, int32_t ngauss,
+                        const char *model_code, const double *params, const double *scattering_index,
+                        const double *freqs, const double *nu_ref, int32_t nfree,
+                        const int32_t *free_idx, const double *delta, int32_t in_dtype,
+                        const void *data, const double *inv_errs, double *gram, void *workspace,
+                        size_t workspace_bytes, void *stream) {
+    return gauss_lsq_run(ctx, nfit, nchan, nbin, ngauss, model_code, params, scattering_index, freqs, nu_ref,
+                         nullptr, nullptr, nfree, free_idx, delta, in_dtype, data, inv_errs, gram, workspace,
+                         workspace_bytes, stream);
+}
+
+int ppf_gauss_lsq_join_batch(ppf_ctx *ctx, int32_t nfit, int32_t nchan, int32_t nbin, int32_t ngauss,
+                             const char *model_code, const double *params, const double *scattering_index,
+                             const double *freqs, const double *nu_ref, int32_t njoin,
+                             const int32_t *join_id, const double *join_params, const double *P,
+                             int32_t nfree, const int32_t *free_idx, const double *delta,
+                             int32_t in_dtype, const void *data, const double *inv_errs, double *gram,
+                             void *workspace, size_t workspace_bytes, void *stream) {
+    ppf::GaussJoin j{};
+    j.njoin = njoin; j.join_params = join_params; j.P = P;
+    return gauss_lsq_run(ctx, nfit, nchan, nbin, ngauss, model_code, params, scattering_index, freqs, nu_ref, &j,
+                         join_id, nfree, free_idx, delta, in_dtype, data, inv_errs, gram, workspace,
+                         workspace_bytes, stream);
 }
 
 namespace {

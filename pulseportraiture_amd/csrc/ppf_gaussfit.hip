@@ -18,6 +18,12 @@
 //                  written as the chunk's partial tile.
 //   k_gauss_gram_fin  sums the partial tiles in chunk order and writes both
 //                  triangles.  No atomics: the result is bitwise reproducible.
+//
+// The joined model (ppf_gauss_portrait_join_batch, ppf_gauss_lsq_join_batch:
+// several archives, each rotated by a phase and a DM of its own):
+// k_gauss_port_join, k_gauss_rows_join and k_gauss_gram_join take the join
+// arguments (GaussJoin) as a second kernel argument and build an archive's
+// rows with gp_build_row<..., ROT>; the kernels above are as they were.
 #include <hip/hip_runtime.h>
 
 #include "ppf_device.hpp"
@@ -55,6 +61,94 @@ __global__ __launch_bounds__(kBlock) void k_gauss_rows(GaussLsqArgs a) {
     for (int j = threadIdx.x; j < N; j += kBlock) o[j] = lds[j];   // nbin is even here
 }
 
+// the rotation of a row of archive id (>= 0) at frequency f, rotate_data's
+// order of operations (pplib.py:2478-2504); jp: the fit's join parameters,
+// entry pq (an index into them, < 0: none) read as jp[pq] + dj
+__device__ __forceinline__ double join_rot(const double *jp, int id, int pq, double dj, double P, double f,
+                                           double nu_ref) {
+#pragma clang fp contract(off)
+    const double phi = pq == 2 * id ? jp[2 * id] + dj : jp[2 * id];
+    const double DM = pq == 2 * id + 1 ? jp[2 * id + 1] + dj : jp[2 * id + 1];
+    const double D = kDconst * DM / P;
+    const double fterm = pow(f, -2.0) - pow(nu_ref, -2.0);
+    return phi + D * fterm;
+}
+
+// k_gauss_rows of the joined model (even nbin): free_idx indexes [params,
+// join params, scattering index].  A column that perturbs a join parameter
+// of another archive than the row's equals m(p): its workgroup builds
+// nothing, and k_gauss_gram_join reads no row there.
+template <int KMAX, bool MX>
+__global__ __launch_bounds__(kBlock) void k_gauss_rows_join(GaussLsqArgs a, GaussJoin jn) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) double2 lds[];
+    __shared__ double red[kWaves * 2];
+    const int nbin = a.nbin, N = nbin >> 1, ncol = a.nfree + 1;
+    const int col = blockIdx.x % ncol;
+    const int n = (blockIdx.x / ncol) % a.nchan, fit = blockIdx.x / (ncol * a.nchan);
+    const int id = jn.join_id[(int64_t)fit * a.nchan + n];
+    const int next = a.npar + 2 * jn.njoin;
+    int pj = -1;
+    double dj = 0.0;
+    if (col < a.nfree) {
+        pj = a.free_idx[col];
+        dj = a.delta[(int64_t)fit * a.nfree + col];
+    }
+    const int pq = pj >= a.npar && pj < next ? pj - a.npar : -1;
+    if (pq >= 0 && (pq >> 1) != id) return;   // (block-uniform)
+    const double *prm = a.params + (int64_t)fit * a.npar;
+    const double f = a.freqs[(int64_t)fit * a.nchan + n], nu_ref = a.nu_ref[fit];
+    const double tau = pj == 1 ? prm[1] + dj : prm[1];
+    const double alpha = pj == next ? a.scat_index[fit] + dj : a.scat_index[fit];
+    GpRow kind;
+    if (id >= 0) {
+        const double rot = join_rot(jn.join_params + (int64_t)fit * 2 * jn.njoin, id, pq, dj, jn.P[fit], f, nu_ref);
+        kind = gp_build_row<KMAX, MX, true, true>(lds, red, nbin, a.ngauss, a.code[0], a.code[1], a.code[2], prm, pj,
+                                                  dj, tau, alpha, f, nu_ref, a.T, a.T2, a.T, a.T2, rot);
+    } else {
+        kind = gp_build_row<KMAX, MX, true>(lds, red, nbin, a.ngauss, a.code[0], a.code[1], a.code[2], prm, pj, dj,
+                                            tau, alpha, f, nu_ref, a.T, a.T2, a.T, a.T2);
+    }
+    double2 *o = reinterpret_cast<double2 *>(a.rows) + (int64_t)blockIdx.x * N;
+    if (kind == kGpPacked) {
+        const double sc = 1.0 / (double)N;
+        for (int j = threadIdx.x; j < N; j += kBlock) o[j] = cscale(lds[j], sc);
+        return;
+    }
+    for (int j = threadIdx.x; j < N; j += kBlock) o[j] = lds[j];
+}
+
+// k_gauss_port of the joined model (even nbin within the LDS transforms): a
+// row of no archive (join_id < 0) is built by the unrotated code
+template <int KMAX, bool MX>
+__global__ __launch_bounds__(kBlock) void k_gauss_port_join(GaussArgs a, GaussJoin jn) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) double2 lds[];
+    __shared__ double red[kWaves * 2];
+    const int nbin = a.nbin, N = nbin >> 1;
+    const int p = blockIdx.x / a.nchan, n = blockIdx.x % a.nchan;
+    const double *prm = a.params + (int64_t)p * a.npar;
+    const double f = a.freqs[(int64_t)p * a.nchan + n], nu_ref = a.nu_ref[p];
+    const int id = jn.join_id[blockIdx.x];
+    GpRow kind;
+    if (id >= 0) {
+        const double rot = join_rot(jn.join_params + (int64_t)p * 2 * jn.njoin, id, -1, 0.0, jn.P[p], f, nu_ref);
+        kind = gp_build_row<KMAX, MX, false, true>(lds, red, nbin, a.ngauss, a.code[0], a.code[1], a.code[2], prm, -1,
+                                                   0.0, prm[1], a.scat_index[p], f, nu_ref, a.T, a.T2, a.Te, a.T2e,
+                                                   rot);
+    } else {
+        kind = gp_build_row<KMAX, MX, false>(lds, red, nbin, a.ngauss, a.code[0], a.code[1], a.code[2], prm, -1, 0.0,
+                                             prm[1], a.scat_index[p], f, nu_ref, a.T, a.T2, a.Te, a.T2e);
+    }
+    double2 *o = reinterpret_cast<double2 *>(a.out) + (int64_t)blockIdx.x * N;
+    if (kind == kGpPacked) {
+        const double sc = 1.0 / (double)N;
+        for (int j = threadIdx.x; j < N; j += kBlock) o[j] = cscale(lds[j], sc);
+        return;
+    }
+    for (int j = threadIdx.x; j < N; j += kBlock) o[j] = lds[j];
+}
+
 // tile pair index -> (ti <= tj), row-major over the upper triangle
 __device__ __forceinline__ void gram_pair(int pair, int ntile, int &ti, int &tj) {
     ti = 0;
@@ -63,7 +157,11 @@ __device__ __forceinline__ void gram_pair(int pair, int ntile, int &ti, int &tj)
     tj = ti + pair;
 }
 
-__global__ __launch_bounds__(kBlock) void k_gauss_gram(GaussLsqArgs a) {
+// JOIN: a column that perturbs a join parameter of another archive than the
+// channel's is exact zeros over the channel (k_gauss_rows_join built no row
+// there: none is read)
+template <bool JOIN>
+__device__ __forceinline__ void gauss_gram_body(const GaussLsqArgs &a, const GaussJoin &jn) {
 #pragma clang fp contract(off)
     __shared__ double sh[kWaves][256];
     const int nbin = a.nbin, nfree = a.nfree, ncol = nfree + 1;
@@ -85,6 +183,18 @@ __global__ __launch_bounds__(kBlock) void k_gauss_gram(GaussLsqArgs a) {
     const double da = ia < nfree ? a.delta[(int64_t)fit * nfree + ia] : 1.0;
     const double db = ib < nfree ? a.delta[(int64_t)fit * nfree + ib] : 1.0;
     const bool needd = ia == nfree || ib == nfree;
+    bool za = false, zb = false;   // the column is zero over this channel
+    if constexpr (JOIN) {
+        const int id = jn.join_id[rowch], next = a.npar + 2 * jn.njoin;
+        if (ia < nfree) {
+            const int pa = a.free_idx[ia];
+            za = pa >= a.npar && pa < next && ((pa - a.npar) >> 1) != id;
+        }
+        if (ib < nfree) {
+            const int pb = a.free_idx[ib];
+            zb = pb >= a.npar && pb < next && ((pb - a.npar) >> 1) != id;
+        }
+    }
     const int kend = min(nbin, (seg + 1) * kGramSeg);
     typedef double d4 __attribute__((ext_vector_type(4)));
     d4 acc = {0.0, 0.0, 0.0, 0.0};
@@ -98,7 +208,14 @@ __global__ __launch_bounds__(kBlock) void k_gauss_gram(GaussLsqArgs a) {
                 const int k = k0 + s;
                 const bool in = k < kend;
                 const double m0 = in ? mb[k] : 0.0, wk = in ? w[k] : 0.0;
-                const double xa = in ? ma[k] : 0.0, xb = in ? mc[k] : 0.0;
+                double xa, xb;
+                if constexpr (JOIN) {
+                    xa = in && !za ? ma[k] : 0.0;
+                    xb = in && !zb ? mc[k] : 0.0;
+                } else {
+                    xa = in ? ma[k] : 0.0;
+                    xb = in ? mc[k] : 0.0;
+                }
                 double dk = 0.0;
                 if (in && needd) dk = a.dtype == 0 ? (double)d32[k] : d64[k];
                 double ca = 0.0, cb = 0.0;
@@ -107,6 +224,10 @@ __global__ __launch_bounds__(kBlock) void k_gauss_gram(GaussLsqArgs a) {
                     else if (ia == nfree) ca = (dk - m0) * wk;
                     if (ib < nfree) cb = ((xb - m0) / db) * wk;
                     else if (ib == nfree) cb = (dk - m0) * wk;
+                    if constexpr (JOIN) {
+                        if (za) ca = 0.0;
+                        if (zb) cb = 0.0;
+                    }
                 }
                 va[s] = ca;
                 vb[s] = cb;
@@ -122,6 +243,14 @@ __global__ __launch_bounds__(kBlock) void k_gauss_gram(GaussLsqArgs a) {
     const int t = threadIdx.x;
     const double s = ((sh[0][t] + sh[1][t]) + sh[2][t]) + sh[3][t];
     a.part[(((int64_t)fit * gridDim.x + chunk) * a.npair + pair) * 256 + t] = s;
+}
+
+__global__ __launch_bounds__(kBlock) void k_gauss_gram(GaussLsqArgs a) {
+    gauss_gram_body<false>(a, GaussJoin{});
+}
+
+__global__ __launch_bounds__(kBlock) void k_gauss_gram_join(GaussLsqArgs a, GaussJoin jn) {
+    gauss_gram_body<true>(a, jn);
 }
 
 __global__ __launch_bounds__(kBlock) void k_gauss_gram_fin(GaussLsqArgs a, int nchunk) {
@@ -171,6 +300,57 @@ hipError_t launch_gauss_lsq(const GaussLsqArgs &a, hipStream_t st) {
     hipLaunchKernelGGL(k_gauss_gram, dim3((unsigned)nchunk, (unsigned)a.npair, (unsigned)a.nfit), b, 0, st, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(k_gauss_gram_fin, dim3((unsigned)a.npair, (unsigned)a.nfit), b, 0, st, a, nchunk);
+    return hipGetLastError();
+}
+
+#define GROWSJ(K)                                                                       \
+    do {                                                                                \
+        if (mx) hipLaunchKernelGGL((k_gauss_rows_join<K, true>), g, b, lds, st, a, j);  \
+        else hipLaunchKernelGGL((k_gauss_rows_join<K, false>), g, b, lds, st, a, j);    \
+    } while (0)
+
+hipError_t launch_gauss_lsq_join(const GaussLsqArgs &a, const GaussJoin &j, hipStream_t st) {
+    const size_t lds = (size_t)(a.nbin / 2) * sizeof(double2);
+    const int ncol = a.nfree + 1;
+    dim3 g((unsigned)((int64_t)a.nfit * a.nchan * ncol)), b(kBlock);
+    const bool mx = !is_pow2(a.nbin / 2);
+    switch (kmax_pow2(a.nbin / 2)) {
+        case 1: GROWSJ(1); break;
+        case 2: GROWSJ(2); break;
+        case 4: GROWSJ(4); break;
+        case 8: GROWSJ(8); break;
+        case 16: GROWSJ(16); break;
+        default: return hipErrorInvalidValue;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int nchunk = a.nchan * a.nseg;
+    hipLaunchKernelGGL(k_gauss_gram_join, dim3((unsigned)nchunk, (unsigned)a.npair, (unsigned)a.nfit), b, 0, st, a,
+                       j);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_gauss_gram_fin, dim3((unsigned)a.npair, (unsigned)a.nfit), b, 0, st, a, nchunk);
+    return hipGetLastError();
+}
+
+#define GPORTJ(K)                                                                       \
+    do {                                                                                \
+        if (mx) hipLaunchKernelGGL((k_gauss_port_join<K, true>), g, b, lds, st, a, j);  \
+        else hipLaunchKernelGGL((k_gauss_port_join<K, false>), g, b, lds, st, a, j);    \
+    } while (0)
+
+// even nbin within the LDS transforms (checked by the caller)
+hipError_t launch_gauss_port_join(const GaussArgs &a, const GaussJoin &j, hipStream_t st) {
+    const size_t lds = (size_t)(a.nbin / 2) * sizeof(double2);
+    dim3 g((unsigned)((int64_t)a.nport * a.nchan)), b(kBlock);
+    const bool mx = !is_pow2(a.nbin / 2);
+    switch (kmax_pow2(a.nbin / 2)) {
+        case 1: GPORTJ(1); break;
+        case 2: GPORTJ(2); break;
+        case 4: GPORTJ(4); break;
+        case 8: GPORTJ(8); break;
+        case 16: GPORTJ(16); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -1,8 +1,8 @@
-// One row of pplib.gen_gaussian_portrait (pplib.py:886-963, join_ichans = [])
-// in a workgroup's LDS: the row builder shared by k_gauss_port (model
-// portraits) and k_gauss_rows (the columns of the Gaussian least-squares
-// problem, ppf_gaussfit.hip), so both produce the same bits.  Per component:
-// the evolved loc/wid/amp (evolve_parameter pplib.py:1032-1084), the wrapped,
+// One row of pplib.gen_gaussian_portrait (pplib.py:886-963) in a workgroup's
+// LDS: the row builder shared by k_gauss_port (model portraits), k_gauss_rows
+// (the columns of the Gaussian least-squares problem, ppf_gaussfit.hip) and
+// their joined variants (join_ichans: ROT below), so all produce the same
+// bits.  Per component: the evolved loc/wid/amp (evolve_parameter pplib.py:1032-1084), the wrapped,
 // truncated Gaussian of gaussian_profile (pplib.py:801-856) with its unit-peak
 // factor taken at the first argmax (a block reduction), accumulated into the
 // LDS row in component order as gen_gaussian_profile does (pplib.py:859-883).
@@ -55,13 +55,24 @@ enum GpRow {
 // PERT: entry pj of prm is read as prm[pj] + dj (pj < 0: none; the
 // forward-difference columns of ppf_gauss_lsq_batch); tau and alpha are
 // passed already so.
+// ROT (even nbin only): the row of an archive of a joined model
+// (gen_gaussian_portrait's join_ichans, pplib.py:956-962), rotated by rot
+// [rot] as rotate_data does (pplib.py:2447-2512).  The rotation is folded
+// into the scattering multiply: harmonic k is multiplied by B_k e^{2 pi i k
+// rot} (B_k = 1 when tau == 0) in ONE transform round trip, which a row with
+// rot == 0 takes too, so that the rows of a forward difference in a join
+// parameter are built alike.  The reference's irfft between the two steps
+// drops the imaginary parts of the DC and Nyquist bins BEFORE the phasor:
+// they are zeroed here after the B_k multiply, and again after the phasor
+// (the final irfft).  Without ROT rot is not read and the function compiles
+// to what it was.
 // Every thread of the workgroup calls it; LDS is readable on return.
-template <int KMAX, bool MX, bool PERT>
+template <int KMAX, bool MX, bool PERT, bool ROT = false>
 __device__ __forceinline__ GpRow gp_build_row(double2 *lds, double *red, int nbin, int ngauss, int code0,
                                               int code1, int code2, const double *prm, int pj, double dj,
                                               double tau, double alpha, double f, double nu_ref,
                                               const double2 *T, const double2 *T2, const double2 *Te,
-                                              const double2 *T2e) {
+                                              const double2 *T2e, double rot = 0.0) {
 #pragma clang fp contract(off)
     double *row = reinterpret_cast<double *>(lds);
     const int N = nbin >> 1;
@@ -112,6 +123,39 @@ __device__ __forceinline__ GpRow gp_build_row(double2 *lds, double *red, int nbi
     // (the scattered branch first: with the unscattered return ahead of it
     // k_gauss_port<4, false> takes 130 VGPRs instead of 125, one wave less
     // per SIMD, and 2048-bin portraits build 3-8 % slower)
+    if constexpr (ROT) {
+        const double tn = tau != 0.0 ? tau / (double)nbin * pow(f / nu_ref, alpha) : 0.0;
+        __syncthreads();
+        lds_fft_n<MX>(lds, N, T, false);
+        double2 Xk[KMAX], Xn[KMAX];
+#pragma unroll
+        for (int i = 0; i < KMAX; ++i) {
+            const int k = threadIdx.x + i * kBlock;
+            if (k < N) {
+                double2 X1 = rfft_bin(lds, N, T2, k);
+                double2 X2 = rfft_bin(lds, N, T2, N - k);
+                if (tn != 0.0) {
+                    X1 = cmul(X1, scat_recip((2.0 * kPi * (double)k) * tn));
+                    X2 = cmul(X2, scat_recip((2.0 * kPi * (double)(N - k)) * tn));
+                }
+                if (k == 0) { X1.y = 0.0; X2.y = 0.0; }   // the scattering irfft: DC, Nyquist real
+                X1 = cmul(X1, cexp2pi((double)k * rot));
+                X2 = cmul(X2, cexp2pi((double)(N - k) * rot));
+                if (k == 0) { X1.y = 0.0; X2.y = 0.0; }   // the rotation's irfft
+                Xk[i] = X1;
+                Xn[i] = X2;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < KMAX; ++i) {
+            const int k = threadIdx.x + i * kBlock;
+            if (k < N) lds[k] = irfft_prebin(Xk[i], Xn[i], T2[k]);
+        }
+        __syncthreads();
+        lds_fft_n<MX>(lds, N, T, true);
+        return kGpPacked;
+    }
     if (tau != 0.0) {
         // taus = (tau / nbin) * (freqs / nu_ref)**alpha; B_k = 1 / (1 + 2 pi i k tau_n)
         const double tn = tau / (double)nbin * pow(f / nu_ref, alpha);

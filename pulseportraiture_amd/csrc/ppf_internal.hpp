@@ -457,6 +457,21 @@ struct GaussLsqArgs {
 };
 hipError_t launch_gauss_lsq(const GaussLsqArgs &a, hipStream_t st);
 
+// The joined model (gen_gaussian_portrait's join_ichans, pplib.py:956-962):
+// the rows of archive a = join_id[row] are rotated by phi_a + Dconst DM_a /
+// P (nu^-2 - nu_ref^-2).  A second kernel argument of the joined kernels
+// (ppf_gaussfit.hip), so GaussArgs / GaussLsqArgs and the unjoined kernels
+// stay as they are.  The extended parameter vector of the joined fit is
+// [params (npar), join_params (2 njoin), scattering index].
+struct GaussJoin {
+    int njoin;
+    const int32_t *join_id;      // [nport | nfit][nchan] (device copy): archive, -1 = not rotated
+    const double *join_params;   // [nport | nfit][2 njoin]: phase [rot], DM per archive
+    const double *P;             // [nport | nfit] period [s]
+};
+hipError_t launch_gauss_port_join(const GaussArgs &a, const GaussJoin &j, hipStream_t st);
+hipError_t launch_gauss_lsq_join(const GaussLsqArgs &a, const GaussJoin &j, hipStream_t st);
+
 // ppf_swt_analyse_batch / ppf_swt_score_batch (ppf_swt.hip): the stationary
 // db8 wavelet transform of profiles and the denoise-and-score cases of
 // pplib.smart_smooth

@@ -1015,14 +1015,35 @@ def phase_shift_batch(data, model, noise=None, Ns=100, bounds=(-0.5, 0.5),
     return out
 
 
+def _join_args(join_id, join_params, P, n, nchan, dev):
+    """The join arguments of the joined Gaussian entry points: join_id
+    [n, nchan] int32 on the HOST (the archive of each channel, -1: none),
+    join_params [n, 2 njoin] (phase [rot], DM per archive) and P [n] [s] on
+    the device."""
+    if join_params is None or P is None:
+        raise ValueError("join_id needs join_params and P")
+    ji = np.ascontiguousarray(np.broadcast_to(
+        np.asarray(join_id, dtype=np.int32).reshape(-1, nchan), (n, nchan)))
+    jp = to_dev(join_params, dev, torch.float64).reshape(n, -1).contiguous()
+    if jp.shape[1] % 2:
+        raise ValueError("join_params must hold (phase, DM) per archive")
+    Pd = to_dev(np.broadcast_to(np.asarray(P, dtype=float), (n,)), dev,
+                torch.float64).contiguous()
+    return ji, jp, Pd, jp.shape[1] // 2
+
+
 def gauss_portraits(model_code, params, scattering_index, freqs, nu_ref, nbin,
-                    dev=None):
+                    dev=None, join_id=None, join_params=None, P=None):
     """Gaussian-component model portraits (pplib.gen_gaussian_portrait,
     pplib.py:886-963) on the device: params [nport, 2 + 6 ngauss] (DC, tau
     [bin], per component loc, m_loc, wid, m_wid, amp, m_amp),
     scattering_index [nport], freqs [nport, nchan], nu_ref [nport] ->
     float64 [nport, nchan, nbin] (odd nbin with tau != 0: nbin - 1 bins, as
-    the reference's length-less irfft gives, then a zero column)."""
+    the reference's length-less irfft gives, then a zero column).
+    join_id [nport, nchan] (the archive of each channel, -1: none) with
+    join_params [nport, 2 njoin] (phase [rot], DM per archive) and P [nport]
+    [s] rotates each archive's rows as gen_gaussian_portrait(join_ichans=...)
+    does (ppf_gauss_portrait_join_batch; even nbin in [32, 8192])."""
     code = str(model_code)
     if len(code) != 3 or any(c not in "01" for c in code):
         raise KeyError(code)     # evolve_parameter's dictionary lookup
@@ -1042,6 +1063,15 @@ def gauss_portraits(model_code, params, scattering_index, freqs, nu_ref, nbin,
     out = torch.empty((nport, nchan, int(nbin)), dtype=torch.float64,
                       device=dev)
     ctx = _lib.context(dev.index)
+    if join_id is not None:
+        ji, jp, Pd, njoin = _join_args(join_id, join_params, P, nport, nchan,
+                                       dev)
+        rc = _lib.load().ppf_gauss_portrait_join_batch(
+            ctx, nport, nchan, int(nbin), (npar - 2) // 6, code.encode(),
+            _p(prm), _p(si), _p(f), _p(nr), njoin, ji.ctypes.data, _p(jp),
+            _p(Pd), _p(out), _stream(dev))
+        _lib.check(rc, ctx)
+        return out
     rc = _lib.load().ppf_gauss_portrait_batch(
         ctx, nport, nchan, int(nbin), (npar - 2) // 6, code.encode(),
         _p(prm), _p(si), _p(f), _p(nr), _p(out), _stream(dev))
@@ -1050,7 +1080,8 @@ def gauss_portraits(model_code, params, scattering_index, freqs, nu_ref, nbin,
 
 
 def gauss_lsq(model_code, params, scattering_index, freqs, nu_ref, free_idx,
-              delta, data, inv_errs, dev=None, workspace=None):
+              delta, data, inv_errs, dev=None, workspace=None, join_id=None,
+              join_params=None, P=None):
     """Normal equations of the Gaussian portrait model on the device
     (ppf_gauss_lsq_batch): for each of nfit fits the Gram matrix C C^T of
     the forward-difference Jacobian columns ((m(p + delta_j e_j) - m(p)) /
@@ -1062,7 +1093,10 @@ def gauss_lsq(model_code, params, scattering_index, freqs, nu_ref, free_idx,
     inv_errs [nfit, nchan, nbin] -> float64 [nfit, nfree + 1, nfree + 1]
     on the device: J^T J, J^T r in the last column, chi^2 in the corner.
     workspace: a uint8 device tensor to reuse between calls (any size; a
-    larger one is allocated when it is too small)."""
+    larger one is allocated when it is too small).
+    join_id / join_params / P as for gauss_portraits
+    (ppf_gauss_lsq_join_batch): free_idx then indexes [params, join_params,
+    scattering index], the index at npar + 2 njoin."""
     code = str(model_code)
     if len(code) != 3 or any(c not in "01" for c in code):
         raise KeyError(code)     # evolve_parameter's dictionary lookup
@@ -1104,11 +1138,21 @@ def gauss_lsq(model_code, params, scattering_index, freqs, nu_ref, free_idx,
     gram = torch.empty((nfit, nfree + 1, nfree + 1), dtype=torch.float64,
                        device=dev)
     ctx = _lib.context(dev.index)
-    rc = lib.ppf_gauss_lsq_batch(
-        ctx, nfit, nchan, nbin, (npar - 2) // 6, code.encode(), _p(prm),
-        _p(si), _p(f), _p(nr), nfree, fi.ctypes.data, dl.ctypes.data,
-        _lib.PPF_F32 if ddt == torch.float32 else _lib.PPF_F64, _p(d), _p(w),
-        _p(gram), _p(workspace), workspace.numel(), _stream(dev))
+    if join_id is not None:
+        ji, jp, Pd, njoin = _join_args(join_id, join_params, P, nfit, nchan,
+                                       dev)
+        rc = lib.ppf_gauss_lsq_join_batch(
+            ctx, nfit, nchan, nbin, (npar - 2) // 6, code.encode(), _p(prm),
+            _p(si), _p(f), _p(nr), njoin, ji.ctypes.data, _p(jp), _p(Pd),
+            nfree, fi.ctypes.data, dl.ctypes.data,
+            _lib.PPF_F32 if ddt == torch.float32 else _lib.PPF_F64, _p(d),
+            _p(w), _p(gram), _p(workspace), workspace.numel(), _stream(dev))
+    else:
+        rc = lib.ppf_gauss_lsq_batch(
+            ctx, nfit, nchan, nbin, (npar - 2) // 6, code.encode(), _p(prm),
+            _p(si), _p(f), _p(nr), nfree, fi.ctypes.data, dl.ctypes.data,
+            _lib.PPF_F32 if ddt == torch.float32 else _lib.PPF_F64, _p(d),
+            _p(w), _p(gram), _p(workspace), workspace.numel(), _stream(dev))
     _lib.check(rc, ctx)
     # free_idx / delta are host arrays the stream still reads
     torch.cuda.current_stream(dev).synchronize()
@@ -1118,12 +1162,14 @@ def gauss_lsq(model_code, params, scattering_index, freqs, nu_ref, free_idx,
 class GaussLsqEvaluator:
     """The device evaluator of _gaussfit.levenberg_marquardt for ONE fit:
     (p_ext, free_idx, delta) -> Gram matrix (numpy), p_ext the parameters
-    with the scattering index appended.  The data, weights and workspace
+    with the scattering index appended; with join_id [nchan] (the archive
+    of each channel, -1: none) and P [s], p_ext is [params, 2 njoin join
+    parameters, scattering index].  The data, weights and workspace
     stay on the device between calls.  time_kernels=True brackets each call
     with HIP events; kernel_ms then lists the device time of every call."""
 
     def __init__(self, model_code, data, inv_errs, freqs, nu_ref, dev=None,
-                 time_kernels=False):
+                 time_kernels=False, join_id=None, P=None, njoin=None):
         self.dev = device(dev)
         self.code = model_code
         data = np.asarray(data) if not isinstance(data, torch.Tensor) else data
@@ -1133,6 +1179,15 @@ class GaussLsqEvaluator:
         self.w = to_dev(inv_errs, self.dev, torch.float64).unsqueeze(0)
         self.freqs = to_dev(freqs, self.dev, torch.float64).reshape(1, -1)
         self.nu_ref = float(nu_ref)
+        self.join_id = None
+        self.njoin = 0
+        if join_id is not None:
+            if P is None:
+                raise ValueError("join_id needs P")
+            self.join_id = np.ascontiguousarray(join_id, dtype=np.int32)
+            self.njoin = int(self.join_id.max()) + 1 if njoin is None \
+                else int(njoin)
+            self.P = float(P)
         self.ws = None
         self.time_kernels = time_kernels
         self.kernel_ms = []
@@ -1149,9 +1204,17 @@ class GaussLsqEvaluator:
             e0 = torch.cuda.Event(enable_timing=True)
             e1 = torch.cuda.Event(enable_timing=True)
             e0.record()
-        g = gauss_lsq(self.code, p_ext[None, :-1], [p_ext[-1]], self.freqs,
-                      [self.nu_ref], free_idx, delta, self.data, self.w,
-                      dev=self.dev, workspace=self.ws)
+        if self.join_id is not None:
+            npar = len(p_ext) - 1 - 2 * self.njoin
+            g = gauss_lsq(self.code, p_ext[None, :npar], [p_ext[-1]],
+                          self.freqs, [self.nu_ref], free_idx, delta,
+                          self.data, self.w, dev=self.dev, workspace=self.ws,
+                          join_id=self.join_id[None, :],
+                          join_params=p_ext[None, npar:-1], P=[self.P])
+        else:
+            g = gauss_lsq(self.code, p_ext[None, :-1], [p_ext[-1]],
+                          self.freqs, [self.nu_ref], free_idx, delta,
+                          self.data, self.w, dev=self.dev, workspace=self.ws)
         if self.time_kernels:
             e1.record()
             e1.synchronize()

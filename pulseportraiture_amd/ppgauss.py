@@ -2,17 +2,23 @@
 portrait models fitted on the device.
 
 ``DataPortrait(datafile).make_gaussian_model(...)`` is the reference's
-workflow (ppgauss.py:62-245) for ONE archive: the evolving-Gaussian model is
-fitted to the dedispersed, time-averaged portrait with
-pplib.fit_gaussian_portrait (ppf_gauss_lsq_batch under a Levenberg-Marquardt
-driver), the residual phase / DM offset between data and model is measured
-with fit_phase_shift + fit_portrait, the data are rotated by it and the fit
-is repeated until the offset is within its errors.  The written .gmodel is
-what pptoas.GetTOAs reads.
+workflow (ppgauss.py:62-245): the evolving-Gaussian model is fitted to the
+dedispersed, time-averaged portrait with pplib.fit_gaussian_portrait
+(ppf_gauss_lsq_batch under a Levenberg-Marquardt driver), the residual phase
+/ DM offset between data and model is measured with fit_phase_shift +
+fit_portrait, the data are rotated by it and the fit is repeated until the
+offset is within its errors.  The written .gmodel is what pptoas.GetTOAs
+reads.
 
-Outside the accelerated path (NotImplementedError): metafiles (several
-archives joined in one fit), joinfiles, the interactive GaussianSelector and
-every plot.
+A metafile of several archives of one pulsar (or a list of DataBunches) is
+fitted with ONE model: every archive gets a phase and a DM offset of its own
+(the join parameters), fitted with the model on the device
+(ppf_gauss_lsq_join_batch).  The data are then not rotated between
+iterations; the join parameters are appended to the join file after every
+fit, and port, portx and model are de-rotated by them at the end.
+
+Outside the accelerated path (NotImplementedError): the interactive
+GaussianSelector, rotate_stuff and every plot.
 """
 import time
 
@@ -29,19 +35,21 @@ _OUTSIDE = "%s is outside the accelerated path"
 
 
 class DataPortrait(_DataPortrait):
-    """The data a Gaussian model is fitted to (pplib.py:155-349 for a single
-    archive, with ppgauss.py's methods).  datafile: a fold-mode PSRFITS file
-    (loaded with dedisperse=True, tscrunch=True on the PSRFITS fast path) or
-    an in-memory DataBunch with load_data's keys (subints [nsub, npol,
-    nchan, nbin], masks, freqs [nsub, nchan], ok_ichans, noise_stds, SNRs
-    [nsub, npol, nchan], Ps, phases, nu0, bw, source); its first
-    sub-integration is the portrait."""
+    """The data a Gaussian model is fitted to (pplib.py:155-349, with
+    ppgauss.py's methods).  datafile: a fold-mode PSRFITS file (loaded with
+    dedisperse=True, tscrunch=True on the PSRFITS fast path) or an in-memory
+    DataBunch with load_data's keys (subints [nsub, npol, nchan, nbin],
+    masks, freqs [nsub, nchan], ok_ichans, noise_stds, SNRs [nsub, npol,
+    nchan], Ps, phases, nu0, bw, source); its first sub-integration is the
+    portrait.  A metafile, or a list of DataBunches, joins several archives
+    (see pplib.DataPortrait)."""
 
     def __init__(self, datafile=None, joinfile=None, quiet=False,
                  **load_data_kwargs):
         self.init_params = []
         _DataPortrait.__init__(self, datafile, joinfile, quiet,
                                **load_data_kwargs)
+        self.init_params = []
 
     def fit_profile(self, profile, tau=0.0, fixscat=True, auto_gauss=0.0,
                     profile_fit_flags=None, show=True):
@@ -158,10 +166,12 @@ class DataPortrait(_DataPortrait):
         while self.niter and not self.cnvrgnc:
             if not quiet:
                 print("\n...iteration %d..." % (self.itern - self.niter + 1))
-            self.port = rotate_data(self.port, self.phi, self.DM, self.Ps[0],
-                                    self.freqs[0], self.nu_fit)
-            self.portx = rotate_data(self.portx, self.phi, self.DM,
-                                     self.Ps[0], self.freqsxs[0], self.nu_fit)
+            if not self.njoin:
+                self.port = rotate_data(self.port, self.phi, self.DM,
+                                        self.Ps[0], self.freqs[0], self.nu_fit)
+                self.portx = rotate_data(self.portx, self.phi, self.DM,
+                                         self.Ps[0], self.freqsxs[0],
+                                         self.nu_fit)
             next(iterator)
             self.niter -= 1
             self.cnvrgnc = self.check_convergence(efac=1.0, quiet=quiet)
@@ -170,6 +180,22 @@ class DataPortrait(_DataPortrait):
                 self.write_model(outfile=outfile, quiet=quiet)
             if writeerrfile:
                 self.write_errfile(errfile=errfile, quiet=quiet)
+        # ppgauss.py:213-231: the archives aligned with the fitted model
+        for ii in range(self.njoin):
+            phi, DM = -self.join_params[0::2][ii], -self.join_params[1::2][ii]
+            jic, jicx = self.join_ichans[ii], self.join_ichanxs[ii]
+            self.port[jic] = rotate_data(self.port[jic], phi, DM, self.Ps[0],
+                                         self.freqs[0, jic], self.nu_ref)
+            self.portx[jicx] = rotate_data(self.portx[jicx], phi, DM,
+                                           self.Ps[0], self.freqsxs[0][jicx],
+                                           self.nu_ref)
+            self.model[jic] = rotate_data(self.model[jic], phi, DM,
+                                          self.Ps[0], self.freqs[0, jic],
+                                          self.nu_ref)
+        if self.njoin:
+            mask = np.asarray(self.masks[0, 0])
+            self.model_masked = self.model * mask
+            self.modelx = self.model[mask.mean(axis=1) != 0]
         if not quiet:
             print("Residuals std:  %.2e" % (self.portx - self.modelx).std())
             print("Data std:       %.2e" % np.median(self.noise_stdsxs))
@@ -189,11 +215,21 @@ class DataPortrait(_DataPortrait):
             self.scattering_index = fgp.scattering_index
             self.scattering_index_err = fgp.scattering_index_err
             self.fgp = fgp
-            self.model_params = self.fitted_params[:]
-            self.model_param_errs = self.fit_errs[:]
+            if self.njoin:
+                nj = 2 * self.njoin
+                self.model_params = self.fitted_params[:-nj]
+                self.model_param_errs = self.fit_errs[:-nj]
+                self.join_params = self.fitted_params[-nj:]
+                self.join_param_errs = self.fit_errs[-nj:]
+                self.all_join_params[1] = self.join_params
+                self.write_join_parameters()
+            else:
+                self.model_params = self.fitted_params[:]
+                self.model_param_errs = self.fit_errs[:]
             self.model = gen_gaussian_portrait(
                 self.model_code, self.fitted_params, self.scattering_index,
-                self.phases, self.freqs[0], self.nu_ref)
+                self.phases, self.freqs[0], self.nu_ref, self.join_ichans,
+                self.Ps[0])
             mask = np.asarray(self.masks[0, 0])
             self.model_masked = self.model * mask
             self.modelx = self.model[mask.mean(axis=1) != 0]
@@ -205,12 +241,26 @@ class DataPortrait(_DataPortrait):
         """ppgauss.py:285-341: the phase and DM of the data against the
         fitted model (fit_phase_shift for the guess, fit_portrait for both);
         converged (1) when each is within efac of its error, else 0."""
-        phase_guess = fit_phase_shift(self.portx.mean(axis=0),
-                                      self.modelx.mean(axis=0)).phase
+        portx, modelx = self.portx, self.modelx
+        if self.njoin:
+            # data and model with every archive's join rotation taken out
+            portx, modelx = np.zeros(portx.shape), np.zeros(modelx.shape)
+            for ii in range(self.njoin):
+                jicx = self.join_ichanxs[ii]
+                phi = -self.join_params[0::2][ii]
+                DM = -self.join_params[1::2][ii]
+                portx[jicx] = rotate_data(self.portx[jicx], phi, DM,
+                                          self.Ps[0], self.freqsxs[0][jicx],
+                                          self.nu_ref)
+                modelx[jicx] = rotate_data(self.modelx[jicx], phi, DM,
+                                           self.Ps[0], self.freqsxs[0][jicx],
+                                           self.nu_ref)
+        phase_guess = fit_phase_shift(portx.mean(axis=0),
+                                      modelx.mean(axis=0)).phase
         phase_guess %= 1
         if phase_guess >= 0.5:
             phase_guess -= 1.0
-        fp = fit_portrait(self.portx, self.modelx,
+        fp = fit_portrait(portx, modelx,
                           np.array([phase_guess, 0.0]), self.Ps[0],
                           self.freqsxs[0], self.nu_fit, None, None,
                           bounds=[(None, None), (None, None)], id=None,

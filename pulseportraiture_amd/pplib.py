@@ -181,14 +181,41 @@ def gaussian_profile(nbin, loc, wid, norm=False, abs_wid=False, zeroout=True):
                                  1.0)[0]
 
 
+def _join_ids(join_ichans, nchan):
+    """join_ichans (one list of channel indices per archive) -> the archive
+    of each channel, int32 [nchan], -1 for a channel in none.  A channel
+    listed by two archives would be rotated twice by the reference; that is
+    refused."""
+    join_id = np.full(nchan, -1, dtype=np.int32)
+    for ia, ichans in enumerate(join_ichans):
+        ichans = np.arange(nchan)[np.asarray(ichans)]
+        if np.any(join_id[ichans] >= 0):
+            raise ValueError("join_ichans: a channel belongs to two archives")
+        join_id[ichans] = ia
+    return join_id
+
+
 def gen_gaussian_portrait(model_code, params, scattering_index, phases, freqs,
                           nu_ref, join_ichans=[], P=None):
-    """pplib.py:886-963 for join_ichans == [], built on the device by
-    ppf_gauss_portrait_batch (k_gauss_port)."""
-    if len(join_ichans):
-        raise NotImplementedError("join_ichans (ppgauss only) is out of scope")
+    """pplib.py:886-963, built on the device by ppf_gauss_portrait_batch
+    (k_gauss_port).  With join_ichans (one list of channel indices per
+    archive) params carries 2 len(join_ichans) trailing values, (phase, DM)
+    per archive, and the period P [s] is needed: each archive's rows are
+    rotated in the same kernel (ppf_gauss_portrait_join_batch; even nbin in
+    [32, 8192], anything else raises NotImplementedError)."""
     from . import engine
     params = np.asarray(params, dtype=float)
+    njoin = len(join_ichans)
+    if njoin:
+        if P is None:
+            raise ValueError("join_ichans needs the period P")
+        join_id = _join_ids(join_ichans, len(freqs))
+        out = engine.gauss_portraits(
+            model_code, params[None, :-2 * njoin], [scattering_index],
+            np.asarray(freqs, dtype=float)[None, :], [nu_ref], len(phases),
+            join_id=join_id[None, :], join_params=params[None, -2 * njoin:],
+            P=[P])
+        return out[0].cpu().numpy()
     out = engine.gauss_portraits(model_code, params[None, :],
                                  [scattering_index],
                                  np.asarray(freqs, dtype=float)[None, :],
@@ -221,17 +248,19 @@ def gen_gaussian_profile(params, nbin):
 
 
 def _gauss_fit(model_code, data, params, alpha, errs, vary, freqs, nu_ref,
-               evaluator):
+               evaluator, join_id=None, P=None, njoin=0):
     """The Levenberg-Marquardt fit both Gaussian fits share
-    (_gaussfit.levenberg_marquardt on ppf_gauss_lsq_batch)."""
+    (_gaussfit.levenberg_marquardt on ppf_gauss_lsq_batch).  With join_id
+    (the archive of each channel) params ends in the 2 njoin join values."""
     from . import _gaussfit
     data = np.asarray(data)
     errs = np.broadcast_to(np.asarray(errs, dtype=float), data.shape)
     if evaluator is None:
         evaluator = engine.GaussLsqEvaluator(model_code, data, 1.0 / errs,
-                                             freqs, nu_ref)
+                                             freqs, nu_ref, join_id=join_id,
+                                             P=P, njoin=njoin)
     p0 = np.append(np.asarray(params, dtype=float), float(alpha))
-    lo, hi = _gaussfit.portrait_bounds(len(p0) - 1)
+    lo, hi = _gaussfit.portrait_bounds(len(p0) - 1 - 2 * njoin, njoin)
     return _gaussfit.levenberg_marquardt(evaluator, p0, vary, lo, hi,
                                          data.size)
 
@@ -292,22 +321,39 @@ def fit_gaussian_portrait(model_code, data, init_params, scattering_index,
     fitted_params, fit_errs, scattering_index, scattering_index_err, chi2,
     dof); lm_results has message, nfev, success, covar and residual (the
     weighted residuals, flat).  A fixed parameter's error is 0.0 (lmfit
-    gives None).  join_params (several archives in one fit) is outside the
-    accelerated path.  evaluator (not in the reference) replaces the device
+    gives None).  join_params = [join_ichans, values, flags] fits several
+    archives at once (pplib.py:2073-2098): values / flags hold (phase, DM)
+    per archive, P [s] is the period, and fitted_params / fit_errs end in
+    the join values, as the reference returns them (ppf_gauss_lsq_join_batch;
+    even nbin).  evaluator (not in the reference) replaces the device
     evaluator, see _gaussfit."""
-    if len(join_params):
-        raise NotImplementedError("fit_gaussian_portrait(join_params=...) is "
-                                  "outside the accelerated path")
     data = np.asarray(data)
     errs = np.broadcast_to(np.asarray(errs, dtype=float), data.shape)
-    vary = np.append(np.asarray(fit_flags, dtype=float) != 0,
-                     bool(fit_scattering_index))
+    init_params = np.asarray(init_params, dtype=float)
+    flags = np.asarray(fit_flags, dtype=float) != 0
+    join_ichans, join_id = [], None
+    if len(join_params):
+        join_ichans = join_params[0]
+        if P is None:
+            # (the reference divides by None in rotate_data)
+            raise NotImplementedError("fit_gaussian_portrait(join_params="
+                                      "...) without the period P")
+        if len(join_params[1]) != 2 * len(join_ichans) or \
+                len(join_params[2]) != 2 * len(join_ichans):
+            raise ValueError("join_params: (phase, DM) values and flags per "
+                             "archive")
+        join_id = _join_ids(join_ichans, data.shape[0])
+        init_params = np.append(init_params,
+                                np.asarray(join_params[1], dtype=float))
+        flags = np.append(flags, np.asarray(join_params[2], dtype=float) != 0)
+    vary = np.append(flags, bool(fit_scattering_index))
     p, perr, chi2, dof, lm_results = _gauss_fit(
         model_code, data, init_params, scattering_index, errs, vary,
-        np.asarray(freqs, dtype=float), nu_ref, evaluator)
+        np.asarray(freqs, dtype=float), nu_ref, evaluator, join_id, P,
+        len(join_ichans))
     if evaluator is None:
         model = gen_gaussian_portrait(model_code, p[:-1], p[-1], phases,
-                                      freqs, nu_ref)
+                                      freqs, nu_ref, join_ichans, P)
         lm_results.residual = np.ravel((data - model) / errs)
     if not quiet:
         print("Gaussian Portrait Fit")
@@ -1423,32 +1469,66 @@ _OUTSIDE = "%s is outside the accelerated path"
 
 
 class DataPortrait(object):
-    """The data a portrait model is made from (pplib.py:155-349 for a single
-    archive); ppgauss.DataPortrait and ppspline.DataPortrait add their
-    model makers.  datafile: a fold-mode PSRFITS file (loaded with
-    dedisperse=True, tscrunch=True on the PSRFITS fast path) or an in-memory
-    DataBunch with load_data's keys (subints [nsub, npol, nchan, nbin],
-    masks, freqs [nsub, nchan], ok_ichans, noise_stds, SNRs [nsub, npol,
-    nchan], Ps, phases, nu0, bw, source; weights [nsub, nchan], unit on
-    ok_ichans when missing); its first sub-integration is the portrait."""
+    """The data a portrait model is made from (pplib.py:155-349);
+    ppgauss.DataPortrait and ppspline.DataPortrait add their model makers.
+    datafile: a fold-mode PSRFITS file (loaded with dedisperse=True,
+    tscrunch=True on the PSRFITS fast path) or an in-memory DataBunch with
+    load_data's keys (subints [nsub, npol, nchan, nbin], masks, freqs [nsub,
+    nchan], ok_ichans, noise_stds, SNRs [nsub, npol, nchan], Ps, phases,
+    nu0, bw, source; weights [nsub, nchan], unit on ok_ichans when missing);
+    its first sub-integration is the portrait.
+
+    A metafile (an ASCII list of fold-mode PSRFITS files, one per line) or,
+    not in the reference, a list / tuple of DataBunches joins several
+    archives of one pulsar (pplib.py:179-326): their channels are
+    concatenated and sorted by frequency, join_ichans / join_ichanxs list
+    each archive's channels in the sorted full / condensed portrait, and
+    join_params holds a (phase, DM) pair per archive: the first archive's
+    phase 0 and fixed, every other phase started at
+    -fit_phase_shift(prof, first prof).phase, every DM 0, all free.  A bunch
+    without prof gets the mean of its ok rows.  joinfile (the output of
+    write_join_parameters, either format) overrides the start values."""
 
     def __init__(self, datafile=None, joinfile=None, quiet=False,
                  **load_data_kwargs):
-        if joinfile is not None:
-            raise NotImplementedError(_OUTSIDE % "DataPortrait(joinfile=...)")
-        self.joinfile = None
+        self.init_params = []
         self.njoin = 0
         self.join_params = []
         self.join_ichans = []
         self.all_join_params = []
+        bunches = None
+        if isinstance(datafile, (list, tuple)):
+            bunches = list(datafile)
+            names = [str(b.get("filename", "DataBunch%d" % i))
+                     for i, b in enumerate(bunches)]
+            self.metafile = self.datafile = "DataBunches"
+        elif not isinstance(datafile, dict) and \
+                file_is_type(datafile, "ASCII"):
+            with open(datafile) as fh:
+                names = [line.strip() for line in fh if line.strip()]
+            for name in names:
+                # PSRCHIVE reads the other formats in the reference
+                if not (os.path.isfile(name) and file_is_type(name, "FITS")):
+                    raise NotImplementedError(
+                        _OUTSIDE % ("DataPortrait(metafile): '%s' is not a "
+                                    "PSRFITS file, which" % name))
+            bunches = [load_data(name, dedisperse=True, dededisperse=False,
+                                 tscrunch=True, pscrunch=True, fscrunch=False,
+                                 quiet=quiet, **load_data_kwargs)
+                       for name in names]
+            self.metafile = self.datafile = datafile
+        if bunches is not None:
+            self.joinfile = joinfile
+            self._join_archives(bunches, names)
+            return
+        if joinfile is not None:
+            raise NotImplementedError(_OUTSIDE % "DataPortrait(joinfile=...) "
+                                      "with a single archive")
+        self.joinfile = None
         if isinstance(datafile, dict):
             self.datafile = datafile.get("filename", "DataBunch")
             self.data = datafile
         else:
-            if file_is_type(datafile, "ASCII"):
-                raise NotImplementedError(
-                    _OUTSIDE % "DataPortrait(metafile): joining several "
-                    "archives")
             self.datafile = datafile
             self.data = load_data(datafile, dedisperse=True,
                                   dededisperse=False, tscrunch=True,
@@ -1471,6 +1551,155 @@ class DataPortrait(object):
         if getattr(self, "weights", None) is None:
             self.weights = np.zeros((1, self.nchan))
             self.weights[0, ok] = 1.0
+
+    def _join_archives(self, bunches, names):
+        """The metafile branch of pplib.py:179-326 on loaded archives."""
+        if not bunches:
+            raise ValueError("no archive to join")
+        self.datafiles = list(names)
+        self.njoin = len(bunches)
+        self.join_nchans, self.join_nchanxs = [0], [0]
+        join_params, join_fit_flags = [], []
+        freqs, freqsxs, masks, port, portx = [], [], [], [], []
+        noise, noisex, snrs, snrsx, wts, wtsx = [], [], [], [], [], []
+        self.nchans = []
+        self.Ps = 0.0
+        self.lofreq, self.hifreq = np.inf, 0.0
+        refprof = None
+        for ia, data in enumerate(bunches):
+            sub = np.asarray(data["subints"][0, 0], dtype=float)
+            mask = np.asarray(data["masks"][0, 0], dtype=float)
+            nchan, nbin = sub.shape
+            ok = np.asarray(data["ok_ichans"][0], dtype=int)
+            f = np.asarray(data["freqs"], dtype=float)[0]
+            prof = data.get("prof", None)
+            if prof is None:
+                prof = sub[ok].mean(axis=0)
+            prof = np.asarray(prof, dtype=float)
+            if ia == 0:
+                self.nbin = nbin
+                self.phases = np.asarray(data["phases"])
+                self.source = data.get("source", None) or "noname"
+                refprof = prof
+                join_params += [0.0, 0.0]
+                join_fit_flags += [0, 1]
+            else:
+                if nbin != self.nbin:
+                    raise ValueError("archive '%s' has nbin=%d, the first "
+                                     "one %d: joined archives need the same "
+                                     "nbin" % (names[ia], nbin, self.nbin))
+                phi = -fit_phase_shift(prof, refprof, Ns=self.nbin).phase
+                join_params += [phi, 0.0]
+                join_fit_flags += [1, 1]
+            self.nchans.append(nchan)
+            self.join_nchans.append(self.join_nchans[-1] + nchan)
+            self.join_nchanxs.append(self.join_nchanxs[-1] + len(ok))
+            self.Ps += float(np.mean(data["Ps"]))
+            half = abs(float(data["bw"])) / (2 * nchan)
+            self.lofreq = min(self.lofreq, f.min() - half)
+            self.hifreq = max(self.hifreq, f.max() + half)
+            w = data.get("weights", None)
+            if w is None:
+                w = np.zeros((1, nchan))
+                w[0, ok] = 1.0
+            w = np.asarray(w, dtype=float)[0]
+            ns = np.asarray(data["noise_stds"], dtype=float)[0, 0]
+            sn = np.asarray(data["SNRs"], dtype=float)[0, 0]
+            freqs.append(f), freqsxs.append(f[ok]), masks.append(mask)
+            port.append(sub * mask), portx.append(sub[ok])
+            noise.append(ns), noisex.append(ns[ok])
+            snrs.append(sn), snrsx.append(sn[ok])
+            wts.append(w), wtsx.append(w[ok])
+        self.nchan, self.nchanx = self.join_nchans[-1], self.join_nchanxs[-1]
+        self.Ps = [self.Ps / self.njoin]
+        self.bw = self.hifreq - self.lofreq
+        freqs, freqsxs = np.concatenate(freqs), np.concatenate(freqsxs)
+        self.nu0 = freqs.mean()
+        self.isort, self.isortx = np.argsort(freqs), np.argsort(freqsxs)
+        self.join_ichans, self.join_ichanxs = [], []
+        for ia in range(self.njoin):
+            self.join_ichans.append(np.flatnonzero(
+                (self.isort >= self.join_nchans[ia]) &
+                (self.isort < self.join_nchans[ia + 1])))
+            self.join_ichanxs.append(np.flatnonzero(
+                (self.isortx >= self.join_nchanxs[ia]) &
+                (self.isortx < self.join_nchanxs[ia + 1])))
+        self.masks = np.concatenate(masks)[self.isort][None, None]
+        self.port = np.concatenate(port)[self.isort]
+        self.portx = np.concatenate(portx)[self.isortx]
+        self.flux_prof = self.port.mean(axis=1)
+        self.flux_profx = self.portx.mean(axis=1)
+        self.noise_stds = np.concatenate(noise)[self.isort][None, None]
+        self.noise_stdsxs = np.concatenate(noisex)[self.isortx]
+        self.SNRs = np.concatenate(snrs)[self.isort][None, None]
+        self.SNRsxs = np.concatenate(snrsx)[self.isortx]
+        self.weights = np.concatenate(wts)[self.isort][None]
+        self.weightsxs = np.concatenate(wtsx)[self.isortx][None]
+        self.ok_ichans = [np.flatnonzero(self.masks[0, 0].mean(axis=1) > 0)]
+        self.freqs = freqs[self.isort][None]
+        self.freqsxs = [freqsxs[self.isortx]]
+        self.join_params = np.array(join_params, dtype=float)
+        self.join_fit_flags = np.array(join_fit_flags)
+        if self.joinfile:
+            self._read_joinfile()
+        self.all_join_params = [self.join_ichanxs, self.join_params,
+                                self.join_fit_flags]
+
+    def _read_joinfile(self):
+        """pplib.py:300-315: the last njoin lines of the join file, either
+        format (old: name phi DM; new: name phi err DM err), matched to the
+        archives by name.  (The reference parses the DM with np.float, which
+        current NumPy no longer has: its reader always prints "Bad join
+        file."; plain float here.)"""
+        with open(self.joinfile) as fh:
+            lines = [line.split() for line in fh.readlines()[-self.njoin:]]
+        try:
+            vals = []
+            for info in lines:
+                ijoin = self.datafiles.index(info[0])
+                phi = float(info[1])
+                DM = float(info[3]) if len(info) > 3 else float(info[2])
+                vals.append((ijoin, phi, DM))
+        except (ValueError, IndexError):
+            print("Bad join file.")
+            return
+        for ijoin, phi, DM in vals:
+            self.join_params[ijoin * 2] = phi
+            self.join_params[ijoin * 2 + 1] = DM
+
+    def apply_joinfile(self, nu_ref, undo=False):
+        """pplib.py:351-370: rotate every archive's channels of port and
+        portx by the negated join parameters at nu_ref (the fitted model's
+        reference frequency); undo=True rotates back."""
+        sign = (-1) ** int(undo)
+        for ii in range(self.njoin):
+            phi = -self.join_params[0::2][ii] * sign
+            DM = -self.join_params[1::2][ii] * sign
+            jic, jicx = self.join_ichans[ii], self.join_ichanxs[ii]
+            self.port[jic] = rotate_data(self.port[jic], phi, DM, self.Ps[0],
+                                         self.freqs[0, jic], nu_ref)
+            self.portx[jicx] = rotate_data(self.portx[jicx], phi, DM,
+                                           self.Ps[0],
+                                           self.freqsxs[0][jicx], nu_ref)
+
+    def write_join_parameters(self):
+        """pplib.py:508-543: append the join parameters and their errors to
+        the join file (joinfile, or model_name + '.join'), the reference's
+        line format byte for byte.  The values are the NEGATIVES of the
+        rotations that align the data (rotate_data)."""
+        joinfile = self.joinfile if self.joinfile is not None \
+            else self.model_name + ".join"
+        lines = ["# archive name" + " " * 32 + "-phase offset & err [rot]" +
+                 " " * 2 + "-delta-DM & err [cm**-3 pc]\n"]
+        for ifile, datafile in enumerate(self.datafiles):
+            lines.append(
+                datafile + " " * abs(45 - len(datafile)) +
+                "% .10f" % self.join_params[ifile * 2] + " " +
+                "%.10f" % self.join_param_errs[::2][ifile] + "  " +
+                "% .6f" % self.join_params[ifile * 2 + 1] + " " +
+                "%.6f" % self.join_param_errs[1::2][ifile] + "\n")
+        with open(joinfile, "a") as jf:
+            jf.writelines(lines)
 
     def normalize_portrait(self, method="rms"):
         """pplib.py:379-404: normalize_portrait(...) on the full and the

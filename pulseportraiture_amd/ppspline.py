@@ -33,6 +33,18 @@ class DataPortrait(_DataPortrait):
     """The data a spline model is made from: pplib.DataPortrait (a fold-mode
     PSRFITS file or a DataBunch) with ppspline.py's methods."""
 
+    def __init__(self, datafile=None, joinfile=None, quiet=False,
+                 **load_data_kwargs):
+        from .pplib import file_is_type
+        if isinstance(datafile, (list, tuple)) or (
+                not isinstance(datafile, dict) and
+                file_is_type(datafile, "ASCII")):
+            raise NotImplementedError(
+                _OUTSIDE % "ppspline.DataPortrait(metafile): joining several "
+                "archives")
+        _DataPortrait.__init__(self, datafile, joinfile, quiet,
+                               **load_data_kwargs)
+
     def make_spline_model(self, max_ncomp=10, smooth=True, snr_cutoff=150.0,
                           rchi2_tol=0.1, k=3, sfac=1.0, max_nbreak=None,
                           model_name=None, quiet=False, **kwargs):

@@ -7,7 +7,12 @@ the same Levenberg-Marquardt driver on the NumPy evaluator (the oracle's
 portrait builder, forward differences, C @ C.T) at 64 x 512 for comparison.
 One warm-up fit, then `reps` fits; the median and the min-max spread are
 printed, and one JSON line at the end.
-usage: python tools/gaussfit_time.py [reps] [--no-cpu] [--small]"""
+--join times instead the joined fit (fit_gaussian_portrait(join_params=...),
+ppf_gauss_lsq_join_batch) at 64 x 512 with the example model, the band split
+into two archives of 32 channels, the second offset by (0.004 rot, 3e-4
+cm**-3 pc): the first archive's phase fixed, the other three join parameters
+fitted from (0, 0.005, 0).
+usage: python tools/gaussfit_time.py [reps] [--no-cpu] [--small] [--join]"""
 import json
 import os
 import sys
@@ -75,6 +80,45 @@ def time_device(pb, reps):
                 calls=ncall, chi2_red=float(res.chi2 / res.dof))
 
 
+JOIN_TRUTH = [0.0, 0.0, 0.004, 3e-4]
+
+
+def time_device_join(reps, nchan=64, nbin=512, seed=1):
+    rng = np.random.default_rng(seed)
+    truth = np.asarray(synth.GMODEL_PARAMS, dtype=float)
+    freqs = synth.channel_freqs(nchan)
+    phases = pplib.get_bin_centers(nbin)
+    ichans = [np.arange(nchan // 2), np.arange(nchan // 2, nchan)]
+    P, nu_ref, noise = 0.003, synth.GMODEL_NU_REF, 0.1
+    model = pplib.gen_gaussian_portrait("000", np.r_[truth, JOIN_TRUTH], -4.0,
+                                        phases, freqs, nu_ref, ichans, P)
+    data = model + noise * rng.standard_normal(model.shape)
+    errs = np.full(model.shape, noise)
+    flags = np.ones(len(truth))
+    flags[1] = 0
+    start = np.where(flags != 0, truth * 1.02, truth)
+    join_id = pplib._join_ids(ichans, nchan)
+    wall, kern = [], []
+    for r in range(reps + 1):
+        ev = engine.GaussLsqEvaluator("000", data, 1.0 / errs, freqs, nu_ref,
+                                      time_kernels=True, join_id=join_id,
+                                      P=P, njoin=2)
+        t0 = time.perf_counter()
+        res = pplib.fit_gaussian_portrait(
+            "000", data, start, -4.0, errs, flags, False, phases, freqs,
+            nu_ref, join_params=[ichans, [0.0, 0.0, 0.005, 0.0],
+                                 [0, 1, 1, 1]], P=P, evaluator=ev)
+        dt = time.perf_counter() - t0
+        if r:
+            wall.append(dt * 1e3)
+            kern.append(sum(ev.kernel_ms))
+        assert res.lm_results.success, res.lm_results.message
+    return dict(wall_ms=stats(wall), evaluator_ms=stats(kern),
+                nfev=res.lm_results.nfev, calls=len(ev.kernel_ms),
+                chi2_red=float(res.chi2 / res.dof),
+                join_params=[float(v) for v in res.fitted_params[-4:]])
+
+
 def time_numpy(pb, reps):
     import oracle as O
     code, freqs, phases = "000", pb["freqs"], pb["phases"]
@@ -98,6 +142,10 @@ def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     reps = int(args[0]) if args else 5
     out = {}
+    if "--join" in sys.argv:
+        out["64x512_g3_join2"] = time_device_join(reps)
+        print(json.dumps(out))
+        return
     shapes = [(64, 512, 3)] + ([] if "--small" in sys.argv else [(512, 2048, 10)])
     for nchan, nbin, ngauss in shapes:
         pb = problem(nchan, nbin, ngauss)
