@@ -834,6 +834,57 @@ int ppf_fake_batch(ppf_ctx *ctx, int32_t nsub, int32_t npol, int32_t nchan, int3
                    const double *noise, uint64_t seed, int64_t first_sub, int32_t out_kind,
                    void *out, float *dat_scl, float *dat_offs, void *stream);
 
+/* The portrait likelihood evaluated at many parameter points (added within
+ * ABI 6: purely additive): chi'^2 = -sum_n C_n^2 / S_n of
+ * pptoaslib.fit_portrait_full_function (pptoaslib.py:564-581), its gradient
+ * (_deriv, 584-614) and Hessian (_2deriv, 617-684), at npoint vectors
+ * theta = (phi, DM, GM, tau, alpha) for each of nprob problems; a problem is
+ * one (data_FT, model_FT) pair as the reference's functions take it.
+ * Device arrays, f64 unless said otherwise:
+ *   data_FT  [nprob][nchan][nharm]   complex128 (re, im), channel-major
+ *   model_FT [nmodel][nchan][nharm]  complex128; problem s uses model
+ *            model_index[s] (int32 [nprob]); model_index NULL: model s
+ *            (nmodel == nprob) or the one model (nmodel == 1)
+ *   errs_FT, freqs [nprob][nchan];  P [nprob];  nus [nprob][3] = nu_DM,
+ *            nu_GM, nu_tau;  mask [nprob][nchan] uint8 or NULL (0 drops the
+ *            channel: it adds exactly 0 to every sum and its data, which may
+ *            be NaN, are never loaded)
+ *   theta    [nprob][npoint][5];  fit_flags [5] or NULL (all 1): the gradient
+ *            is multiplied by flags_i, the Hessian by flags_i flags_j
+ *   log10_tau: tau = 10^theta_3 and the derivatives are with respect to theta_3
+ *   order    0: f; 1: f and grad; 2: f, grad and hess
+ *   f [nprob][npoint], grad [nprob][npoint][5], hess [nprob][npoint][5][5]
+ *            (both triangles); grad / hess may be NULL below their order
+ *   terms    NULL, or [nprob][npoint][62][nchan]: per channel C, S, dC[5],
+ *            dS[5], d2C[5][5], d2S[5][5] (rows 0, 1, 2..6, 7..11, 12..36,
+ *            37..61), the quantities of the reference's Cdbp* / Sbp* family;
+ *            derivatives past `order` are 0
+ * nharm is any value >= 2 (no transform is taken); harmonic 0 is summed as
+ * given; the per-channel phase is not wrapped (phase_shifts, mod = False).
+ * Linear tau = 0: B = 1 and every tau / alpha derivative is exactly 0 (the
+ * reference's taus.sum() branches).  Where the reference divides 0 / 0 (a
+ * channel with C = 0, a channel exactly at nu_tau) the closed-form finite
+ * value is returned.  The points of a block of ppf_eval_point_block() share
+ * one load of a channel's spectra; all sums run in a fixed order without
+ * atomics, so results are bitwise reproducible, the same for a point however
+ * the points are split over calls, and the same with a channel masked or
+ * deleted.  The workspace holds the per-channel contributions
+ * (ppf_eval_workspace_bytes; 0 for a bad shape).
+ * PPF_EINVAL, before anything touches the device: a NULL ctx, nprob < 0,
+ * nchan < 1, nharm < 2, npoint < 1, nmodel < 1, an order outside 0..2, a
+ * model_index missing where nmodel is neither 1 nor nprob; then nprob == 0
+ * returns PPF_OK; then a NULL array, more than 2^31 - 1 workgroups
+ * (nprob x ceil(npoint / block) x nchan); a short workspace is PPF_ENOMEM. */
+int ppf_eval_point_block(void);
+int ppf_eval_harm_tile(void);
+size_t ppf_eval_workspace_bytes(int32_t nprob, int32_t nchan, int32_t npoint, int32_t order);
+int ppf_eval_batch(ppf_ctx *ctx, int32_t nprob, int32_t nchan, int32_t nharm, int32_t npoint,
+                   const double *data_FT, const double *model_FT, int32_t nmodel,
+                   const int32_t *model_index, const double *errs_FT, const double *P,
+                   const double *freqs, const double *nus, const uint8_t *mask, const double *theta,
+                   const double *fit_flags, int32_t log10_tau, int32_t order, double *f, double *grad,
+                   double *hess, double *terms, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Host-side (CPU) helper: real roots of a degree <= 8 polynomial, highest
  * power first, with np.roots semantics (companion-matrix eigenvalues with an
  * exactly zero imaginary part; pptoaslib.py:834-836, 902-904).  Returns the

@@ -173,6 +173,13 @@ SIGNATURES = {
                                       _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64,
                                       ctypes.c_int64, _i32, _vp, _vp, _vp,
                                       _vp]),
+    "ppf_eval_point_block": (ctypes.c_int, []),
+    "ppf_eval_harm_tile": (ctypes.c_int, []),
+    "ppf_eval_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32, _i32]),
+    "ppf_eval_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp,
+                                      _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _i32, _i32, _vp, _vp, _vp, _vp,
+                                      _vp, ctypes.c_size_t, _vp]),
     "ppf_unpack_workspace_bytes": (ctypes.c_size_t, [_i32, _i32, _i32]),
     "ppf_unpack_psrfits_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32,
                                                 _i32, _vp, ctypes.c_int64,

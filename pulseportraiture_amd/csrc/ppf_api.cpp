@@ -1482,6 +1482,49 @@ int ppf_scales_batch(ppf_ctx *ctx, int32_t nsub, int32_t nchan, int32_t nharm, c
     return PPF_OK;
 }
 
+int ppf_eval_point_block(void) { return ppf::kEvalPointBlock; }
+int ppf_eval_harm_tile(void) { return ppf::kEvalTile; }
+
+size_t ppf_eval_workspace_bytes(int32_t nprob, int32_t nchan, int32_t npoint, int32_t order) {
+    if (nprob < 1 || nchan < 1 || npoint < 1 || order < 0 || order > 2) return 0;
+    return (size_t)ppf::eval_partials(nprob, nchan, npoint, order) * sizeof(double) + 256;
+}
+
+int ppf_eval_batch(ppf_ctx *ctx, int32_t nprob, int32_t nchan, int32_t nharm, int32_t npoint,
+                   const double *data_FT, const double *model_FT, int32_t nmodel,
+                   const int32_t *model_index, const double *errs_FT, const double *P,
+                   const double *freqs, const double *nus, const uint8_t *mask, const double *theta,
+                   const double *fit_flags, int32_t log10_tau, int32_t order, double *f, double *grad,
+                   double *hess, double *terms, void *workspace, size_t workspace_bytes, void *stream) {
+    if (!ctx) return PPF_EINVAL;
+    if (nprob < 0 || nchan < 1 || nharm < 2 || npoint < 1 || nmodel < 1)
+        return fail(ctx, PPF_EINVAL, "bad eval shape: nprob %d nchan %d nharm %d npoint %d nmodel %d", nprob,
+                    nchan, nharm, npoint, nmodel);
+    if (order < 0 || order > 2) return fail(ctx, PPF_EINVAL, "eval order %d not 0, 1 or 2", order);
+    if (!model_index && nmodel != 1 && nmodel != nprob)
+        return fail(ctx, PPF_EINVAL, "eval: %d models for %d problems need a model_index", nmodel, nprob);
+    if (nprob == 0) return PPF_OK;
+    if (!data_FT || !model_FT || !errs_FT || !P || !freqs || !nus || !theta || !f || (order >= 1 && !grad) ||
+        (order >= 2 && !hess) || !workspace)
+        return fail(ctx, PPF_EINVAL, "null eval pointer");
+    const int64_t npb = ((int64_t)npoint + ppf::kEvalPointBlock - 1) / ppf::kEvalPointBlock;
+    if ((int64_t)nprob * npb > INT32_MAX / (int64_t)nchan || (int64_t)nprob * npoint > INT32_MAX)
+        return fail(ctx, PPF_EINVAL, "eval: more than 2^31 - 1 workgroups; split the points over calls");
+    if (workspace_bytes < ppf_eval_workspace_bytes(nprob, nchan, npoint, order))
+        return fail(ctx, PPF_ENOMEM, "eval workspace %zu < %zu", workspace_bytes,
+                    ppf_eval_workspace_bytes(nprob, nchan, npoint, order));
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
+    ppf::EvalArgs a{};
+    a.nprob = nprob; a.nchan = nchan; a.nharm = nharm; a.npoint = npoint; a.nmodel = nmodel;
+    a.order = order; a.log10_tau = log10_tau ? 1 : 0;
+    a.D = (const double2 *)data_FT; a.M = (const double2 *)model_FT; a.model_index = model_index;
+    a.errs = errs_FT; a.P = P; a.freqs = freqs; a.nus = nus; a.mask = mask; a.theta = theta;
+    a.flags = fit_flags; a.part = (double *)workspace; a.f = f; a.g = grad; a.H = hess; a.terms = terms;
+    if ((e = ppf::launch_eval(a, (hipStream_t)stream)) != hipSuccess) return hip_fail(ctx, e, "k_eval");
+    return PPF_OK;
+}
+
 size_t ppf_unpack_workspace_bytes(int32_t nsub, int32_t nchan, int32_t nbin) {
     if (nsub < 0 || nchan < 1 || nbin < 2) return 0;
     return ppf::unpack_partials(nsub, nchan, nbin) * sizeof(double) + 256;

@@ -380,6 +380,30 @@ struct ScalesArgs {
 };
 hipError_t launch_scales(const ScalesArgs &a, hipStream_t st);
 
+// The likelihood at many parameter points (ppf_eval.hip): f, gradient,
+// Hessian and the per-channel terms of ppf_eval_batch
+constexpr int kEvalPointBlock = 8;   // points that share one load of a channel's spectra
+constexpr int kEvalTile = 1024;      // harmonics staged in LDS at a time
+constexpr int kEvalTerms = 62;       // C, S, dC[5], dS[5], d2C[5][5], d2S[5][5]
+struct EvalArgs {
+    int nprob, nchan, nharm, npoint, nmodel, order, log10_tau;
+    const double2 *D;            // [nprob][nchan][nharm] data spectra
+    const double2 *M;            // [nmodel][nchan][nharm] model spectra
+    const int32_t *model_index;  // [nprob] or null (model s, or model 0 when nmodel == 1)
+    const double *errs;          // [nprob][nchan] errs_FT
+    const double *P;             // [nprob]
+    const double *freqs;         // [nprob][nchan]
+    const double *nus;           // [nprob][3] nu_DM, nu_GM, nu_tau
+    const uint8_t *mask;         // [nprob][nchan] or null
+    const double *theta;         // [nprob][npoint][5]
+    const double *flags;         // [5] or null (all 1)
+    double *part;                // workspace: [nprob][npoint][nchan][1 | 6 | 21]
+    double *f, *g, *H;           // [nprob][npoint] ([5], [5][5]); g / H unused below their order
+    double *terms;               // [nprob][npoint][kEvalTerms][nchan] or null
+};
+int64_t eval_partials(int64_t nprob, int64_t nchan, int64_t npoint, int order);   // doubles in part
+hipError_t launch_eval(const EvalArgs &a, hipStream_t st);
+
 // PSRFITS fast path (ppf_psrfits.hip): raw SUBINT DATA bytes -> float32
 // rows (total intensity, or all four polarisations), baseline window,
 // per-row statistics

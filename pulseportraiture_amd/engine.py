@@ -988,6 +988,175 @@ def scales_batch(D, M, params, P, freqs, nus, log10_tau, errs_FT=None,
     return out
 
 
+EVAL_TERMS = 62      # C, S, dC[5], dS[5], d2C[5][5], d2S[5][5] per channel
+
+
+def eval_point_block():
+    """Points that share one load of a channel's spectra in ppf_eval_batch."""
+    return int(_lib.load().ppf_eval_point_block())
+
+
+def _shape(x):
+    return tuple(x.shape) if isinstance(x, torch.Tensor) else np.shape(x)
+
+
+def _eval_shapes(theta, data_FT, model_FT, errs_FT, P, freqs, nus, fit_flags,
+                 order, mask, model_index):
+    """Shape checks of eval_points, on the host arrays' shapes alone (no
+    device needed): returns (nprob, npoint, nchan, nharm, nmodel)."""
+    ds = _shape(data_FT)
+    if len(ds) == 2:
+        ds = (1,) + ds
+    if len(ds) != 3:
+        raise ValueError("data_FT must be [nchan, nharm] or [nprob, nchan, "
+                         "nharm], got %s" % (ds,))
+    nprob, nchan, nharm = ds
+    if nprob < 1 or nchan < 1 or nharm < 2:
+        raise ValueError("data_FT %s: need nprob >= 1, nchan >= 1, nharm >= 2"
+                         % (ds,))
+    ms = _shape(model_FT)
+    if len(ms) == 2:
+        ms = (1,) + ms
+    if len(ms) != 3 or ms[1:] != (nchan, nharm) or ms[0] < 1:
+        raise ValueError("model_FT %s != [*, %d, %d]" % (ms, nchan, nharm))
+    nmodel = ms[0]
+    ts = _shape(theta)
+    if len(ts) == 2:
+        ts = (1,) + ts
+    if len(ts) != 3 or ts[2] != 5 or ts[0] != nprob or ts[1] < 1:
+        raise ValueError("theta %s != [%d, K >= 1, 5]" % (ts, nprob))
+    for name, x, inner in (("errs_FT", errs_FT, nchan),
+                           ("freqs", freqs, nchan), ("nus", nus, 3)):
+        n = int(np.prod(_shape(x), dtype=np.int64))
+        if n not in (inner, nprob * inner):
+            raise ValueError("%s has %d elements, not %d or %d" %
+                             (name, n, inner, nprob * inner))
+    n = int(np.prod(_shape(P), dtype=np.int64))
+    if n not in (1, nprob):
+        raise ValueError("P has %d elements, not 1 or %d" % (n, nprob))
+    if mask is not None:
+        n = int(np.prod(_shape(mask), dtype=np.int64))
+        if n not in (nchan, nprob * nchan):
+            raise ValueError("mask has %d elements, not %d or %d" %
+                             (n, nchan, nprob * nchan))
+    if fit_flags is not None and \
+            int(np.prod(_shape(fit_flags), dtype=np.int64)) != 5:
+        raise ValueError("fit_flags must have 5 entries")
+    if order not in (0, 1, 2):
+        raise ValueError("order must be 0, 1 or 2, not %r" % (order,))
+    if model_index is None:
+        if nmodel not in (1, nprob):
+            raise ValueError("%d models for %d problems need a model_index"
+                             % (nmodel, nprob))
+    else:
+        mi = _host(model_index).reshape(-1)
+        if mi.size != nprob or mi.min() < 0 or mi.max() >= nmodel:
+            raise ValueError("model_index must be [%d] in [0, %d)" %
+                             (nprob, nmodel))
+    return nprob, ts[1], nchan, nharm, nmodel
+
+
+def eval_points(theta, data_FT, model_FT, errs_FT, P, freqs, nus,
+                fit_flags=None, log10_tau=True, order=2, per_channel=False,
+                mask=None, model_index=None, max_bytes=None, dev=None):
+    """The portrait likelihood of fit_portrait_full_function
+    (pptoaslib.py:564-684) at many parameter points (ppf_eval_batch).
+
+    theta [nprob, K, 5] (or [K, 5]); data_FT [nprob, nchan, nharm] and
+    model_FT [nmodel, nchan, nharm] complex128 (or [nchan, nharm]); errs_FT,
+    freqs [nprob, nchan]; P [nprob]; nus [nprob, 3] = nu_DM, nu_GM, nu_tau
+    (each may be given once for all problems); mask [nprob, nchan] (0 drops
+    a channel); model_index [nprob]; fit_flags [5].
+
+    Returns device tensors (f [nprob, K], grad [nprob, K, 5] or None, hess
+    [nprob, K, 5, 5] or None, terms [nprob, K, 62, nchan] or None): terms
+    (per_channel) holds C, S, dC[5], dS[5], d2C[5, 5], d2S[5, 5] per
+    channel.  The points are evaluated in consecutive chunks when the
+    per-channel arrays of all of them would pass max_bytes (default half
+    the free device memory); a point's result does not depend on the
+    chunking."""
+    nprob, K, nchan, nharm, nmodel = _eval_shapes(
+        theta, data_FT, model_FT, errs_FT, P, freqs, nus, fit_flags, order,
+        mask, model_index)
+    dev = device(dev)
+    c128, f64 = torch.complex128, torch.float64
+    D_t = to_dev(data_FT, dev, c128).reshape(nprob, nchan, nharm)
+    M_t = to_dev(model_FT, dev, c128).reshape(nmodel, nchan, nharm)
+    th = to_dev(theta, dev, f64).reshape(nprob, K, 5)
+
+    def per_prob(x, inner, dtype=f64):
+        t = to_dev(x, dev, dtype).reshape(-1)
+        if t.numel() == inner and nprob > 1:
+            t = t.repeat(nprob)
+        return t.reshape(nprob, inner).contiguous()
+
+    e_t = per_prob(errs_FT, nchan)
+    fr = per_prob(freqs, nchan)
+    nu = per_prob(nus, 3)
+    P_t = per_prob(P if isinstance(P, torch.Tensor) else
+                   np.asarray(P, dtype=float), 1)
+    mk = None if mask is None else per_prob(
+        mask if isinstance(mask, torch.Tensor) else
+        (np.asarray(mask) != 0).astype(np.uint8), nchan, torch.uint8)
+    mi = None if model_index is None else \
+        to_dev(model_index, dev, torch.int32).reshape(nprob).contiguous()
+    fl = None if fit_flags is None else \
+        to_dev(np.asarray(_host(fit_flags), dtype=float).reshape(5), dev, f64)
+    ncomp = (1, 6, 21)[order]
+    per_point = nprob * nchan * 8 * (ncomp +
+                                     (EVAL_TERMS if per_channel else 0))
+    if max_bytes is None:
+        if K * per_point <= (64 << 20):
+            max_bytes = 64 << 20
+        else:
+            free, _ = torch.cuda.mem_get_info(dev)
+            max_bytes = free // 2
+    # also within the 2^31 - 1 workgroups of one launch
+    pb = eval_point_block()
+    kmax = max(pb, ((2 ** 31 - 1) // (nprob * nchan) - 1) * pb)
+    step = int(min(K, kmax, max(1, max_bytes // per_point)))
+    f = torch.empty((nprob, K), dtype=f64, device=dev)
+    g = torch.empty((nprob, K, 5), dtype=f64, device=dev) if order >= 1 \
+        else None
+    H = torch.empty((nprob, K, 5, 5), dtype=f64, device=dev) if order >= 2 \
+        else None
+    terms = torch.empty((nprob, K, EVAL_TERMS, nchan), dtype=f64,
+                        device=dev) if per_channel else None
+    lib = _lib.load()
+    ctx = _lib.context(dev.index)
+    ws = None
+    for k0 in range(0, K, step):
+        k1 = min(K, k0 + step)
+        whole = k0 == 0 and k1 == K
+        n = k1 - k0
+        need = lib.ppf_eval_workspace_bytes(nprob, nchan, n, order)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        th_c = th if whole else th[:, k0:k1].contiguous()
+        f_c = f if whole else torch.empty((nprob, n), dtype=f64, device=dev)
+        g_c = g if whole or g is None else \
+            torch.empty((nprob, n, 5), dtype=f64, device=dev)
+        H_c = H if whole or H is None else \
+            torch.empty((nprob, n, 5, 5), dtype=f64, device=dev)
+        t_c = terms if whole or terms is None else \
+            torch.empty((nprob, n, EVAL_TERMS, nchan), dtype=f64, device=dev)
+        rc = lib.ppf_eval_batch(
+            ctx, nprob, nchan, nharm, n, _p(D_t), _p(M_t), nmodel, _p(mi),
+            _p(e_t), _p(P_t), _p(fr), _p(nu), _p(mk), _p(th_c), _p(fl),
+            int(bool(log10_tau)), int(order), _p(f_c), _p(g_c), _p(H_c),
+            _p(t_c), _p(ws), ws.numel(), _stream(dev))
+        _lib.check(rc, ctx)
+        if not whole:
+            f[:, k0:k1] = f_c
+            if g is not None:
+                g[:, k0:k1] = g_c
+            if H is not None:
+                H[:, k0:k1] = H_c
+            if terms is not None:
+                terms[:, k0:k1] = t_c
+    return f, g, H, terms
+
+
 def phase_shift_batch(data, model, noise=None, Ns=100, bounds=(-0.5, 0.5),
                       model_index=None, dev=None):
     """Batched pplib.fit_phase_shift: data [nprof, nbin], model

@@ -759,6 +759,80 @@ def fit_phase_shift(data, model, noise=None, bounds=[-0.5, 0.5], Ns=100):
                      duration=time.time() - t0)
 
 
+def _phase_terms(theta, model, data, freqs, P, nu_ref, order):
+    """Per channel Cdp = Re sum_k d_k conj(m_k) e^{2 pi i k phi_n} and its
+    first two phase derivatives (pplib.py:1373-1377, 1400-1401, 1438-1439) at
+    (phase, DM) on the GPU: ppf_eval_batch without scattering and with unit
+    errors, whose channel terms C, dC[0], d2C[0, 0] they are."""
+    model = np.atleast_2d(np.asarray(model))
+    data = np.atleast_2d(np.asarray(data))
+    nchan = model.shape[0]
+    _, _, _, t = engine.eval_points(
+        np.array([[theta[0], theta[1], 0.0, 0.0, 0.0]]), data, model,
+        np.ones(nchan), P, freqs, [nu_ref, np.inf, np.inf], log10_tau=False,
+        order=order, per_channel=True)
+    t = t.cpu().numpy()[0, 0]
+    return t[0], t[2], t[12]
+
+
+def fit_phase_shift_function(phase, model=None, data=None, err=None):
+    """pplib.py:1294-1306: -Re sum_k d_k conj(m_k) e^{2 pi i k phase} /
+    err^2 (Fourier-domain model and data of one profile)."""
+    C, _, _ = _phase_terms([phase, 0.0], model, data, [1.0], 1.0, np.inf, 0)
+    return -C[0] / err ** 2.0
+
+
+def fit_phase_shift_function_deriv(phase, model=None, data=None, err=None):
+    """pplib.py:1309-1319: the first derivative of fit_phase_shift_function."""
+    _, dC, _ = _phase_terms([phase, 0.0], model, data, [1.0], 1.0, np.inf, 1)
+    return -dC[0] / err ** 2.0
+
+
+def fit_phase_shift_function_2deriv(phase, model=None, data=None, err=None):
+    """pplib.py:1322-1332: the second derivative."""
+    _, _, d2C = _phase_terms([phase, 0.0], model, data, [1.0], 1.0, np.inf, 2)
+    return -d2C[0] / err ** 2.0
+
+
+def fit_portrait_function(params, model=None, p_n=None, data=None, errs=None,
+                          P=None, freqs=None, nu_ref=np.inf):
+    """pplib.py:1335-1379: -sum_n Cdp_n^2 / (err_n^2 p_n) at params =
+    (phase, DM); the caller's p_n stands where the full function has S.
+    Without P or freqs the DM term is dropped, as in the reference."""
+    if P is None or freqs is None:
+        theta, fr, per = [params[0], 0.0], np.ones(len(model)), 1.0
+    else:
+        theta, fr, per = params, np.asarray(freqs, dtype=float), P
+    Cdp, _, _ = _phase_terms(theta, model, data, fr, per, nu_ref, 0)
+    return -np.sum(Cdp ** 2.0 / (np.asarray(errs) ** 2.0 * np.asarray(p_n)))
+
+
+def fit_portrait_function_deriv(params, model=None, p_n=None, data=None,
+                                errs=None, P=None, freqs=None, nu_ref=np.inf):
+    """pplib.py:1382-1405: the two first derivatives of
+    fit_portrait_function."""
+    freqs = np.asarray(freqs, dtype=float)
+    Cdp, d1, _ = _phase_terms(params, model, data, freqs, P, nu_ref, 1)
+    w = -2 * Cdp * d1 / (np.asarray(errs) ** 2.0 * np.asarray(p_n))
+    dDM = (freqs ** -2.0 - nu_ref ** -2.0) * (Dconst / P)
+    return np.array([w.sum(), (w * dDM).sum()])
+
+
+def fit_portrait_function_2deriv(params, model=None, p_n=None, data=None,
+                                 errs=None, P=None, freqs=None,
+                                 nu_ref=np.inf):
+    """pplib.py:1408-1447: (d2/dphi2, d2/dDM2, d2/dphi dDM) of
+    fit_portrait_function and the zero-covariance frequency nu_zero."""
+    freqs = np.asarray(freqs, dtype=float)
+    Cdp, d1, d2 = _phase_terms(params, model, data, freqs, P, nu_ref, 2)
+    W_n = (d1 ** 2.0 + Cdp * d2) / (np.asarray(errs) ** 2.0 *
+                                    np.asarray(p_n))
+    dDM = (freqs ** -2.0 - nu_ref ** -2.0) * (Dconst / P)
+    nu_zero = (W_n.sum() / np.sum(W_n * freqs ** -2)) ** 0.5
+    return (np.array([(-2.0 * W_n).sum(), (-2.0 * W_n * dDM ** 2.0).sum(),
+                      (-2.0 * W_n * dDM).sum()]), nu_zero)
+
+
 def fit_portrait(data, model, init_params, P, freqs, nu_fit=None, nu_out=None,
                  errs=None, bounds=[(None, None), (None, None)], id=None,
                  quiet=True):

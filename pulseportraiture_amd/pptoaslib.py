@@ -282,3 +282,188 @@ def get_scales_full(params, data_portrait_FT, model_portrait_FT, errs_FT, P,
         [float(nu_DM), float(nu_GM), float(nu_tau)], log10_tau,
         errs_FT=None if errs_FT is None else np.asarray(errs_FT, dtype=float))
     return out[0].cpu().numpy()
+
+
+# ---------------------------------------------------------------------------
+# The likelihood itself: pptoaslib.py:564-773 evaluated on the GPU
+# (ppf_eval_batch, ppf_eval.hip).  eval_portrait_full is the batched entry;
+# the reference's four signatures are one-point calls of the same kernel.
+# ---------------------------------------------------------------------------
+def _terms_bunch(terms):
+    """[..., 62, nchan] -> DataBunch of C, S [..., nchan], dC, dS
+    [..., 5, nchan], d2C, d2S [..., 5, 5, nchan] (oracle.channel_terms'
+    layout behind the leading axes)."""
+    lead, nchan = terms.shape[:-2], terms.shape[-1]
+    return DataBunch(C=terms[..., 0, :], S=terms[..., 1, :],
+                     dC=terms[..., 2:7, :], dS=terms[..., 7:12, :],
+                     d2C=terms[..., 12:37, :].reshape(lead + (5, 5, nchan)),
+                     d2S=terms[..., 37:62, :].reshape(lead + (5, 5, nchan)))
+
+
+def eval_portrait_full(params, data_portrait_FT, model_portrait_FT, errs_FT,
+                       P, freqs, nu_DM, nu_GM, nu_tau,
+                       fit_flags=(1, 1, 1, 1, 1), log10_tau=True, order=2,
+                       per_channel=False, mask=None, model_index=None,
+                       dev=None):
+    """fit_portrait_full_function and its derivatives (pptoaslib.py:564-684)
+    at K parameter points in one device call (not in the reference).
+
+    params [K, 5] for one problem -- data_portrait_FT, model_portrait_FT
+    [nchan, nharm], errs_FT, freqs [nchan], scalar P and reference
+    frequencies -- or [nprob, K, 5] with a leading problem axis on the other
+    arrays (model_portrait_FT may hold fewer models, chosen by model_index
+    [nprob]).  mask [.., nchan]: 0 drops a channel.  order 0 / 1 / 2: f /
+    + gradient / + Hessian.  Returns DataBunch(f [.., K], grad [.., K, 5],
+    hess [.., K, 5, 5]) of NumPy arrays (None past `order`), with
+    per_channel also terms: C, S [.., K, nchan], dC, dS [.., K, 5, nchan],
+    d2C, d2S [.., K, 5, 5, nchan]."""
+    th = np.asarray(params, dtype=float)
+    if th.ndim not in (2, 3) or th.shape[-1] != 5:
+        raise ValueError("params must be [K, 5] or [nprob, K, 5], got %s" %
+                         (th.shape,))
+    single = th.ndim == 2
+    if single and np.ndim(data_portrait_FT) != 2:
+        raise ValueError("params [K, 5] go with one [nchan, nharm] problem")
+    nprob = 1 if single else th.shape[0]
+    nus = np.empty((nprob, 3))
+    for i, v in enumerate((nu_DM, nu_GM, nu_tau)):
+        nus[:, i] = np.asarray(v, dtype=float)
+    f, g, H, t = engine.eval_points(
+        th, data_portrait_FT, model_portrait_FT,
+        np.ones(np.shape(freqs)) if errs_FT is None else errs_FT, P, freqs,
+        nus, fit_flags=fit_flags, log10_tau=log10_tau, order=order,
+        per_channel=per_channel, mask=mask, model_index=model_index, dev=dev)
+    out = [None if x is None else x.cpu().numpy() for x in (f, g, H, t)]
+    if single:
+        out = [None if x is None else x[0] for x in out]
+    res = DataBunch(f=out[0], grad=out[1], hess=out[2])
+    if per_channel:
+        res["terms"] = _terms_bunch(out[3])
+    return res
+
+
+def _eval_one(params, data_portrait_FT, model_portrait_FT, errs_FT, P, freqs,
+              nu_DM, nu_GM, nu_tau, fit_flags, log10_tau, order,
+              per_channel=False):
+    r = eval_portrait_full(
+        np.asarray(params, dtype=float).reshape(1, 5),
+        np.asarray(data_portrait_FT), np.asarray(model_portrait_FT), errs_FT,
+        P, np.asarray(freqs, dtype=float), nu_DM, nu_GM, nu_tau,
+        fit_flags=np.asarray(fit_flags, dtype=float), log10_tau=log10_tau,
+        order=order, per_channel=per_channel)
+    t = None
+    if per_channel:
+        t = DataBunch(**{k: v[0] for k, v in r.terms.items()})
+    return r, t
+
+
+def fit_portrait_full_function(params, data_portrait_FT, model_portrait_FT,
+                               errs_FT, P, freqs, nu_DM, nu_GM, nu_tau,
+                               fit_flags, log10_tau):
+    """pptoaslib.py:564-581: chi'^2 = -sum C_n^2 / S_n (a float)."""
+    r, _ = _eval_one(params, data_portrait_FT, model_portrait_FT, errs_FT, P,
+                     freqs, nu_DM, nu_GM, nu_tau, fit_flags, log10_tau, 0)
+    return np.float64(r.f[0])
+
+
+def fit_portrait_full_function_deriv(params, data_portrait_FT,
+                                     model_portrait_FT, errs_FT, P, freqs,
+                                     nu_DM, nu_GM, nu_tau, fit_flags,
+                                     log10_tau):
+    """pptoaslib.py:584-614: the gradient [5], times fit_flags."""
+    r, _ = _eval_one(params, data_portrait_FT, model_portrait_FT, errs_FT, P,
+                     freqs, nu_DM, nu_GM, nu_tau, fit_flags, log10_tau, 1)
+    return r.grad[0].copy()
+
+
+def _channel_hessian(t, flags):
+    """Per-channel profiled Hessian [5, 5, nchan] from the channel terms
+    (pptoaslib.py:662-671 multiplied out, so a channel with C = 0 gives its
+    finite value instead of the reference's 0 / 0)."""
+    C, S, dC, dS = t.C, t.S, t.dC, t.dS
+    ff = flags[:, None] * flags[None, :]
+    return -2.0 * (C * t.d2C / S - 0.5 * C ** 2 * t.d2S / S ** 2 +
+                   dC[:, None] * dC[None, :] / S +
+                   C ** 2 * dS[:, None] * dS[None, :] / S ** 3 -
+                   C * (dC[:, None] * dS[None, :] + dS[:, None] * dC[None, :])
+                   / S ** 2) * ff[:, :, None]
+
+
+def _returns(hessian, extra):
+    return hessian if not extra else tuple([hessian] + extra)
+
+
+def fit_portrait_full_function_2deriv(params, data_portrait_FT,
+                                      model_portrait_FT, errs_FT, P, freqs,
+                                      nu_DM, nu_GM, nu_tau, fit_flags,
+                                      log10_tau, per_channel=False,
+                                      return_covariance_matrix=False,
+                                      return_scales=False):
+    """pptoaslib.py:617-684: the Hessian [5, 5] (summed on the device), or
+    [5, 5, nchan] with per_channel (assembled from the device's channel
+    terms); then, as asked, the covariance matrix inv(0.5 H) over the fitted
+    parameters and the scales C / S, in the reference's return order (the
+    bare Hessian when nothing else is asked)."""
+    flags = np.asarray(fit_flags, dtype=float)
+    need_t = per_channel or return_scales
+    r, t = _eval_one(params, data_portrait_FT, model_portrait_FT, errs_FT, P,
+                     freqs, nu_DM, nu_GM, nu_tau, flags, log10_tau, 2, need_t)
+    hess = r.hess[0].copy()
+    extra = []
+    if return_covariance_matrix:
+        ifit = np.where(np.asarray(fit_flags))[0]
+        extra.append(np.linalg.inv(0.5 * hess[np.ix_(ifit, ifit)]))
+    if return_scales:
+        extra.append(t.C / t.S)
+    return _returns(_channel_hessian(t, flags) if per_channel else hess,
+                    extra)
+
+
+def fit_portrait_full_function_2deriv_with_scales(
+        params, data_portrait_FT, model_portrait_FT, errs_FT, P, freqs,
+        nu_DM, nu_GM, nu_tau, fit_flags, log10_tau, per_channel=False,
+        return_covariance_matrix=False, return_scales=False):
+    """pptoaslib.py:687-773: the Hessian over (theta, a_n), (5 + nchan)^2
+    (with per_channel one more axis of nchan, as the reference builds it),
+    assembled on the host from the device's channel terms -- it is
+    O(nchan^2) by definition -- and its block inverse (Schur complement of
+    the diagonal a_n block) as the covariance matrix."""
+    flags = np.asarray(fit_flags, dtype=float)
+    _, t = _eval_one(params, data_portrait_FT, model_portrait_FT, errs_FT, P,
+                     freqs, nu_DM, nu_GM, nu_tau, flags, log10_tau, 2, True)
+    C, S = t.C, t.S
+    n = len(C)
+    scales = C / S
+    ff = flags[:, None] * flags[None, :]
+    top = -2.0 * (C * t.d2C / S - 0.5 * C ** 2 * t.d2S / S ** 2) * \
+        ff[:, :, None]                                   # [5, 5, n]
+    cross = -2.0 * (t.dC - scales * t.dS)                # [5, n]
+    total = np.zeros((5 + n, 5 + n))
+    total[:5, :5] = top.sum(axis=-1)
+    total[:5, 5:] = cross * flags[:, None]
+    total[5:, :5] = total[:5, 5:].T
+    total[5:, 5:] = np.diag(2.0 * S)
+    if per_channel:
+        hessian = np.zeros((5 + n, 5 + n, n))
+        hessian[:5, :5] = top
+        ic = np.arange(n)
+        hessian[5 + ic, 5 + ic, ic] = 2.0 * S
+        for j in range(5):
+            hessian[5 + ic, j, ic] = hessian[j, 5 + ic, ic] = \
+                cross[j] * flags[j]
+    else:
+        hessian = total
+    extra = []
+    if return_covariance_matrix:
+        ifit = np.where(np.asarray(fit_flags))[0]
+        A = total[np.ix_(ifit, ifit)]
+        U = cross[ifit]
+        cinv = 1.0 / (2.0 * S)
+        Xinv = np.linalg.inv(A - (U * cinv) @ U.T)
+        UR = -(Xinv @ U) * cinv
+        LL = -cinv[:, None] * (U.T @ Xinv)
+        LR = -(LL @ U) * cinv + np.diag(cinv)
+        extra.append(2.0 * np.block([[Xinv, UR], [LL, LR]]))
+    if return_scales:
+        extra.append(scales)
+    return _returns(hessian, extra)
