@@ -202,14 +202,99 @@ int cz_tables(ppf_ctx *ctx, const ppf::CzPlan &c, hipStream_t st, const double2 
     return PPF_OK;
 }
 
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// workspace regions in the order they are taken, each a multiple of 256
+// bytes (an empty one takes none)
+struct Carver {
+    size_t o = 0;
+    size_t operator()(size_t bytes) {
+        const size_t at = o;
+        o += align256(bytes);
+        return at;
+    }
+};
+
+// ---- the long (four-step / Bluestein) transforms: what their callers share --
+// The transform of rows of n complex points (packed: two real samples each):
+// M >= n points (a plain power of two) or >= 2 n - 1 (Bluestein), M = M1 M2
+// for the four-step passes.  False past 2^24 points.
+bool long_len(int64_t nbin, int64_t n, bool packed, bool bluestein, ppf::LongNoiseArgs &a) {
+    a = ppf::LongNoiseArgs{};
+    a.nbin = nbin; a.n = n; a.packed = packed ? 1 : 0; a.bluestein = bluestein ? 1 : 0;
+    int64_t M = 64;
+    while (M < (bluestein ? 2 * n - 1 : n)) M *= 2;
+    int m = 0;
+    while (((int64_t)1 << m) < M) ++m;
+    if (m > 24) return false;             // M1, M2 <= 4096 (the block LDS FFT)
+    a.M = M; a.log2M = m; a.log2M1 = (m + 1) / 2;
+    a.M1 = (int64_t)1 << a.log2M1; a.M2 = M / a.M1;
+    return true;
+}
+bool bluestein_plan(int64_t nbin, int64_t n, bool packed, ppf::LongNoiseArgs &a) {
+    return long_len(nbin, n, packed, true, a);
+}
+
+// rows per chunk: at most 256 MB of complex work rows (A and Y together), at
+// least one row, no more than the call has
+int64_t long_chunk_rows(int64_t nrows, size_t row_b) {
+    int64_t rc = (int64_t)((size_t)(256u << 20) / (2 * row_b));
+    if (rc < 1) rc = 1;
+    return nrows < rc ? (nrows > 0 ? nrows : 1) : rc;
+}
+
+// A long transform's work area in a workspace: the chirp table (two rows;
+// chirp_b: the inverse plan's, ppf_rotate_long), the chunk's work rows A and
+// Y, and the rows per chunk
+struct LongWork {
+    size_t chirp, chirp_b, A, Y;
+    int64_t rows;
+};
+LongWork long_work(Carver &take, int64_t nrows, size_t row_b, size_t chirp_bytes, size_t chirp_b_bytes = 0) {
+    LongWork w;
+    w.rows = long_chunk_rows(nrows, row_b);
+    w.chirp = take(chirp_bytes);
+    w.chirp_b = take(chirp_b_bytes);
+    w.A = take((size_t)w.rows * row_b);
+    w.Y = take((size_t)w.rows * row_b);
+    return w;
+}
+
+// a plan's twiddle pair (of 2 M1 and 2 M2) and its chirp table at B,
+// launched where `chirp` asks for it
+struct LongTables {
+    const double2 *T1, *T2;
+    double2 *B;
+};
+int long_tables(ppf_ctx *ctx, const ppf::LongNoiseArgs &f, double2 *B, bool chirp, hipStream_t st,
+                LongTables &t) {
+    const double2 *unused;
+    int rc;
+    if ((rc = twiddles(ctx, (int)(2 * f.M1), st, &t.T1, &unused))) return rc;
+    if ((rc = twiddles(ctx, (int)(2 * f.M2), st, &t.T2, &unused))) return rc;
+    t.B = B;
+    hipError_t e;
+    if (chirp && (e = ppf::launch_chirp_ft(f, B, B + f.M, t.T1, t.T2, st)) != hipSuccess)
+        return hip_fail(ctx, e, "k_lf_chirp");
+    return PPF_OK;
+}
+
+// body(r0, nr) for each chunk of at most rows_c rows, until one fails
+template <class F>
+int for_chunks(int64_t nrows, int64_t rows_c, F &&body) {
+    for (int64_t r0 = 0; r0 < nrows; r0 += rows_c)
+        if (int rc = body(r0, nrows - r0 < rows_c ? nrows - r0 : rows_c)) return rc;
+    return PPF_OK;
+}
+
 struct FitLayout {
     size_t M, X, chan, stats, x0, gP, gw, nuref, Msum, gpart, gwx, gflag, state, partials, active, mom, dphi,
         mres, hcen, Mpow, MP, KC, needx, xslot, xtile, cls, rec, hmlist, nglist, rclist, Bt, total;
     // rows past the LDS transforms (round 6): their rFFTs (data spectra,
-    // long-transform chirp tables and work rows, rows per chunk)
+    // the long transform's work area)
     int lng;
-    size_t spec, lchirp, lA, lY, gprof, gspec, gsh;
-    int64_t lrows;
+    size_t spec, gprof, gspec, gsh;
+    LongWork lw;
     int nblk, cb, cbd, nblkd;
     int cbx, nblkx;   // the spectrum pass's own channel block (ppf::xspec_own_cb), else cb, nblk
     int fused;    // phase+DM fits on the fused moment pass (k_xmom_g), X only for scattering fits
@@ -230,10 +315,6 @@ struct FitLayout {
 static bool mom16_layout(const FitLayout &L, int nbin) {
     return L.momx || (!L.fused && !ppf::is_pow2(ppf::rfft_len(nbin)));
 }
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-bool bluestein_plan(int64_t nbin, int64_t n, bool packed, ppf::LongNoiseArgs &a);
 
 // the long-transform plan of the rFFT of real rows of nbin samples (even
 // nbin: two samples per complex point)
@@ -284,14 +365,7 @@ FitLayout fit_layout(const ppf_fit_desc *d) {
     if (L.momx) L.xcap = d->nsub;
     L.cbd = d->nchan < 128 ? d->nchan : 128;          // k_dsum channel block
     L.nblkd = (d->nchan + L.cbd - 1) / L.cbd;
-    // regions in the order they are taken, each a multiple of 256 bytes (an
-    // empty one takes none)
-    size_t o = 0;
-    auto take = [&o](size_t bytes) {
-        const size_t at = o;
-        o += align256(bytes);
-        return at;
-    };
+    Carver take;
     L.M = take(sizeof(double2) * nmodel * nchan * nharm);
     // tiled slots hold whole tiles of 8 harmonics per channel (1032 at 2048
     // bins); the harmonic-major slots of the same call keep that stride
@@ -325,7 +399,7 @@ FitLayout fit_layout(const ppf_fit_desc *d) {
         L.gw = take(sizeof(double) * nsub * (size_t)L.nblkd * 2);
         L.nuref = take(sizeof(double) * nsub);
         L.Msum = take(sizeof(double2) * nmodel * nharm);
-        if (L.fused) {   // guess spectrum fused into k_xspec_w (k_classify: gflag)
+        if (L.fused) {   // guess spectrum fused into k_xspec_w2 (k_classify: gflag)
             const size_t ng = (size_t)ppf::guess_slots(rfft_log2(d->nbin));
             L.gpart = take(sizeof(double2) * nsub * (size_t)L.nblkx * ng);
             L.gwx = take(sizeof(double) * nsub * (size_t)L.nblkx * 3);
@@ -337,49 +411,35 @@ FitLayout fit_layout(const ppf_fit_desc *d) {
         ppf::LongNoiseArgs f;
         long_row_plan(d->nbin, f);
         const size_t row_b = (size_t)f.M * sizeof(double2);
-        const int64_t rows = (int64_t)(nsub > nmodel ? nsub : nmodel) * (int64_t)nchan;
-        int64_t rc = (int64_t)((size_t)(256u << 20) / (2 * row_b));
-        if (rc < 1) rc = 1;
-        L.lrows = rows < rc ? rows : rc;
         L.spec = take(sizeof(double2) * nsub * nchan * nharm);
         if (d->guess) {
             L.gprof = take(sizeof(double) * nsub * (size_t)d->nbin);
             L.gspec = take(sizeof(double2) * nsub * nharm);
         }
-        L.lchirp = take(2 * row_b);
-        L.lA = take((size_t)L.lrows * row_b);
-        L.lY = take((size_t)L.lrows * row_b);
+        L.lw = long_work(take, (int64_t)(nsub > nmodel ? nsub : nmodel) * (int64_t)nchan, row_b, 2 * row_b);
     }
     if (d->guess && grid_gsh(d->nbin, d->guess_Ns, L.lng))
         L.gsh = take(sizeof(double) * nsub * ((size_t)d->guess_Ns + 8));
-    L.total = o;
+    L.total = take.o;
     return L;
 }
 
 // the rFFTs of nrows real rows of nbin samples on the long transforms into
 // out[row][k], k <= nbin / 2 (Bluestein; the chirp table once per call)
-int long_rfft_rows(ppf_ctx *ctx, const FitLayout &L, char *ws, int64_t nbin, int64_t nrows, int dtype,
+int long_rfft_rows(ppf_ctx *ctx, const LongWork &w, char *ws, int64_t nbin, int64_t nrows, int dtype,
                    const void *in, double2 *out, bool chirp_ready, hipStream_t st) {
     ppf::LongNoiseArgs f;
     if (!long_row_plan(nbin, f)) return fail(ctx, PPF_EUNSUP, "nbin=%lld", (long long)nbin);
-    const double2 *T1, *T2, *unused;
-    int rc;
-    if ((rc = twiddles(ctx, (int)(2 * f.M1), st, &T1, &unused))) return rc;
-    if ((rc = twiddles(ctx, (int)(2 * f.M2), st, &T2, &unused))) return rc;
-    double2 *Bf = (double2 *)(ws + L.lchirp);
-    hipError_t e;
-    if (!chirp_ready && (e = ppf::launch_chirp_ft(f, Bf, Bf + f.M, T1, T2, st)) != hipSuccess)
-        return hip_fail(ctx, e, "k_lf_chirp");
+    LongTables t;
+    if (int rc = long_tables(ctx, f, (double2 *)(ws + w.chirp), !chirp_ready, st, t)) return rc;
     f.in_dtype = dtype;
     f.in = in;
-    for (int64_t r0 = 0; r0 < nrows; r0 += L.lrows) {
+    return for_chunks(nrows, w.rows, [&](int64_t r0, int64_t nr) {
         f.row0 = r0;
-        const int64_t nr = nrows - r0 < L.lrows ? nrows - r0 : L.lrows;
-        if ((e = ppf::launch_rfft_long(f, nr, (double2 *)(ws + L.lA), (double2 *)(ws + L.lY), Bf, out, T1, T2,
-                                       st)) != hipSuccess)
-            return hip_fail(ctx, e, "k_lr_spec");
-    }
-    return PPF_OK;
+        const hipError_t e = ppf::launch_rfft_long(f, nr, (double2 *)(ws + w.A), (double2 *)(ws + w.Y), t.B, out,
+                                                   t.T1, t.T2, st);
+        return e == hipSuccess ? PPF_OK : hip_fail(ctx, e, "k_lr_spec");
+    });
 }
 
 int check_fit_desc(ppf_ctx *ctx, const ppf_fit_desc *d) {
@@ -475,7 +535,7 @@ struct FitCall {
     uint8_t *needx;
     int32_t *xslot;
     uint8_t *xtile;              // null: no tiled slot
-    // fused guess: the sub-ints k_xspec_w streams whose mean-model cutoff
+    // fused guess: the sub-ints of k_xspec_w2 whose mean-model cutoff
     // fits its guess harmonics accumulate the guess spectrum there
     uint8_t *gflag;              // null: no fused guess (then gpart, gwx too)
     double2 *gpart;
@@ -543,7 +603,7 @@ int FitCall::begin() {
 int FitCall::models() {
     hipError_t e;
     if (L.lng) {
-        if (int rc = long_rfft_rows(ctx, L, ws, d->nbin, (int64_t)d->nmodel * d->nchan, PPF_F64, d->model, Mft,
+        if (int rc = long_rfft_rows(ctx, L.lw, ws, d->nbin, (int64_t)d->nmodel * d->nchan, PPF_F64, d->model, Mft,
                                     false, st))
             return rc;
     } else {
@@ -614,7 +674,7 @@ int FitCall::spectra() {
             return hip_fail(ctx, e, "k_xspec_w");
     } else if (L.lng) {
         double2 *spec = at<double2>(L.spec);
-        if (int rc = long_rfft_rows(ctx, L, ws, d->nbin, (int64_t)d->nsub * d->nchan, d->data_dtype, d->data,
+        if (int rc = long_rfft_rows(ctx, L.lw, ws, d->nbin, (int64_t)d->nsub * d->nchan, d->data_dtype, d->data,
                                     spec, true, st))
             return rc;
         xa.spec = spec;
@@ -661,7 +721,7 @@ int FitCall::guess() {
         double2 *gspec = at<double2>(L.gspec);
         if ((e = ppf::launch_gsum(d->nsub, L.nblkd, d->nbin, da.gP, prof, st)) != hipSuccess)
             return hip_fail(ctx, e, "k_gsum");
-        if ((rc = long_rfft_rows(ctx, L, ws, d->nbin, d->nsub, PPF_F64, prof, gspec, true, st))) return rc;
+        if ((rc = long_rfft_rows(ctx, L.lw, ws, d->nbin, d->nsub, PPF_F64, prof, gspec, true, st))) return rc;
         ga.gspec = gspec;
     }
     if (grid_gsh(d->nbin, ga.Ns, L.lng)) ga.gsh = at<double>(L.gsh);
@@ -1168,43 +1228,23 @@ int ppf_noise_batch(ppf_ctx *ctx, int64_t nrows, int32_t nbin, int32_t in_dtype,
 namespace {
 struct LongPlan {
     ppf::LongNoiseArgs a;
-    int64_t rows_c;
-    size_t off_A, off_Y, off_part, bytes;
+    LongWork w;
+    size_t off_part, bytes;
 };
 bool long_plan(int64_t nrows, int64_t nbin, int frac, LongPlan &p) {
     if (nrows < 0 || nbin < 1 || frac < 1) return false;
     ppf::LongNoiseArgs &a = p.a;
-    a = ppf::LongNoiseArgs{};
-    a.nbin = nbin;
-    a.packed = (nbin % 2 == 0) ? 1 : 0;
-    a.n = a.packed ? nbin / 2 : nbin;
+    const bool packed = nbin % 2 == 0;
+    const int64_t n = packed ? nbin / 2 : nbin;
+    const bool pow2 = (n & (n - 1)) == 0;
+    if (!long_len(nbin, n, packed, !(pow2 && n >= 64), a)) return false;
     a.nharm = nbin / 2 + 1;
     a.kc = (int64_t)((1.0 - std::pow((double)frac, -1.0)) * (double)a.nharm);
-    const bool pow2 = (a.n & (a.n - 1)) == 0;
-    a.bluestein = (pow2 && a.n >= 64) ? 0 : 1;
-    int64_t M = 64;
-    const int64_t need = a.bluestein ? 2 * a.n - 1 : a.n;
-    while (M < need) M *= 2;
-    int m = 0;
-    while (((int64_t)1 << m) < M) ++m;
-    if (m > 24) return false;             // M1, M2 <= 4096 (the block LDS FFT)
-    a.M = M;
-    a.log2M = m;
-    a.log2M1 = (m + 1) / 2;
-    a.M1 = (int64_t)1 << a.log2M1;
-    a.M2 = M / a.M1;
-    const size_t row_b = (size_t)M * sizeof(double2);
-    int64_t rc = (int64_t)((size_t)(256u << 20) / (2 * row_b));
-    if (rc < 1) rc = 1;
-    p.rows_c = nrows < rc ? (nrows > 0 ? nrows : 1) : rc;
-    size_t off = a.bluestein ? align256(2 * row_b) : 0;
-    p.off_A = off;
-    off += align256((size_t)p.rows_c * row_b);
-    p.off_Y = off;
-    off += align256((size_t)p.rows_c * row_b);
-    p.off_part = off;
-    off += align256((size_t)p.rows_c * 256 * sizeof(double));
-    p.bytes = off;
+    const size_t row_b = (size_t)a.M * sizeof(double2);
+    Carver take;
+    p.w = long_work(take, nrows, row_b, a.bluestein ? 2 * row_b : 0);
+    p.off_part = take((size_t)p.w.rows * 256 * sizeof(double));
+    p.bytes = take.o;
     return true;
 }
 }  // namespace
@@ -1229,24 +1269,17 @@ int ppf_noise_long(ppf_ctx *ctx, int64_t nrows, int64_t nbin, int32_t in_dtype, 
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
     hipStream_t st = (hipStream_t)stream;
-    const double2 *T1, *T2, *unused;
-    int rc = twiddles(ctx, (int)(2 * p.a.M1), st, &T1, &unused);
-    if (rc) return rc;
-    if ((rc = twiddles(ctx, (int)(2 * p.a.M2), st, &T2, &unused))) return rc;
     char *ws = (char *)workspace;
-    double2 *Bf = (double2 *)ws;
-    if (p.a.bluestein && (e = ppf::launch_chirp_ft(p.a, Bf, Bf + p.a.M, T1, T2, st)) != hipSuccess)
-        return hip_fail(ctx, e, "k_lf_chirp");
+    LongTables t;
+    if (int rc = long_tables(ctx, p.a, (double2 *)(ws + p.w.chirp), p.a.bluestein, st, t)) return rc;
     p.a.in_dtype = in_dtype;
     p.a.in = in;
-    for (int64_t r0 = 0; r0 < nrows; r0 += p.rows_c) {
+    return for_chunks(nrows, p.w.rows, [&](int64_t r0, int64_t nr) {
         p.a.row0 = r0;
-        const int64_t nr = nrows - r0 < p.rows_c ? nrows - r0 : p.rows_c;
-        e = ppf::launch_noise_long(p.a, nr, (double2 *)(ws + p.off_A), (double2 *)(ws + p.off_Y), Bf,
-                                   (double *)(ws + p.off_part), out, T1, T2, st);
-        if (e != hipSuccess) return hip_fail(ctx, e, "k_lf");
-    }
-    return PPF_OK;
+        const hipError_t el = ppf::launch_noise_long(p.a, nr, (double2 *)(ws + p.w.A), (double2 *)(ws + p.w.Y), t.B,
+                                                     (double *)(ws + p.off_part), out, t.T1, t.T2, st);
+        return el == hipSuccess ? PPF_OK : hip_fail(ctx, el, "k_lf");
+    });
 }
 
 // get_noise_fit / find_kc (ppf_noisefit.hip)
@@ -1267,7 +1300,7 @@ int noise_fit_args(ppf_ctx *ctx, int32_t fn, const double *a_grid, const int32_t
 }
 bool fact_ok(double fact) { return fact > 0.0 && fact <= ppf::kDblMax; }
 size_t fit_long_pows_bytes(const LongPlan &p) {
-    return align256((size_t)p.rows_c * (size_t)p.a.nharm * sizeof(double));
+    return align256((size_t)p.w.rows * (size_t)p.a.nharm * sizeof(double));
 }
 }  // namespace
 
@@ -1321,27 +1354,22 @@ int ppf_noise_fit_long(ppf_ctx *ctx, int64_t nrows, int64_t nbin, int32_t in_dty
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
     hipStream_t st = (hipStream_t)stream;
-    const double2 *T1, *T2, *unused;
-    if ((rc = twiddles(ctx, (int)(2 * p.a.M1), st, &T1, &unused))) return rc;
-    if ((rc = twiddles(ctx, (int)(2 * p.a.M2), st, &T2, &unused))) return rc;
     char *ws = (char *)workspace;
-    double2 *Bf = (double2 *)ws;
-    if (p.a.bluestein && (e = ppf::launch_chirp_ft(p.a, Bf, Bf + p.a.M, T1, T2, st)) != hipSuccess)
-        return hip_fail(ctx, e, "k_lf_chirp");
+    LongTables t;
+    if ((rc = long_tables(ctx, p.a, (double2 *)(ws + p.w.chirp), p.a.bluestein, st, t))) return rc;
     p.a.in_dtype = in_dtype;
     p.a.in = in;
     double *pows = (double *)(ws + p.bytes);
     f.nharm = p.a.nharm; f.pows = pows; f.fact = fact; f.noise_out = noise_out; f.kc_out = kc_out;
-    for (int64_t r0 = 0; r0 < nrows; r0 += p.rows_c) {
+    return for_chunks(nrows, p.w.rows, [&](int64_t r0, int64_t nr) {
         p.a.row0 = r0;
         f.row0 = r0;
-        const int64_t nr = nrows - r0 < p.rows_c ? nrows - r0 : p.rows_c;
-        e = ppf::launch_pows_long(p.a, nr, (double2 *)(ws + p.off_A), (double2 *)(ws + p.off_Y), Bf, pows, T1,
-                                  T2, st);
-        if (e != hipSuccess) return hip_fail(ctx, e, "k_lf");
-        if ((e = ppf::launch_spec_fit(f, nr, st)) != hipSuccess) return hip_fail(ctx, e, "k_spec_fit");
-    }
-    return PPF_OK;
+        hipError_t el = ppf::launch_pows_long(p.a, nr, (double2 *)(ws + p.w.A), (double2 *)(ws + p.w.Y), t.B, pows,
+                                              t.T1, t.T2, st);
+        if (el != hipSuccess) return hip_fail(ctx, el, "k_lf");
+        if ((el = ppf::launch_spec_fit(f, nr, st)) != hipSuccess) return hip_fail(ctx, el, "k_spec_fit");
+        return (int)PPF_OK;
+    });
 }
 
 int ppf_find_kc_batch(ppf_ctx *ctx, int64_t nrows, int64_t nharm, const double *pows, const double *errs,
@@ -1366,22 +1394,10 @@ int ppf_find_kc_batch(ppf_ctx *ctx, int64_t nrows, int64_t nharm, const double *
 
 // ppf_rotate_long's plans and workspace: Bluestein transforms both ways
 namespace {
-bool bluestein_plan(int64_t nbin, int64_t n, bool packed, ppf::LongNoiseArgs &a) {
-    a = ppf::LongNoiseArgs{};
-    a.nbin = nbin; a.n = n; a.packed = packed ? 1 : 0; a.bluestein = 1;
-    int64_t M = 64;
-    while (M < 2 * n - 1) M *= 2;
-    int m = 0;
-    while (((int64_t)1 << m) < M) ++m;
-    if (m > 24) return false;
-    a.M = M; a.log2M = m; a.log2M1 = (m + 1) / 2;
-    a.M1 = (int64_t)1 << a.log2M1; a.M2 = M / a.M1;
-    return true;
-}
 struct RotPlan {
     ppf::LongRotArgs r;
-    int64_t rows_c;
-    size_t off_Bf, off_Bb, off_A, off_Y, bytes;
+    LongWork w;
+    size_t bytes;
 };
 bool rot_plan(int64_t nrows, int64_t nbin, bool ref_len, RotPlan &p) {
     if (nrows < 0 || nbin < 2) return false;
@@ -1393,15 +1409,9 @@ bool rot_plan(int64_t nrows, int64_t nbin, bool ref_len, RotPlan &p) {
     p.r.out_even = out_even ? 1 : 0;
     p.r.nout = nout;
     const size_t row_b = (size_t)p.r.f.M * sizeof(double2);     // b.M <= f.M
-    int64_t rc = (int64_t)((size_t)(256u << 20) / (2 * row_b));
-    if (rc < 1) rc = 1;
-    p.rows_c = nrows < rc ? (nrows > 0 ? nrows : 1) : rc;
-    size_t off = 0;
-    p.off_Bf = off; off += align256(2 * row_b);
-    p.off_Bb = off; off += align256(2 * (size_t)p.r.b.M * sizeof(double2));
-    p.off_A = off; off += align256((size_t)p.rows_c * row_b);
-    p.off_Y = off; off += align256((size_t)p.rows_c * row_b);
-    p.bytes = off;
+    Carver take;
+    p.w = long_work(take, nrows, row_b, 2 * row_b, 2 * (size_t)p.r.b.M * sizeof(double2));
+    p.bytes = take.o;
     return true;
 }
 }  // namespace
@@ -1438,31 +1448,21 @@ int ppf_rotate_long(ppf_ctx *ctx, int64_t nrows, int64_t nbin, int32_t in_dtype,
 // they are written)
 static int rotate_long_run(ppf_ctx *ctx, RotPlan &p, int64_t nrows, int32_t in_dtype, const void *in,
                            const double *phases, const double *taus, double *out, char *ws, hipStream_t st) {
-    hipError_t e;
-    const double2 *T1f, *T2f, *T1b, *T2b, *unused;
+    LongTables tf, tb;
     int rc;
-    if ((rc = twiddles(ctx, (int)(2 * p.r.f.M1), st, &T1f, &unused))) return rc;
-    if ((rc = twiddles(ctx, (int)(2 * p.r.f.M2), st, &T2f, &unused))) return rc;
-    if ((rc = twiddles(ctx, (int)(2 * p.r.b.M1), st, &T1b, &unused))) return rc;
-    if ((rc = twiddles(ctx, (int)(2 * p.r.b.M2), st, &T2b, &unused))) return rc;
-    double2 *Bff = (double2 *)(ws + p.off_Bf), *Bfb = (double2 *)(ws + p.off_Bb);
-    if ((e = ppf::launch_chirp_ft(p.r.f, Bff, Bff + p.r.f.M, T1f, T2f, st)) != hipSuccess)
-        return hip_fail(ctx, e, "k_lf_chirp");
-    if ((e = ppf::launch_chirp_ft(p.r.b, Bfb, Bfb + p.r.b.M, T1b, T2b, st)) != hipSuccess)
-        return hip_fail(ctx, e, "k_lf_chirp");
+    if ((rc = long_tables(ctx, p.r.f, (double2 *)(ws + p.w.chirp), true, st, tf))) return rc;
+    if ((rc = long_tables(ctx, p.r.b, (double2 *)(ws + p.w.chirp_b), true, st, tb))) return rc;
     p.r.f.in_dtype = in_dtype;
     p.r.f.in = in;
     p.r.phases = phases;
     p.r.taus = taus;
     p.r.out = out;
-    for (int64_t r0 = 0; r0 < nrows; r0 += p.rows_c) {
+    return for_chunks(nrows, p.w.rows, [&](int64_t r0, int64_t nr) {
         p.r.f.row0 = p.r.b.row0 = r0;
-        const int64_t nr = nrows - r0 < p.rows_c ? nrows - r0 : p.rows_c;
-        e = ppf::launch_rotate_long(p.r, nr, (double2 *)(ws + p.off_A), (double2 *)(ws + p.off_Y), Bff, Bfb,
-                                    T1f, T2f, T1b, T2b, st);
-        if (e != hipSuccess) return hip_fail(ctx, e, "k_lr");
-    }
-    return PPF_OK;
+        const hipError_t e = ppf::launch_rotate_long(p.r, nr, (double2 *)(ws + p.w.A), (double2 *)(ws + p.w.Y), tf.B,
+                                                     tb.B, tf.T1, tf.T2, tb.T1, tb.T2, st);
+        return e == hipSuccess ? PPF_OK : hip_fail(ctx, e, "k_lr");
+    });
 }
 
 int ppf_scales_batch(ppf_ctx *ctx, int32_t nsub, int32_t nchan, int32_t nharm, const double *D,
@@ -1714,20 +1714,14 @@ int ppf_phase_shift_batch(ppf_ctx *ctx, int32_t nprof, int32_t nbin, int32_t in_
     ppf::LongNoiseArgs f;
     if (!long_row_plan(nbin, f)) return fail(ctx, PPF_EUNSUP, "nbin=%d", nbin);
     const size_t nharm = (size_t)nbin / 2 + 1, row_b = (size_t)f.M * sizeof(double2);
-    FitLayout L{};
-    const int64_t rows = std::max<int64_t>(nprof, nmodel);
-    int64_t rcn = (int64_t)((size_t)(256u << 20) / (2 * row_b));
-    L.lrows = rows < rcn ? rows : (rcn < 1 ? 1 : rcn);
-    size_t o = 0;
-    const size_t oD = o; o += align256(sizeof(double2) * (size_t)nprof * nharm);
-    const size_t oM = o; o += align256(sizeof(double2) * (size_t)nmodel * nharm);
-    L.lchirp = o; o += align256(2 * row_b);
-    L.lA = o; o += align256((size_t)L.lrows * row_b);
-    L.lY = o; o += align256((size_t)L.lrows * row_b);
+    Carver take;
+    const size_t oD = take(sizeof(double2) * (size_t)nprof * nharm);
+    const size_t oM = take(sizeof(double2) * (size_t)nmodel * nharm);
+    const LongWork L = long_work(take, std::max<int64_t>(nprof, nmodel), row_b, 2 * row_b);
     const bool gs = grid_gsh(nbin, Ns, true);
-    const size_t oG = o; o += gs ? align256(sizeof(double) * (size_t)nprof * ((size_t)Ns + 8)) : 0;
+    const size_t oG = take(gs ? sizeof(double) * (size_t)nprof * ((size_t)Ns + 8) : 0);
     std::lock_guard<std::mutex> lk(ctx->lscr_mu);
-    if ((rc = lscr_reserve(ctx, o))) return rc;
+    if ((rc = lscr_reserve(ctx, take.o))) return rc;
     char *ws = (char *)ctx->lscr;
     if ((rc = long_rfft_rows(ctx, L, ws, nbin, nmodel, PPF_F64, model, (double2 *)(ws + oM), false, st))) return rc;
     if ((rc = long_rfft_rows(ctx, L, ws, nbin, nprof, in_dtype, data, (double2 *)(ws + oD), true, st))) return rc;

@@ -80,7 +80,7 @@ struct DsumArgs {
     const double *freqs, *P, *guess_DM, *guess_weights;
     double *gP;                  // [nsub][nblkd][nbin] partial profiles
     double *gw;                  // [nsub][nblkd][2] (sum w, count)
-    const uint8_t *gflag;        // [nsub]: 1 = fused into k_xspec_w (skip), or null
+    const uint8_t *gflag;        // [nsub]: 1 = fused into k_xspec_w2 (skip), or null
     double *nuref;               // [nsub] nu_ref^-2 per sub-int (k_nu_ref), or null:
                                  // every workgroup reduces the frequencies itself
     // bounded launch of k_dsum_w (fused guess with PPF_OPT_NO_X): the
@@ -127,7 +127,7 @@ struct GuessArgs {
     const double2 *Mft;
     const int32_t *model_index;
     const int32_t *KC;           // [nmodel][nchan] harmonic cutoff (k_model_cut) or null
-    // fused guess spectrum (k_xspec_w) for the sub-ints with gflag set
+    // fused guess spectrum (k_xspec_w2) for the sub-ints with gflag set
     const uint8_t *gflag;        // [nsub] or null
     const double2 *gpart;        // [nsub][nblk][guess_slots(log2N)]
     const double *gwx;           // [nsub][nblk][3]
@@ -581,8 +581,7 @@ struct ClassifyArgs {
 };
 hipError_t launch_classify(const ClassifyArgs &a, hipStream_t st);
 // k_xspec_w2 writes the moment-mode sub-ints' X tiled (X[k/8][n][k%8]) for
-// k_moments: 1024-point rows on k_xspec_w2, unless PPF_XTILE=0 (environment,
-// read once) selects the harmonic-major slots and the round's write-out
+// k_moments at this FFT size (1024-point rows)
 bool xspec_tiled(int log2N);
 // harmonics per channel of a tiled slot: whole tiles of 8
 constexpr int kXTile = 8;

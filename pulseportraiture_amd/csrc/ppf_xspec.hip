@@ -5,8 +5,8 @@
 // register/LDS FFT of ppf_wfft.hpp (no workgroup barrier inside a row) and
 // finished by the real-FFT post-pass on (k, N-k) pairs.
 //
-// k_xspec_w<LOG2N, DT>: the cross spectrum for the sub-ints whose fit
-//   streams it (scattering fits, k_pass):
+// k_xspec_w<LOG2N, DT> (128..512 points; k_xspec_w2 at 1024): the cross
+//   spectrum for the sub-ints whose fit streams it (scattering fits, k_pass):
 //     get_noise_PS noise (pplib.py:2312-2332), Sd_n, S_n(tau = 0)
 //     X_k = D_k conj(M_k) / sigma~_n^2 (pptoaslib.py:1014-1031), k = 0 zeroed
 //   Sub-ints fitted from moments (TRState.mmode) are skipped: k_xmom_g
@@ -32,7 +32,6 @@
 //   The first launch of a ppf_fit_batch call (FULL) covers every moment-mode
 //   sub-int in index order; re-centring launches take the sub-ints k_tr_mom
 //   listed (rc_list), packed eight to a workgroup, on 8-channel blocks.
-#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 
@@ -44,12 +43,9 @@
 namespace ppf {
 
 constexpr int kXW = 8;                 // waves per k_align_part_w workgroup
-// waves (= channel rows per round) per k_xspec_w workgroup: 4 at 1024-point
-// rows (two 70 KB workgroups per CU instead of one of 139 KB: a round's
-// write-out barrier holds 4 waves, not 8; C3 k_xspec_w 27.7 vs 29.2 ms),
-// 8 below (C5, 512-point rows: 29.8 vs 37.0 ms)
-template <int LOG2N>
-__host__ __device__ constexpr int xsw() { return LOG2N == 10 ? 4 : 8; }
+// waves (= channel rows per round) per k_xspec_w workgroup (C5, 512-point
+// rows: 29.8 ms with 8, 37.0 with 4)
+constexpr int kXSW = 8;
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 // row elements as native vectors: arrays of HIP_vector_type structs carried
 // across the row loop are not promoted to VGPRs
@@ -112,45 +108,25 @@ __host__ __device__ constexpr int tw_slots() {
 template <int LOG2N>
 __host__ __device__ constexpr int xspec_slw() { return wfft::buf_slots<LOG2N>() + 2; }
 
-// GS: the sub-ints with gflag set (k_classify: every channel's harmonic cutoff
-// below NL = 64 guess_npl) also accumulate the GetTOAs guess spectrum
-// (pptoas.py:461-464 in the Fourier domain, as rotate_data does it):
-// G_k = sum_n w_n D_nk exp(2 pi i k dphi_n), dphi_n = Dconst DM_guess / P
-// (nu_n^-2 - nu_ref^-2), for 1 <= k < NL.  No register holds them: pass 2
-// of the post-pass stores a row's terms in the wave-buffer slots of the
-// harmonics N - k, which X no longer needs (its write-out stops below the
-// cutoff), and the write-out phase adds the round's rows to a workgroup sum
-// in LDS in wave order (deterministic).  The profile's noise for the
-// FFTFIT scale is its expectation from the channels' noise:
-// err^2 = sum_n w_n^2 errs_FT,n^2 / W^2.
-// minimum waves per SIMD: at 1024 points the LDS admits two 4-wave
-// workgroups per CU (two waves per SIMD), and the fused-guess variant must
-// keep that register budget (<= 256).
-// The fused guess runs at 1024 points only: below, its extra registers cost a
-// wave per SIMD or spill, and those shapes take k_dsum_w.  (At 512 points,
-// round 5, C5 per 500 sub-ints in one call: the model reaches harmonic ~430 of
-// 513, above the NL = 192 guess harmonics, so k_classify sets no sub-int and the
-// variant only costs its registers: k_xspec_w<9> 26.5 vs 22.0 ms, 90.1 vs
-// 84.7 ms per step.  Removed.)
+// The fused GetTOAs guess (xspec_w2_block's GS) runs at 1024 points only:
+// below, its extra registers cost a wave per SIMD or spill, and those shapes
+// take k_dsum_w.
 bool xspec_guess_fused_n(int log2N) { return log2N == 10; }
 // One post-pass over the transform: power sums and X together, X scaled at
 // the write-out.
-template <int LOG2N, int DT, bool GS>
-__global__ __launch_bounds__(64 * xsw<LOG2N>()) __attribute__((amdgpu_waves_per_eu(LOG2N == 10 ? 2 : 1)))
+template <int LOG2N, int DT>
+__global__ __launch_bounds__(64 * kXSW) __attribute__((amdgpu_waves_per_eu(1)))
 void k_xspec_w(XspecArgs a) {
-    constexpr int kXSW = xsw<LOG2N>();
     using P = wfft::Plan<LOG2N>;
     constexpr int N = P::N, R = P::R, NH = N + 1;
     constexpr int NP = N / 128;                       // (k, N-k) pairs per lane
     constexpr int SL = xspec_slw<LOG2N>();           // padded wave buffer + 2 side slots
     constexpr int XNYQ = SL - 2;                      // X_{N/2} of the row
     constexpr int XIE2 = SL - 1;                      // the row's 1/errs_FT^2 (.x)
-    // model pairs loaded ahead in pass 2: at 1024 points the 4-wave
-    // workgroups leave VGPRs to spare (LDS caps them at two waves per SIMD:
-    // 4 ahead, C3 27.1 -> 25.5 ms); at 512 points k_xspec_w runs four waves
-    // per SIMD at <= 128 VGPRs, which one pair ahead keeps (126; C5 29.2 ->
-    // 28.6 ms), two would not (132)
-    constexpr int MD = LOG2N == 10 ? 4 : (LOG2N == 9 ? 1 : 0);
+    // model pairs loaded ahead in pass 2: at 512 points k_xspec_w runs four
+    // waves per SIMD at <= 128 VGPRs, which one pair ahead keeps (126; C5
+    // 29.2 -> 28.6 ms), two would not (132)
+    constexpr int MD = LOG2N == 9 ? 1 : 0;
     using RowT = typename std::conditional<DT == 0, vf2, vd2>::type;
     extern __shared__ __attribute__((aligned(16))) double2 lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -198,45 +174,6 @@ void k_xspec_w(XspecArgs a) {
     const int nlr = cbase + lane;
     const double ch_mpow = nlr < cend ? a.Mpow[(int64_t)mi * a.nchan + nlr] : 0.0;
     const double ch_err = (a.errs && nlr < cend) ? a.errs[(int64_t)s * a.nchan + nlr] : 0.0;
-    // fused guess: per-lane channel weight and dedispersion phase of
-    // channel cbase + lane; the workgroup sum G[1..NL) after the twiddles
-    constexpr int NL = 64 * guess_npl(LOG2N);
-    bool gon = false;
-    // the row's weight and dedispersion phase come from wave-uniform loads
-    // (guess_weights, freqs) and two uniform scalars (Dg, nu_ref^-2, moved
-    // to SGPRs): no VGPRs held across the round loop for them
-    double g_Dg = 0.0, g_nrm2 = 0.0, g_w2e2 = 0.0;
-    auto g_wn = [&](int nn) {
-        return a.guess_weights[(int64_t)s * a.nchan + __builtin_amdgcn_readfirstlane(nn)];
-    };
-    auto g_dgn = [&](int nn) {
-        const double f = a.freqs[(int64_t)s * a.nchan + __builtin_amdgcn_readfirstlane(nn)];
-        return g_Dg * (1.0 / (f * f) - g_nrm2);
-    };
-    double2 *gacc = lds + kXSW * SL + tw_slots<LOG2N>();
-    if constexpr (GS) {
-        gon = a.gflag[s] != 0;                         // uniform
-        if (gon) {
-            for (int t = threadIdx.x; t < NL; t += 64 * kXSW) gacc[t] = cmk(0.0, 0.0);
-            // nu_ref: mean usable frequency of the sub-int (GetTOAs) or
-            // nu_fit (ppalign), as k_dsum
-            const double *fr = a.freqs + (int64_t)s * a.nchan;
-            double v0 = 0.0, v1 = 0.0;
-            for (int nn = lane; nn < a.nchan; nn += 64)
-                if (!mask || mask[nn]) { v0 += fr[nn]; v1 += 1.0; }
-            v0 = wave_sum(v0);
-            v1 = wave_sum(v1);
-            const double mu = v0 / v1;
-            double nu_ref_m2 = 1.0 / (mu * mu);
-            if (a.guess_ref) {
-                const double nf = a.nu_fits[(int64_t)s * 3];
-                if (nf == nf) nu_ref_m2 = 1.0 / (nf * nf);
-            }
-            g_Dg = readlane_d(kDconst * a.guess_DM[s] / a.P[s], 0);
-            g_nrm2 = readlane_d(nu_ref_m2, 0);
-            __syncthreads();
-        }
-    }
     RowT zr[R];
     auto fetch = [&](int n) {
         const RowT *src = rows + ((int64_t)s * a.nchan + n) * N;
@@ -283,18 +220,6 @@ void k_xspec_w(XspecArgs a) {
                 const double2 zm = buf[wfft::pad<LOG2N>(N / 2)];
                 Dm = cmk(zm.x, -zm.y);
             }
-            // guess phasor of this row: El = w e^{2 pi i k dphi} at k = lane
-            // + 64 i by recurrence (step e^{2 pi i 64 dphi}: lane 1's phasor
-            // squared six times)
-            double2 El = cmk(0.0, 0.0), Est = El;
-            if (GS && gon) {
-                const double dg = g_dgn(n);
-                const double2 E1 = cexp2pi((double)lane * dg);
-                El = cscale(E1, g_wn(n));
-                Est = cmk(readlane_d(E1.x, 1), readlane_d(E1.y, 1));
-#pragma unroll
-                for (int q = 0; q < 6; ++q) Est = cmul(Est, Est);
-            }
             preload_m();
             double pn = 0.0, pd = 0.0;
             {
@@ -310,31 +235,20 @@ void k_xspec_w(XspecArgs a) {
                     if (khi >= a.kc) pn += p1;
                     if (klo >= 1) pd += p0;
                     pd += p1;
-                    // (fused guess: X stops below NL, past it only the sums)
-                    if (!(GS && gon && 64 * i >= NL)) {
-                        double2 Mlo, Mhi;
-                        if constexpr (MD > 0) {
-                            Mlo = Mq[i % MD][0];
-                            Mhi = Mq[i % MD][1];
-                            if (i + MD < NP) {
-                                Mq[i % MD][0] = Mrow[klo + 64 * MD];
-                                Mq[i % MD][1] = Mrow[khi - 64 * MD];
-                            }
-                        } else {
-                            Mlo = Mrow[klo];
-                            Mhi = Mrow[khi];
+                    double2 Mlo, Mhi;
+                    if constexpr (MD > 0) {
+                        Mlo = Mq[i % MD][0];
+                        Mhi = Mq[i % MD][1];
+                        if (i + MD < NP) {
+                            Mq[i % MD][0] = Mrow[klo + 64 * MD];
+                            Mq[i % MD][1] = Mrow[khi - 64 * MD];
                         }
-                        buf[wfft::pad<LOG2N>(klo)] = (klo == 0) ? cmk(0.0, 0.0) : cmulc(Dlo, Mlo);
-                        if (GS && gon) {
-                            // X_{N-k} is past the cutoff: its slot takes the
-                            // row's guess term of harmonic k (k = 0: dropped)
-                            if (klo != 0) buf[wfft::pad<LOG2N>(khi)] = cmul(Dlo, El);
-                            El = cmul(El, Est);
-                        } else {
-                            buf[klo == 0 ? wfft::pad<LOG2N>(N / 2) : wfft::pad<LOG2N>(khi)] =
-                                cmulc(Dhi, Mhi);
-                        }
+                    } else {
+                        Mlo = Mrow[klo];
+                        Mhi = Mrow[khi];
                     }
+                    buf[wfft::pad<LOG2N>(klo)] = (klo == 0) ? cmk(0.0, 0.0) : cmulc(Dlo, Mlo);
+                    buf[klo == 0 ? wfft::pad<LOG2N>(N / 2) : wfft::pad<LOG2N>(khi)] = cmulc(Dhi, Mhi);
                     SCHED_CUT();
                 }
             }
@@ -349,10 +263,6 @@ void k_xspec_w(XspecArgs a) {
             if (a.errs) errs_FT = readlane_d(ch_err, n - cbase) * sqrtN;
             else errs_FT = sqrt(pn / (double)(NH - a.kc) / (double)(2 * N)) * sqrtN;
             const double inv_e2 = 1.0 / (errs_FT * errs_FT);
-            if (GS && gon) {
-                const double wn = g_wn(n);
-                g_w2e2 += wn * wn * errs_FT * errs_FT;
-            }
             if (lane == 0) {
                 buf[XNYQ] = cmulc(Dm, Mrow[N / 2]);
                 reinterpret_cast<double *>(buf + XIE2)[0] = inv_e2;   // for the write-out
@@ -380,40 +290,7 @@ void k_xspec_w(XspecArgs a) {
                 }
             }
         }
-        if (GS && gon) {
-            // the round's rows' guess terms, in wave order
-            for (int t = threadIdx.x; t < NL; t += 64 * kXSW) {
-                if (t == 0) continue;
-                double2 acc = gacc[t];
-#pragma unroll
-                for (int w2 = 0; w2 < kXSW; ++w2)
-                    if (usable(cbase + r * kXSW + w2)) acc = cadd(acc, lds[w2 * SL + wfft::pad<LOG2N>(N - t)]);
-                gacc[t] = acc;
-            }
-        }
         __syncthreads();
-    }
-    if constexpr (GS) {
-        if (gon) {
-            double2 *gp = a.gpart + ((int64_t)s * a.nblk + cb) * NL;
-            for (int t = threadIdx.x; t < NL; t += 64 * kXSW) gp[t] = gacc[t];
-            // the block's weight sum and usable-channel count (every wave
-            // holds the block's weights in its lanes), and sum w^2 errs_FT^2
-            // per wave, added in wave order (buffer slot 0 is free after the
-            // last round's barrier)
-            const double gwl = mlane ? a.guess_weights[(int64_t)s * a.nchan + cbase + lane] : 0.0;
-            const double wsum = wave_sum(gwl), cnt = wave_sum(mlane ? 1.0 : 0.0);
-            if (lane == 0) reinterpret_cast<double *>(buf)[0] = g_w2e2;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                double acc = 0.0;
-                for (int w2 = 0; w2 < kXSW; ++w2) acc += reinterpret_cast<const double *>(lds + w2 * SL)[0];
-                double *o = a.gw + ((int64_t)s * a.nblk + cb) * 3;
-                o[0] = wsum;
-                o[1] = cnt;
-                o[2] = acc;
-            }
-        }
     }
 }
 
@@ -838,7 +715,7 @@ __global__ __launch_bounds__(256) void k_model_sum(const double2 *Mft, int nchan
 // ===========================================================================
 // k_xspec_w2: k_xspec_w for 1024-point rows (2048 bins) on the one-exchange
 // wave FFT of ppf_wfft2.hpp (round 5).  Same outputs and the same
-// workgroup structure (4 waves, a round of 4 channel rows, X written
+// workgroup structure (here 4 waves, a round of 4 channel rows, X written
 // harmonic-major after a barrier), but per row:
 //   - one LDS exchange inside the FFT instead of three, no natural-order
 //     write-back: the real post-pass takes each pair (Z_k, Z_{N-k}) from
@@ -849,9 +726,16 @@ __global__ __launch_bounds__(256) void k_model_sum(const double2 *Mft, int nchan
 //     when the group's cutoff passes N/2);
 //   - the X staging slots are k + k/64 (k <= N): no special Nyquist slot.
 // get_noise_PS (pplib.py:2312-2332), Sd, S(tau = 0) and X = D conj(M) /
-// sigma~^2 (pptoaslib.py:1014-1031) as k_xspec_w; the fused GetTOAs guess
-// (GS, pptoas.py:461-464) as k_xspec_w, its terms in the slots of N - k.
-// PPF_XSPEC2=0 (environment) selects k_xspec_w instead.
+// sigma~^2 (pptoaslib.py:1014-1031) as k_xspec_w.
+//
+// GS: the sub-ints with gflag set (k_classify: every channel's harmonic cutoff
+// below NL = 64 guess_npl) also accumulate the GetTOAs guess spectrum
+// (pptoas.py:461-464 in the Fourier domain, as rotate_data does it):
+// G_k = sum_n w_n D_nk exp(2 pi i k dphi_n), dphi_n = Dconst DM_guess / P
+// (nu_n^-2 - nu_ref^-2), for 1 <= k < NL.  A row's terms go to the staging
+// slots of the harmonics N - k, which X no longer needs (its write-out stops
+// below the cutoff).  The profile's noise for the FFTFIT scale is its
+// expectation from the channels' noise: err^2 = sum_n w_n^2 errs_FT,n^2 / W^2.
 //
 // TL (round 7): the sub-ints whose slot is tiled (XspecArgs::xtile: the
 // moment-mode ones, read by k_moments).  X[slot][k/8][n][k%8] keeps one
@@ -871,7 +755,8 @@ __global__ __launch_bounds__(256) void k_model_sum(const double2 *Mft, int nchan
 // spectrum differs in its last bits (summation order, and the row's phasors
 // taken as powers of one phasor per channel: see ch_e1).  !TL: the
 // harmonic-major slots (scattering sub-ints, which k_pass streams; every
-// sub-int with PPF_XTILE=0) and the round's write-out after a barrier.
+// sub-int of a call without a tile table) and the round's write-out after a
+// barrier.
 // ===========================================================================
 // waves per workgroup (= rows per round; !TL: channels per X line written,
 // 64-B segments of the 128-B lines); two workgroups per CU
@@ -1469,24 +1354,21 @@ __device__ __forceinline__ void wmr_stage_g(double2 *buf, int N, int L, int R, c
 // (the LDS of a workgroup -- four row buffers and the twiddles -- admits
 // three of them per CU at NMAX 512 and two at 1024, so the register budget
 // is three / two waves per SIMD)
-// ODD: odd nbin (<= 1023), the row as NF = nbin complex points with zero
-// imaginary parts (rfft_len), X_k = Z_k for k <= nbin / 2: no pair post-pass.
-template <int DT, int NMAX, bool ODD>
+// (even nbin only: odd nbin takes k_xspec_wo)
+template <int DT, int NMAX>
 __global__ __launch_bounds__(64 * kWmW) __attribute__((amdgpu_waves_per_eu(NMAX <= 512 ? 3 : 2)))
 void k_xspec_wm(XspecArgs a) {
     const int N = a.nbin >> 1, NH = N + 1;
-    const int NF = ODD ? a.nbin : N;           // complex points per row
-    // even: [0, N] Z then X, [N + 1] 1/errs_FT^2; odd: Z in [0, NF), X in
-    // [0, N] and 1/errs_FT^2 in [N + 1] after the post-pass (N + 1 < NF)
-    const int SL = ODD ? NF : N + 2, IE = N + 1;
+    // [0, N] Z then X, [N + 1] 1/errs_FT^2
+    const int SL = N + 2, IE = N + 1;
     extern __shared__ __attribute__((aligned(16))) double2 lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double2 *buf = lds + wave * SL;
-    double2 *twl = lds + kWmW * SL;            // T[0, NF): the stage twiddles
+    double2 *twl = lds + kWmW * SL;            // T[0, N): the stage twiddles
     int s, cb;
     block_map(a.xcd_swizzle, a.nblk, s, cb, a.nsub);
     if (a.needx && !a.needx[s]) return;
-    for (int i = threadIdx.x; i < NF; i += 64 * kWmW) twl[i] = a.T[i];
+    for (int i = threadIdx.x; i < N; i += 64 * kWmW) twl[i] = a.T[i];
     __syncthreads();
     const int cbase = cb * a.cb, cend = min(a.nchan, cbase + a.cb);
     const int nround = (a.cb + kWmW - 1) / kWmW;
@@ -1506,19 +1388,18 @@ void k_xspec_wm(XspecArgs a) {
     const int nl = cbase + lane;
     const double ch_mpow = nl < cend ? a.Mpow[(int64_t)mi * a.nchan + nl] : 0.0;
     const double ch_err = (a.errs && nl < cend) ? a.errs[(int64_t)s * a.nchan + nl] : 0.0;
-    const bool two0 = !ODD && (__builtin_ctz((unsigned)N) & 1) != 0;
+    const bool two0 = (__builtin_ctz((unsigned)N) & 1) != 0;
     // the wave's next row in registers while this one is transformed
     // (unconditional loads of a valid row: the prefetch stays in VGPRs)
-    using ET = typename std::conditional<DT == 0, float, double>::type;
-    using LT = typename std::conditional<ODD, ET, typename std::conditional<DT == 0, float2, double2>::type>::type;
+    using LT = typename std::conditional<DT == 0, float2, double2>::type;
     constexpr int PJ = NMAX / 64;
     LT pre[PJ];
     auto fetch = [&](int m) {
-        const LT *src = reinterpret_cast<const LT *>(a.data) + ((int64_t)s * a.nchan + m) * (int64_t)NF;
+        const LT *src = reinterpret_cast<const LT *>(a.data) + ((int64_t)s * a.nchan + m) * (int64_t)N;
 #pragma unroll
         for (int i = 0; i < PJ; ++i) {
             const int t = lane + 64 * i;
-            pre[i] = ld_stream(src + (t < NF ? t : NF - 1));
+            pre[i] = ld_stream(src + (t < N ? t : N - 1));
         }
     };
     fetch(min(cbase + wave, cend - 1));
@@ -1529,11 +1410,7 @@ void k_xspec_wm(XspecArgs a) {
 #pragma unroll
             for (int i = 0; i < PJ; ++i) {
                 const int t = lane + 64 * i;
-                if constexpr (ODD) {
-                    if (t < NF) buf[t] = cmk((double)pre[i], 0.0);
-                } else {
-                    if (t < N) buf[t] = cmk((double)pre[i].x, (double)pre[i].y);
-                }
+                if (t < N) buf[t] = cmk((double)pre[i].x, (double)pre[i].y);
             }
         }
         fetch(min(n + kWmW, cend - 1));
@@ -1542,7 +1419,7 @@ void k_xspec_wm(XspecArgs a) {
             wfft::wave_sync();
             // the stages in fft_radices' order (one 2 when the power of two
             // is odd, 4s, then the odd primes ascending), wave-uniform
-            int L = 1, rem = NF;
+            int L = 1, rem = N;
             bool two = two0;
             while (rem > 1) {
                 int R;
@@ -1550,11 +1427,11 @@ void k_xspec_wm(XspecArgs a) {
                 else if ((rem & 3) == 0) R = 4;
                 else { R = 3; while (rem % R) R += 2; }
                 switch (R) {
-                    case 2: wmr_stage<2, NMAX>(buf, NF, L, twl, lane); break;
-                    case 3: wmr_stage<3, NMAX>(buf, NF, L, twl, lane); break;
-                    case 4: wmr_stage<4, NMAX>(buf, NF, L, twl, lane); break;
-                    case 5: wmr_stage<5, NMAX>(buf, NF, L, twl, lane); break;
-                    default: wmr_stage_g<NMAX>(buf, NF, L, R, twl, lane); break;
+                    case 2: wmr_stage<2, NMAX>(buf, N, L, twl, lane); break;
+                    case 3: wmr_stage<3, NMAX>(buf, N, L, twl, lane); break;
+                    case 4: wmr_stage<4, NMAX>(buf, N, L, twl, lane); break;
+                    case 5: wmr_stage<5, NMAX>(buf, N, L, twl, lane); break;
+                    default: wmr_stage_g<NMAX>(buf, N, L, R, twl, lane); break;
                 }
                 L *= R;
                 rem /= R;
@@ -1564,15 +1441,7 @@ void k_xspec_wm(XspecArgs a) {
             // slot N); unscaled, the write-out applies 1/errs_FT^2
             const double2 *Mrow = a.Mft + ((int64_t)mi * a.nchan + n) * NH;
             double pn = 0.0, pd = 0.0;
-            // odd nbin: X_k = Z_k (k <= N), each lane its own slots
-            for (int k = lane; ODD && k <= N; k += 64) {
-                const double2 dk = buf[k];
-                const double p0 = cabs2(dk);
-                if (k >= a.kc) pn += p0;
-                if (k >= 1) pd += p0;
-                if (k < kw) buf[k] = k == 0 ? cmk(0.0, 0.0) : cmulc(dk, Mrow[k]);
-            }
-            for (int k = lane; !ODD && k <= N / 2; k += 64) {
+            for (int k = lane; k <= N / 2; k += 64) {
                 const int kn = N - k;
                 const double2 dk = rfft_bin(buf, N, a.T2, k);
                 const double2 dn = rfft_bin(buf, N, a.T2, kn);
@@ -1627,8 +1496,8 @@ void k_xspec_wm(XspecArgs a) {
 // complex transform: row A as the real part, row B as the imaginary part,
 // Z = FFT_NF(a + i b) (NF = nbin points, the stages of k_xspec_wm), then
 // X_A(k) = (Z_k + conj Z_{NF-k}) / 2 and X_B(k) = (Z_k - conj Z_{NF-k}) / 2i
-// for k <= N = nbin / 2: half the transform work per row of the one-row
-// path (k_xspec_wm<ODD>, PPF_XSPEC_WO=0).  A round is 8 rows, two per wave
+// for k <= N = nbin / 2: half the transform work per row of one row per
+// transform.  A round is 8 rows, two per wave
 // (rows w and w + 4 of the round).  Each pair (k, NF - k) is read and
 // written back by one lane in its own two slots: the unscaled X of row A at
 // slot k, of row B at slot NF - k (k = 1 .. N); the k = 0 positions (X_0 = 0:
@@ -1803,35 +1672,20 @@ void k_xspec_wo(XspecArgs a) {
     }
 }
 
-// nbin / 2 <= 1024 not a power of two; odd nbin < 1024 (NF = nbin points)
+// nbin / 2 <= 1024 not a power of two (k_xspec_wm); odd nbin < 1024
+// (k_xspec_wo, NF = nbin points)
 bool xspec_wm_supported(int nbin) {
     if (nbin & 1) return nbin >= 33 && nbin < kWmMaxN;
     const int N = nbin / 2;
     return !is_pow2(N) && N <= kWmMaxN && fft_len_supported(N);
 }
 
-#define PPF_WM_LAUNCH(NM, ODD)                                                           \
-    do {                                                                                 \
-        if (a.dtype == 0) hipLaunchKernelGGL((k_xspec_wm<0, NM, ODD>), g, b, lds, st, a); \
-        else hipLaunchKernelGGL((k_xspec_wm<1, NM, ODD>), g, b, lds, st, a);              \
-    } while (0)
-
-// odd nbin: two rows per transform (k_xspec_wo) unless PPF_XSPEC_WO=0
-// (environment, read once: the one-row k_xspec_wm<ODD>)
-static bool use_xspec_wo() {
-    static const bool on = [] {
-        const char *e = getenv("PPF_XSPEC_WO");
-        return e ? atoi(e) != 0 : true;
-    }();
-    return on;
-}
-
+// odd nbin: two rows per transform (k_xspec_wo); even: k_xspec_wm
 hipError_t launch_xspec_wm(const XspecArgs &a, hipStream_t st) {
-    const bool odd = a.nbin & 1;
     const int NF = rfft_len(a.nbin);
-    if (odd && use_xspec_wo()) {
+    dim3 g((unsigned)((int64_t)a.nsub * a.nblk)), b(64 * kWmW);
+    if (a.nbin & 1) {
         const size_t lds = ((size_t)kWmW * (NF + 1) + NF) * sizeof(double2);
-        dim3 g((unsigned)((int64_t)a.nsub * a.nblk)), b(64 * kWmW);
         if (NF <= 512) {
             if (a.dtype == 0) hipLaunchKernelGGL((k_xspec_wo<0, 512>), g, b, lds, st, a);
             else hipLaunchKernelGGL((k_xspec_wo<1, 512>), g, b, lds, st, a);
@@ -1841,83 +1695,63 @@ hipError_t launch_xspec_wm(const XspecArgs &a, hipStream_t st) {
         }
         return hipGetLastError();
     }
-    const size_t lds = ((size_t)kWmW * (odd ? NF : NF + 2) + NF) * sizeof(double2);
-    dim3 g((unsigned)((int64_t)a.nsub * a.nblk)), b(64 * kWmW);
+    const size_t lds = ((size_t)kWmW * (NF + 2) + NF) * sizeof(double2);
     if (NF <= 512) {
-        if (odd) PPF_WM_LAUNCH(512, true);
-        else PPF_WM_LAUNCH(512, false);
+        if (a.dtype == 0) hipLaunchKernelGGL((k_xspec_wm<0, 512>), g, b, lds, st, a);
+        else hipLaunchKernelGGL((k_xspec_wm<1, 512>), g, b, lds, st, a);
     } else {
-        if (odd) PPF_WM_LAUNCH(1024, true);
-        else PPF_WM_LAUNCH(1024, false);
+        if (a.dtype == 0) hipLaunchKernelGGL((k_xspec_wm<0, 1024>), g, b, lds, st, a);
+        else hipLaunchKernelGGL((k_xspec_wm<1, 1024>), g, b, lds, st, a);
     }
     return hipGetLastError();
 }
 
-// k_xspec_w2 at 1024 points unless PPF_XSPEC2=0 (environment, read once)
-static bool use_xspec2() {
-    static const bool on = [] {
-        const char *e = getenv("PPF_XSPEC2");
-        return e ? atoi(e) != 0 : true;
-    }();
-    return on;
-}
-// tiled X slots for the moment-mode sub-ints of k_xspec_w2 unless PPF_XTILE=0
-// (environment, read once): then every slot is harmonic-major and written
-// by the round's write-out, as before round 7
-bool xspec_tiled(int log2N) {
-    static const bool on = [] {
-        const char *e = getenv("PPF_XTILE");
-        return e ? atoi(e) != 0 : true;
-    }();
-    return on && log2N == 10 && use_xspec2();
-}
+// tiled X slots for the moment-mode sub-ints: 1024-point rows (k_xspec_w2)
+bool xspec_tiled(int log2N) { return log2N == 10; }
 
 // ===========================================================================
 // launchers
 // ===========================================================================
+// 1024 points: k_xspec_w2; below: k_xspec_w
 template <int L2, int DT>
 static void launch_w(const XspecArgs &a, hipStream_t st) {
     if constexpr (L2 == 10) {
-        if (use_xspec2()) {
-            const size_t lds = (size_t)kX2W * kX2SL * sizeof(double2);
-            dim3 g((unsigned)((int64_t)a.nsub * a.nblk)), b(64 * kX2W);
-            // tiled slots (xtile): the moment-mode sub-ints on the TL
-            // instantiation, then the scattering ones (harmonic-major slots)
-            // on the other; each skips the other's sub-ints
-            if (a.xtile) {
-                if (a.gflag)
-                    hipLaunchKernelGGL((k_xspec_w2<DT, true, true>), g, b,
-                                       lds + (size_t)256 * sizeof(double2), st, a);   // the [4][64] lane table
-                else hipLaunchKernelGGL((k_xspec_w2<DT, false, true>), g, b, lds, st, a);
-            }
-            // (bounded where the caller expects no such sub-int: a.list)
-            const dim3 gh = a.list ? dim3(kX2ListGrid) : g;
-            if (a.gflag) {
-                const size_t ldg = lds + (size_t)guess_slots(10) * sizeof(double2);
-                if (a.list) hipLaunchKernelGGL((k_xspec_w2_list<DT, true>), gh, b, ldg, st, a);
-                else hipLaunchKernelGGL((k_xspec_w2<DT, true, false>), gh, b, ldg, st, a);
-            } else {
-                if (a.list) hipLaunchKernelGGL((k_xspec_w2_list<DT, false>), gh, b, lds, st, a);
-                else hipLaunchKernelGGL((k_xspec_w2<DT, false, false>), gh, b, lds, st, a);
-            }
-            return;
+        const size_t lds = (size_t)kX2W * kX2SL * sizeof(double2);
+        dim3 g((unsigned)((int64_t)a.nsub * a.nblk)), b(64 * kX2W);
+        // tiled slots (xtile): the moment-mode sub-ints on the TL
+        // instantiation, then the scattering ones (harmonic-major slots)
+        // on the other; each skips the other's sub-ints
+        if (a.xtile) {
+            if (a.gflag)
+                hipLaunchKernelGGL((k_xspec_w2<DT, true, true>), g, b,
+                                   lds + (size_t)256 * sizeof(double2), st, a);   // the [4][64] lane table
+            else hipLaunchKernelGGL((k_xspec_w2<DT, false, true>), g, b, lds, st, a);
         }
+        // (bounded where the caller expects no such sub-int: a.list)
+        const dim3 gh = a.list ? dim3(kX2ListGrid) : g;
+        if (a.gflag) {
+            const size_t ldg = lds + (size_t)guess_slots(10) * sizeof(double2);
+            if (a.list) hipLaunchKernelGGL((k_xspec_w2_list<DT, true>), gh, b, ldg, st, a);
+            else hipLaunchKernelGGL((k_xspec_w2<DT, true, false>), gh, b, ldg, st, a);
+        } else {
+            if (a.list) hipLaunchKernelGGL((k_xspec_w2_list<DT, false>), gh, b, lds, st, a);
+            else hipLaunchKernelGGL((k_xspec_w2<DT, false, false>), gh, b, lds, st, a);
+        }
+    } else {
+        const size_t lds = ((size_t)kXSW * xspec_slw<L2>() + tw_slots<L2>()) * sizeof(double2);
+        dim3 g((unsigned)((int64_t)a.nsub * a.nblk)), b(64 * kXSW);
+        hipLaunchKernelGGL((k_xspec_w<L2, DT>), g, b, lds, st, a);
     }
-    const size_t lds = ((size_t)xsw<L2>() * xspec_slw<L2>() + tw_slots<L2>()) * sizeof(double2);
-    dim3 g((unsigned)((int64_t)a.nsub * a.nblk)), b(64 * xsw<L2>());
-    if (a.gflag && L2 == 10)                          // the fused guess (xspec_guess_fused_n)
-        hipLaunchKernelGGL((k_xspec_w<L2, DT, L2 == 10>), g, b,
-                           lds + (size_t)guess_slots(L2) * sizeof(double2), st, a);
-    else hipLaunchKernelGGL((k_xspec_w<L2, DT, false>), g, b, lds, st, a);
 }
 
 // k_xspec_w2 takes 64 channels per workgroup (its lane registers hold one
 // channel's scalars per lane; round 9: half the workgroups, prologues and
 // guess partials of the layout's 32)
-int xspec_own_cb(int log2N) { return (log2N == 10 && use_xspec2()) ? 64 : 0; }
+int xspec_own_cb(int log2N) { return log2N == 10 ? 64 : 0; }
 
+// (k_xspec_w2's four-row rounds divide every cb that kXSW does)
 bool xspec_wave_supported(int log2N, int cb) {
-    return log2N >= 7 && log2N <= 10 && cb % xsw<7>() == 0 && cb % xsw<10>() == 0 && cb % kXW == 0;
+    return log2N >= 7 && log2N <= 10 && cb % kXSW == 0 && cb % kXW == 0;
 }
 
 hipError_t launch_xspec_wave(const XspecArgs &a, hipStream_t st) {

@@ -122,9 +122,10 @@ def test_workspace_query_and_validation_without_gpu():
 
 
 def test_workspace_bytes_match_golden_table():
-    """ppf_fit_workspace_bytes, byte for byte, over the descriptor grid of
-    tests/golden/make_golden_workspace.py (the table comes from a build of
-    the commit before the workspace carving was last rewritten)."""
+    """ppf_fit_workspace_bytes and the long transforms' workspace queries,
+    byte for byte, over the grids of tests/golden/make_golden_workspace.py
+    (the tables come from a build of the commit before the workspace carving
+    was last rewritten)."""
     import json
     golden = os.path.join(os.path.dirname(__file__), "golden")
     with open(os.path.join(golden, "fit_workspace.json")) as f:
@@ -142,6 +143,23 @@ def test_workspace_bytes_match_golden_table():
         d.guess, d.guess_Ns, d.options, d.x_subints = guess, ns, options, xs
         assert lib.ppf_fit_workspace_bytes(ctypes.byref(d)) == nbytes, \
             (nbin, nchan, nsub, nmodel, guess, ns, options, xs)
+    # the long transforms' workspaces (zeros where a shape is refused)
+    with open(os.path.join(golden, "long_workspace.json")) as f:
+        entries = json.load(f)
+    assert len(entries) == 5 * 12
+    assert {(e[0], e[1]) for e in entries} == {
+        (nrows, nbin) for nrows in (0, 1, 3, 600, 70000)
+        for nbin in (1, 2, 3, 33, 4097, 8186, 8194, 16384, 1 << 20,
+                     511 * 1023, 1 << 25, (1 << 25) + 2)}
+    for nrows, nbin, noise, noise_fit, rot0, rot1 in entries:
+        assert lib.ppf_noise_long_workspace_bytes(nrows, nbin) == noise, \
+            (nrows, nbin)
+        assert lib.ppf_noise_fit_long_workspace_bytes(nrows, nbin) == \
+            noise_fit, (nrows, nbin)
+        assert lib.ppf_rotate_long_workspace_bytes(nrows, nbin, 0) == rot0, \
+            (nrows, nbin)
+        assert lib.ppf_rotate_long_workspace_bytes(nrows, nbin, 1) == rot1, \
+            (nrows, nbin)
 
 
 @pytest.mark.parametrize("seed", range(40))

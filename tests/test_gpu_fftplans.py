@@ -359,3 +359,41 @@ def test_fit_single_equals_batch(name):
                   "covariance"):
             np.testing.assert_array_equal(one[k][0], full[k][i],
                                           err_msg="%s sub %d" % (k, i))
+
+
+def test_long_rows_chunked_equal_unchunked():
+    """The long transforms with more rows than one 256-MB chunk of work rows
+    holds (at 4097 and 8194 bins the plan is M = 16384: 512 rows per chunk):
+    a row's transform does not depend on its chunk, so the same rows sent as
+    two calls that fit one chunk each are bitwise equal.
+    (a) 600 f32 rows of 4097 bins through ppf_noise_long (also against
+    NumPy's rFFT at test_noise_long_rows_match_numpy's rtol 1e-11) and
+    ppf_rotate_long; (b) one fit of 10 sub-ints x 64 channels at 8194 bins
+    (phase + DM, GetTOAs guess: 640 data rows through long_rfft_rows)
+    against the same sub-ints as two calls of 5."""
+    from pulseportraiture_amd import engine
+    rng = np.random.default_rng(4097)
+    x = rng.normal(size=(600, 4097)).astype(np.float32)
+    ph = rng.uniform(-0.5, 0.5, 600)
+    noise = _np(engine.noise_rows_long(x))
+    np.testing.assert_array_equal(
+        noise, np.concatenate([_np(engine.noise_rows_long(x[:300])),
+                               _np(engine.noise_rows_long(x[300:]))]))
+    F64 = np.fft.rfft(x.astype(np.float64), axis=-1)
+    p = np.real(F64 * np.conj(F64)) / x.shape[-1]
+    np.testing.assert_allclose(
+        noise, np.sqrt(np.mean(p[:, int((1 - 4 ** -1) * p.shape[-1]):],
+                               axis=-1)), rtol=1e-11)
+    np.testing.assert_array_equal(
+        _np(engine.rotate_rows(x, ph)),
+        np.concatenate([_np(engine.rotate_rows(x[:300], ph[:300])),
+                        _np(engine.rotate_rows(x[300:], ph[300:]))]))
+    # (b) the case's four sub-ints (ragged.masks), repeated to ten
+    c = R._case("long", 8194, 64, R.PD, guess=True)
+    subs = [0, 1, 2, 3, 0, 1, 2, 3, 0, 1]
+    full = R.device_fit(c, subs)
+    halves = [R.device_fit(c, subs[:5]), R.device_fit(c, subs[5:])]
+    for k in ("results", "scales", "scale_errs", "channel_snrs",
+              "covariance"):
+        np.testing.assert_array_equal(
+            full[k], np.concatenate([h[k] for h in halves]), err_msg=k)
