@@ -770,6 +770,31 @@ int ppf_swt_score_batch(ppf_ctx *ctx, int32_t nprof, int32_t nbin, int32_t nleve
                         int32_t ncase, const int32_t *cases, const double *fact, double *out,
                         double *smooth, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ppf_swt_search_batch (added within ABI 6): the fmin finish of
+ * scipy.optimize.brute(..., Ns = ngrid, full_output=True) for every (profile,
+ * level L in 1 .. nlevel) of the analysed batch (same prof, medians, noise,
+ * workspace), one workgroup each, with one threshold type (soft 0 / 1).  The
+ * objective of a (signal, noise, red_chi2) triple is pplib._wavelet_snr:
+ * -signal / noise (-inf for noise 0, 0 for signal 0), 0 where
+ * |red_chi2 - 1| > rchi2_tol.  grid [ngrid] f64 is a HOST array (copied by
+ * the call, untouched until the stream has passed it); table
+ * [nprof][nlevel][ngrid][3] f64, device, is the out of one
+ * ppf_swt_score_batch call over the cases (p, L, soft) x grid in that order.
+ * From x0 = the first grid point of minimal objective the kernel runs
+ * scipy's Nelder-Mead in one dimension (xatol = fatol = 1e-4, at most 200
+ * calls; DESIGN.md gives the recurrence), every evaluation the scoring body
+ * of ppf_swt_score_batch, and returns, [nprof][nlevel] each, device:
+ * fact_min (f64) the best factor, fun_min (f64) its objective, nfev (int32)
+ * the calls made.  The workspace must hold max(ngrid, 1) cases.  Errors as
+ * ppf_swt_score_batch, and PPF_EINVAL for ngrid < 1, a non-finite grid value
+ * or tolerance, soft outside {0, 1}; all checked on the host before any
+ * launch. */
+int ppf_swt_search_batch(ppf_ctx *ctx, int32_t nprof, int32_t nbin, int32_t nlevel,
+                         const double *prof, const double *medians, const double *noise,
+                         int32_t soft, double rchi2_tol, int32_t ngrid, const double *grid,
+                         const double *table, double *fact_min, double *fun_min, int32_t *nfev,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* Spline (PCA + B-spline) model portraits: pplib.gen_spline_portrait
  * (pplib.py:966-990) as called by pplib.read_spline_model (pplib.py:3060-3096)
  * from pptoas.GetTOAs.get_TOAs (pptoas.py:416-419) for make_spline_model

@@ -162,6 +162,10 @@ SIGNATURES = {
     "ppf_swt_score_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _vp,
                                            _vp, _i32, _vp, _vp, _vp, _vp, _vp,
                                            ctypes.c_size_t, _vp]),
+    "ppf_swt_search_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _vp,
+                                            _vp, _i32, ctypes.c_double, _i32,
+                                            _vp, _vp, _vp, _vp, _vp, _vp,
+                                            ctypes.c_size_t, _vp]),
     "ppf_spline_portrait_batch": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32,
                                                  _i32, _i32, _i32, _vp, _vp,
                                                  _vp, _vp, _vp, _vp, _vp]),

@@ -27,6 +27,13 @@ find_significant_eigvec compute with:
     ev.score(h, cases, facts, smooth) -> out [ncase, 3] = (signal, noise,
                                          red_chi2) and the smoothed rows
                                          [ncase, n] (None unless smooth)
+    ev.search(h, soft, rchi2_tol, grid)
+                                      -> fact_min, fun_min, nfev, each
+                                         [nprof, nlevel]: per (profile,
+                                         level) what scipy.optimize.brute
+                                         over that grid of factors returns
+                                         with its fmin finish (x, fval) and
+                                         the calls the finish made (fmin_1d)
 
 cases is a sequence of (profile, level, soft).  NumpyEvaluator (this file,
 FFT-based convolutions, no GPU) and engine.SwtEvaluator (the device kernels
@@ -132,6 +139,95 @@ def lam_of(fact, median, nbin):
     return fact * (median / 0.6745) * np.sqrt(2 * np.log(nbin))
 
 
+FMIN_MAXFUN = 200
+FMIN_TOL = 1e-4
+
+
+def fmin_1d(func, x0):
+    """scipy.optimize.fmin(func, x0, full_output=True, disp=False) for a
+    scalar x0, (x, fval, calls): _minimize_neldermead in one dimension,
+    where the simplex is two points, (s0, f0) the better one (xatol = fatol
+    = 1e-4, at most 200 calls; the iteration cap of 200 cannot bind first,
+    every iteration makes a call).  The products 3 * s0, 1.5 * s0, 1.05 * x0
+    round before the subtraction, as NumPy's array arithmetic does there.
+    A call that would be number 201 is not made and the step it belongs to
+    is abandoned with what it had already assigned (_MaxFuncCallError).  The
+    comparisons are IEEE ones; k_swt_search (ppf_swt.hip) is this function
+    on the device.  An objective returning NaN is outside what this
+    reproduces (scipy sorts a NaN last)."""
+    x0 = float(x0)
+    calls = [0]
+
+    class _Cap(Exception):
+        pass
+
+    def f(x):
+        if calls[0] >= FMIN_MAXFUN:
+            raise _Cap()
+        calls[0] += 1
+        return float(func(x))
+
+    s0, s1 = x0, ((1 + 0.05) * x0 if x0 != 0 else 0.00025)
+    f0, f1 = f(s0), f(s1)
+    if f1 < f0:
+        s0, s1, f0, f1 = s1, s0, f1, f0
+    while calls[0] < FMIN_MAXFUN:
+        if abs(s1 - s0) <= FMIN_TOL and abs(f0 - f1) <= FMIN_TOL:
+            break
+        try:
+            xr = 2.0 * s0 - 1.0 * s1
+            fxr = f(xr)
+            shrink = False
+            if fxr < f0:
+                xe = 3.0 * s0 - 2.0 * s1
+                fxe = f(xe)
+                s1, f1 = (xe, fxe) if fxe < fxr else (xr, fxr)
+            elif fxr < f1:
+                xc = 1.5 * s0 - 0.5 * s1
+                fxc = f(xc)
+                if fxc <= fxr:
+                    s1, f1 = xc, fxc
+                else:
+                    shrink = True
+            else:
+                xcc = 0.5 * s0 + 0.5 * s1
+                fxcc = f(xcc)
+                if fxcc < f1:
+                    s1, f1 = xcc, fxcc
+                else:
+                    shrink = True
+            if shrink:
+                s1 = s0 + 0.5 * (s1 - s0)
+                f1 = f(s1)
+        except _Cap:
+            pass
+        if f1 < f0:
+            s0, s1, f0, f1 = s1, s0, f1, f0
+    return s0, (f1 if f1 < f0 else f0), calls[0]
+
+
+def wavelet_snr(score, rchi2_tol):
+    """The figure of merit of pplib.fit_wavelet_smooth_function from one
+    (signal, noise, red_chi2) triple: minus the pseudo-S/N, 0 where the
+    reduced chi^2 is further than rchi2_tol from 1."""
+    signal, noise, red_chi2 = score
+    if signal:
+        snr = signal / noise if noise else np.inf
+    else:
+        snr = 0.0
+    if abs(red_chi2 - 1.0) > rchi2_tol:
+        snr = 0.0
+    return -snr
+
+
+def grid_cases(nprof, nlevel, soft, grid):
+    """The case list and factors of the grid table of search(): (profile,
+    level, soft) x grid, the grid fastest."""
+    cases = [(ip, lev, soft) for ip in range(nprof)
+             for lev in range(1, nlevel + 1) for _ in range(len(grid))]
+    return cases, np.tile(np.asarray(grid, dtype=np.float64), nprof * nlevel)
+
+
 class _Handle(object):
     pass
 
@@ -173,6 +269,27 @@ class NumpyEvaluator(object):
             if smooth:
                 rows[ic] = s
         return out, rows
+
+    def search(self, h, soft, rchi2_tol, grid):
+        grid = np.asarray(grid, dtype=np.float64)
+        nprof, nlevel = len(h.profs), h.nlevel
+        table = self.score(h, *grid_cases(nprof, nlevel, soft, grid))[0]
+        table = table.reshape(nprof, nlevel, len(grid), 3)
+        fact_min = np.zeros((nprof, nlevel))
+        fun_min = np.zeros((nprof, nlevel))
+        nfev = np.zeros((nprof, nlevel), dtype=np.int32)
+        for ip in range(nprof):
+            for il in range(nlevel):
+                J = np.array([wavelet_snr(t, rchi2_tol)
+                              for t in table[ip, il]])
+
+                def func(x, ip=ip, lev=il + 1):
+                    return wavelet_snr(
+                        self.score(h, [(ip, lev, soft)], [x])[0][0], rchi2_tol)
+
+                fact_min[ip, il], fun_min[ip, il], nfev[ip, il] = \
+                    fmin_1d(func, grid[np.argmin(J)])
+        return fact_min, fun_min, nfev
 
 
 def default_evaluator():

@@ -2111,6 +2111,48 @@ int ppf_swt_score_batch(ppf_ctx *ctx, int32_t nprof, int32_t nbin, int32_t nleve
     return PPF_OK;
 }
 
+int ppf_swt_search_batch(ppf_ctx *ctx, int32_t nprof, int32_t nbin, int32_t nlevel, const double *prof,
+                         const double *medians, const double *noise, int32_t soft, double rchi2_tol,
+                         int32_t ngrid, const double *grid, const double *table, double *fact_min,
+                         double *fun_min, int32_t *nfev, void *workspace, size_t workspace_bytes,
+                         void *stream) {
+    SwtLayout L;
+    // the grid takes the factor slot of a score call of ngrid cases
+    int rc = swt_shape(nprof, nbin, nlevel, ngrid, L);
+    if (rc) return swt_fail(ctx, rc, nbin, nlevel);
+    if ((int64_t)nprof * nlevel > 0x7fffffffLL) return swt_fail(ctx, PPF_EUNSUP, nbin, nlevel);   // one workgroup each
+    if (ngrid < 1) return fail(ctx, PPF_EINVAL, "swt search: ngrid = %d", ngrid);
+    if (soft != 0 && soft != 1) return fail(ctx, PPF_EINVAL, "swt search: threshold type %d", soft);
+    if (!std::isfinite(rchi2_tol)) return fail(ctx, PPF_EINVAL, "swt search: rchi2_tol %g", rchi2_tol);
+    if (!grid || (nprof > 0 && (!prof || !medians || !noise || !table || !fact_min || !fun_min || !nfev)))
+        return fail(ctx, PPF_EINVAL, "null swt argument");
+    for (int g = 0; g < ngrid; ++g)
+        if (!std::isfinite(grid[g])) return fail(ctx, PPF_EINVAL, "swt search: grid[%d] = %g", g, grid[g]);
+    if (nprof > 0 && (!workspace || workspace_bytes < L.bytes))
+        return fail(ctx, PPF_EINVAL, "workspace: %zu bytes given, %zu needed", workspace_bytes, L.bytes);
+    if (!ctx) return PPF_EINVAL;
+    if (nprof == 0) return PPF_OK;
+    hipError_t e = hipSetDevice(ctx->device);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
+    hipStream_t st = (hipStream_t)stream;
+    ppf::SwtArgs a{};
+    if ((rc = twiddles(ctx, nbin, st, &a.T, &a.T2))) return rc;
+    char *ws = (char *)workspace;
+    if ((e = hipMemcpyAsync(ws + L.fact, grid, sizeof(double) * (size_t)ngrid, hipMemcpyHostToDevice, st)) !=
+        hipSuccess)
+        return hip_fail(ctx, e, "hipMemcpyAsync(grid)");
+    a.nprof = nprof; a.nbin = nbin; a.nlevel = nlevel; a.kc = noise_kc(nbin / 2 + 1, 4);
+    a.pow2 = (nbin & (nbin - 1)) == 0;
+    a.sq2ln = std::sqrt(2.0 * std::log((double)nbin));
+    a.prof = prof; a.coef = (double *)(ws + L.coef);
+    a.med = const_cast<double *>(medians); a.noise = const_cast<double *>(noise);
+    a.ngrid = ngrid; a.soft = soft; a.rchi2_tol = rchi2_tol;
+    a.grid = (const double *)(ws + L.fact); a.table = table;
+    a.fact_min = fact_min; a.fun_min = fun_min; a.nfev = nfev;
+    if ((e = ppf::launch_swt_search(a, st)) != hipSuccess) return hip_fail(ctx, e, "k_swt_search");
+    return PPF_OK;
+}
+
 int ppf_spline_portrait_batch(ppf_ctx *ctx, int32_t nport, int32_t nchan, int32_t nbin_model,
                               int32_t nbin, int32_t ncomp, int32_t nknots, int32_t degree,
                               const double *mean_prof, const double *eigvec, const double *knots,

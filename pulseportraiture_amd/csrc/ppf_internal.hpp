@@ -512,9 +512,17 @@ struct SwtArgs {
     double *out;                 // [ncase][3]: signal, noise, red_chi2
     double *smooth;              // [ncase][nbin] or null
     const double2 *T, *T2;
+    // k_swt_search only
+    int ngrid, soft;
+    double rchi2_tol;
+    const double *grid;          // [ngrid] (device copy)
+    const double *table;         // [nprof][nlevel][ngrid][3]: k_swt_score's out at the grid points
+    double *fact_min, *fun_min;  // [nprof][nlevel]
+    int32_t *nfev;               // [nprof][nlevel]
 };
 hipError_t launch_swt_analyse(const SwtArgs &a, hipStream_t st);
 hipError_t launch_swt_score(const SwtArgs &a, hipStream_t st);
+hipError_t launch_swt_search(const SwtArgs &a, hipStream_t st);
 
 // pplib.gen_spline_portrait (pplib.py:966-990): per (portrait, channel) row,
 // splev of the B-spline curve tck at the channel frequency (FITPACK splev /

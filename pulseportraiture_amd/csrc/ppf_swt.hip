@@ -22,6 +22,11 @@
 //                  global memory, the residual chi^2 against the profile,
 //                  then the row's rfft in place: sum_{k >= 1} |S_k|^2 and the
 //                  top-quarter noise.
+//   k_swt_search   one workgroup per (profile, level): the fmin finish of
+//                  scipy.optimize.brute over the factor, a two-point
+//                  Nelder-Mead whose every evaluation is the body of
+//                  k_swt_score (swt_score_case), started from the best point
+//                  of a grid that one k_swt_score launch has scored.
 // No atomics anywhere: every sum has a fixed order, results are bitwise
 // reproducible.
 #include <hip/hip_runtime.h>
@@ -162,17 +167,18 @@ __global__ __launch_bounds__(kBlock) void k_swt_analyse(SwtArgs a) {
     }
 }
 
+// One denoise-and-score case, the body k_swt_score and k_swt_search share:
+// profile p, level L, threshold factor fact.  lds0 is the two rows of nbin
+// doubles, red kWaves * 2 doubles; sm receives the smoothed row when not
+// null.  s = (signal, noise, red_chi2) comes back identical in every thread
+// (block_sum's broadcast).  Ends on block_sum's barrier: the LDS rows are
+// free again on return.
 template <bool MX>
-__global__ __launch_bounds__(kBlock) void k_swt_score(SwtArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double2 lds[];
-    __shared__ double red[kWaves * 2];
+__device__ __forceinline__ void swt_score_case(const SwtArgs &a, int64_t p, int L, bool soft, double fact,
+                                               double *lds0, double *red, double *sm, double (&s)[3]) {
     const int n = a.nbin, N = n >> 1, nl = a.nlevel;
-    const int64_t c = blockIdx.x;
-    const int64_t p = a.cases[3 * c];
-    const int L = a.cases[3 * c + 1];
-    const bool soft = a.cases[3 * c + 2] != 0;
-    const double lam = a.fact[c] * (a.med[p * nl + (L - 1)] / 0.6745) * a.sq2ln;
-    double *A = reinterpret_cast<double *>(lds), *B = A + n;
+    const double lam = fact * (a.med[p * nl + (L - 1)] / 0.6745) * a.sq2ln;
+    double *A = lds0, *B = A + n;
     const double *cp = a.coef + p * nl * 2 * n;
     {
         const double *aL = cp + (int64_t)(L - 1) * 2 * n;
@@ -180,13 +186,13 @@ __global__ __launch_bounds__(kBlock) void k_swt_score(SwtArgs a) {
     }
     __syncthreads();
     for (int j = L; j >= 1; --j) {
-        const int s = 1 << (j - 1);
+        const int st = 1 << (j - 1);
         const double *dj = cp + ((int64_t)(j - 1) * 2 + 1) * n;
         for (int i = threadIdx.x; i < n; i += kBlock) {
             double lo = 0.0, hi = 0.0;
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
-                const int q = swt_wrap(i, k * s, n, a.pow2);
+                const int q = swt_wrap(i, k * st, n, a.pow2);
                 lo = fma(swt_lo(k), A[q], lo);
                 hi = fma(swt_hi(k), swt_thresh(dj[q], lam, soft), hi);
             }
@@ -200,7 +206,6 @@ __global__ __launch_bounds__(kBlock) void k_swt_score(SwtArgs a) {
     // A: the smoothed row
     const double *x = a.prof + p * n;
     const double sig_x = a.noise[p];
-    double *sm = a.smooth ? a.smooth + c * n : nullptr;
     double chi[1] = {0.0};
     for (int i = threadIdx.x; i < n; i += kBlock) {
         const double sv = A[i], r = (x[i] - sv) / sig_x;
@@ -217,11 +222,165 @@ __global__ __launch_bounds__(kBlock) void k_swt_score(SwtArgs a) {
         if (k >= a.kc) acc[1] += pw;
     }
     block_sum<2>(acc, red);
+    s[0] = acc[0];
+    s[1] = sqrt(acc[1] / (double)n / (double)(N + 1 - a.kc)) * sqrt((double)n / 2.0);
+    s[2] = chi[0] / (double)n;
+}
+
+template <bool MX>
+__global__ __launch_bounds__(kBlock) void k_swt_score(SwtArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double2 lds[];
+    __shared__ double red[kWaves * 2];
+    const int64_t c = blockIdx.x;
+    const int64_t p = a.cases[3 * c];
+    const int L = a.cases[3 * c + 1];
+    const bool soft = a.cases[3 * c + 2] != 0;
+    double s[3];
+    swt_score_case<MX>(a, p, L, soft, a.fact[c], reinterpret_cast<double *>(lds), red,
+                       a.smooth ? a.smooth + c * a.nbin : nullptr, s);
     if (threadIdx.x == 0) {
         double *o = a.out + c * 3;
-        o[0] = acc[0];
-        o[1] = sqrt(acc[1] / (double)n / (double)(N + 1 - a.kc)) * sqrt((double)n / 2.0);
-        o[2] = chi[0] / (double)n;
+        o[0] = s[0];
+        o[1] = s[1];
+        o[2] = s[2];
+    }
+}
+
+// pplib._wavelet_snr of one (signal, noise, red_chi2) triple, IEEE comparisons
+__device__ __forceinline__ double swt_objective(const double (&s)[3], double rchi2_tol) {
+    double snr = 0.0;
+    if (s[0] != 0.0) snr = s[1] != 0.0 ? s[0] / s[1] : __builtin_huge_val();
+    if (fabs(s[2] - 1.0) > rchi2_tol) snr = 0.0;
+    return -snr;
+}
+
+// c * u, c1 * u - c2 * v and u + c * (v - u) as NumPy rounds them: every
+// product and difference rounded on its own (a contracted fma gives another
+// factor).  The library is built with -ffp-contract=fast, which no pragma
+// overrides; a value passed through swt_rounded is opaque to the compiler,
+// so the operation that made it cannot fuse with the one that uses it.
+__device__ __forceinline__ double swt_rounded(double v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+__device__ __forceinline__ double swt_mul(double c, double u) { return swt_rounded(c * u); }
+__device__ __forceinline__ double swt_lin(double c1, double u, double c2, double v) {
+    const double a1 = swt_rounded(c1 * u), a2 = swt_rounded(c2 * v);
+    return swt_rounded(a1 - a2);
+}
+__device__ __forceinline__ double swt_toward(double u, double c, double v) {
+    const double d = swt_rounded(v - u);
+    const double h = swt_rounded(c * d);
+    return swt_rounded(u + h);
+}
+
+// The fmin finish of scipy.optimize.brute for one (profile, level): the 1-D
+// Nelder-Mead of scipy's _minimize_neldermead (xatol = fatol = 1e-4, at most
+// 200 calls) from the first grid point of minimal objective, as a state
+// machine around ONE evaluation site: the barriers of swt_score_case stand
+// in the loop body alone, and every thread takes every branch from values
+// block_sum gave all of them.  (s0, f0) is the better point, (s1, f1) the
+// other.
+enum { kSwtInit0, kSwtInit1, kSwtReflect, kSwtExpand, kSwtContract, kSwtInside, kSwtShrink };
+constexpr int kSwtMaxCalls = 200;
+constexpr double kSwtTol = 1e-4;
+
+template <bool MX>
+__global__ __launch_bounds__(kBlock) void k_swt_search(SwtArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double2 lds[];
+    __shared__ double red[kWaves * 2];
+    const int nl = a.nlevel;
+    const int64_t pl = blockIdx.x;
+    const int64_t p = pl / nl;
+    const int L = (int)(pl % nl) + 1;
+    const bool soft = a.soft != 0;
+    // np.argmin over the grid's objectives: the first minimum, a NaN first
+    const double *tab = a.table + pl * a.ngrid * 3;
+    int g0 = 0;
+    double best = 0.0;
+    for (int g = 0; g < a.ngrid; ++g) {
+        const double sc[3] = {tab[3 * g], tab[3 * g + 1], tab[3 * g + 2]};
+        const double f = swt_objective(sc, a.rchi2_tol);
+        if (g == 0 || f < best || (f != f && best == best)) {
+            best = f;
+            g0 = g;
+        }
+    }
+    const double x0 = a.grid[g0];
+    double s0 = x0, s1 = x0 != 0.0 ? swt_mul(1.0 + 0.05, x0) : 0.00025;
+    double f0 = __builtin_huge_val(), f1 = f0, xr = 0.0, fxr = 0.0, x = s0;
+    int calls = 0, st = kSwtInit0;
+    while (calls < kSwtMaxCalls) {            // call 201 is not made: the step in progress is abandoned
+        double sc[3];
+        swt_score_case<MX>(a, p, L, soft, x, reinterpret_cast<double *>(lds), red, nullptr, sc);
+        const double fx = swt_objective(sc, a.rchi2_tol);
+        ++calls;
+        bool stepped = false, shrink = false;
+        if (st == kSwtInit0) {
+            f0 = fx;
+            x = s1;
+            st = kSwtInit1;
+        } else if (st == kSwtInit1 || st == kSwtShrink) {
+            f1 = fx;
+            stepped = true;
+        } else if (st == kSwtReflect) {
+            xr = x;
+            fxr = fx;
+            if (fxr < f0) {
+                x = swt_lin(3.0, s0, 2.0, s1);
+                st = kSwtExpand;
+            } else if (fxr < f1) {
+                x = swt_lin(1.5, s0, 0.5, s1);
+                st = kSwtContract;
+            } else {
+                x = swt_lin(0.5, s0, -0.5, s1);   // 0.5 s0 + 0.5 s1
+                st = kSwtInside;
+            }
+        } else if (st == kSwtExpand) {
+            if (fx < fxr) {
+                s1 = x;
+                f1 = fx;
+            } else {
+                s1 = xr;
+                f1 = fxr;
+            }
+            stepped = true;
+        } else if (st == kSwtContract) {
+            if (fx <= fxr) {
+                s1 = x;
+                f1 = fx;
+                stepped = true;
+            } else {
+                shrink = true;
+            }
+        } else {                              // kSwtInside
+            if (fx < f1) {
+                s1 = x;
+                f1 = fx;
+                stepped = true;
+            } else {
+                shrink = true;
+            }
+        }
+        if (shrink) {
+            s1 = swt_toward(s0, 0.5, s1);     // assigned before its evaluation, as scipy does
+            x = s1;
+            st = kSwtShrink;
+        }
+        if (stepped) {
+            if (f1 < f0) {
+                double t = s0; s0 = s1; s1 = t;
+                t = f0; f0 = f1; f1 = t;
+            }
+            if (fabs(s1 - s0) <= kSwtTol && fabs(f0 - f1) <= kSwtTol) break;
+            x = swt_lin(2.0, s0, 1.0, s1);
+            st = kSwtReflect;
+        }
+    }
+    if (threadIdx.x == 0) {
+        a.fact_min[pl] = s0;
+        a.fun_min[pl] = f1 < f0 ? f1 : f0;
+        a.nfev[pl] = calls;
     }
 }
 
@@ -248,6 +407,13 @@ hipError_t launch_swt_score(const SwtArgs &a, hipStream_t st) {
     const size_t lds = (size_t)a.nbin * 2 * sizeof(double);
     if (is_pow2(a.nbin / 2)) return swt_launch(k_swt_score<false>, (unsigned)a.ncase, lds, st, a);
     return swt_launch(k_swt_score<true>, (unsigned)a.ncase, lds, st, a);
+}
+
+hipError_t launch_swt_search(const SwtArgs &a, hipStream_t st) {
+    const size_t lds = (size_t)a.nbin * 2 * sizeof(double);
+    const unsigned grid = (unsigned)((int64_t)a.nprof * a.nlevel);
+    if (is_pow2(a.nbin / 2)) return swt_launch(k_swt_search<false>, grid, lds, st, a);
+    return swt_launch(k_swt_search<true>, grid, lds, st, a);
 }
 
 }  // namespace ppf

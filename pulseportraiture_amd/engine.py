@@ -1427,11 +1427,24 @@ def swt_analyse(profs, nlevel, max_ncase=0, dev=None):
     return h
 
 
-def swt_score(h, cases, facts, smooth=False):
+def _swt_grow(h, ncase):
+    """Room for ncase cases in the handle's workspace: the coefficients sit
+    at its front, a longer case list needs a larger one and the rows are
+    copied over."""
+    if ncase > h.ncase:
+        lib = _lib.load()
+        need = lib.ppf_swt_workspace_bytes(h.nprof, h.nbin, h.nlevel, ncase)
+        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=h.dev)
+        ncoef = h.nprof * h.nlevel * 2 * h.nbin * 8
+        ws[:ncoef].copy_(h.ws[:ncoef])
+        h.ws, h.ncase = ws, ncase
+
+
+def swt_score(h, cases, facts, smooth=False, on_device=False):
     """Denoise-and-score cases on an analysed batch (ppf_swt_score_batch):
     cases [ncase, 3] = (profile, level, 0 hard / 1 soft), facts [ncase] ->
     (out [ncase, 3] = (signal, noise, red_chi2), the smoothed rows [ncase,
-    nbin] or None), NumPy."""
+    nbin] or None), NumPy, or with on_device the device tensors."""
     cs = np.ascontiguousarray(cases, dtype=np.int32).reshape(-1, 3)
     fs = np.ascontiguousarray(facts, dtype=np.float64).reshape(-1)
     ncase = len(cs)
@@ -1439,14 +1452,7 @@ def swt_score(h, cases, facts, smooth=False):
         raise ValueError("one factor per case")
     lib = _lib.load()
     dev = h.dev
-    if ncase > h.ncase:
-        # the coefficients sit at the front of the workspace: a longer case
-        # list needs a larger one, the rows are copied over
-        need = lib.ppf_swt_workspace_bytes(h.nprof, h.nbin, h.nlevel, ncase)
-        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        ncoef = h.nprof * h.nlevel * 2 * h.nbin * 8
-        ws[:ncoef].copy_(h.ws[:ncoef])
-        h.ws, h.ncase = ws, ncase
+    _swt_grow(h, ncase)
     out = torch.empty((ncase, 3), dtype=torch.float64, device=dev)
     rows = torch.empty((ncase, h.nbin), dtype=torch.float64, device=dev) \
         if smooth else None
@@ -1458,7 +1464,40 @@ def swt_score(h, cases, facts, smooth=False):
     _lib.check(rc, ctx)
     # cases / facts are host arrays the stream still reads
     torch.cuda.current_stream(dev).synchronize()
+    if on_device:
+        return out, rows
     return out.cpu().numpy(), (rows.cpu().numpy() if smooth else None)
+
+
+def swt_search(h, soft, rchi2_tol, grid, table):
+    """The fmin finish of scipy.optimize.brute for every (profile, level) of
+    an analysed batch in one launch (ppf_swt_search_batch): grid [ngrid]
+    the factors brute tabulates, table the device out of the swt_score call
+    over _swt.grid_cases -> fact_min, fun_min (float64), nfev (int32), each
+    [nprof, nlevel], NumPy, from one download."""
+    gs = np.ascontiguousarray(grid, dtype=np.float64).reshape(-1)
+    lib = _lib.load()
+    dev = h.dev
+    m = h.nprof * h.nlevel
+    if table.shape != (m * len(gs), 3) or table.dtype != torch.float64 or \
+            not table.is_contiguous():
+        raise ValueError("table: the [nprof * nlevel * ngrid, 3] float64 out "
+                         "of swt_score over the grid")
+    _swt_grow(h, len(gs))
+    # fact_min, fun_min and (two int32 to a double) nfev, one buffer
+    res = torch.empty(2 * m + (m + 1) // 2, dtype=torch.float64, device=dev)
+    ctx = _lib.context(dev.index)
+    rc = lib.ppf_swt_search_batch(
+        ctx, h.nprof, h.nbin, h.nlevel, _p(h.prof), _p(h.med), _p(h.sig),
+        int(soft), float(rchi2_tol), len(gs), gs.ctypes.data, _p(table),
+        _p(res[:m]), _p(res[m:2 * m]), _p(res[2 * m:]), _p(h.ws),
+        h.ws.numel(), _stream(dev))
+    _lib.check(rc, ctx)
+    # the download waits for the stream, which still reads the host grid
+    r = res.cpu().numpy()
+    shape = (h.nprof, h.nlevel)
+    return (r[:m].reshape(shape), r[m:2 * m].reshape(shape),
+            r[2 * m:].view(np.int32)[:m].reshape(shape))
 
 
 class SwtEvaluator(object):
@@ -1477,6 +1516,12 @@ class SwtEvaluator(object):
 
     def score(self, h, cases, facts, smooth=False):
         return swt_score(h, cases, facts, smooth)
+
+    def search(self, h, soft, rchi2_tol, grid):
+        from . import _swt
+        cases, facts = _swt.grid_cases(h.nprof, h.nlevel, soft, grid)
+        table = swt_score(h, cases, facts, on_device=True)[0]
+        return swt_search(h, soft, rchi2_tol, grid, table)
 
 
 def spline_portraits(mean_prof, eigvec, tck, freqs, nbin=None, dev=None):

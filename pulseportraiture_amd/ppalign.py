@@ -31,10 +31,98 @@ import torch
 from . import _lib, engine
 from . import pptoas as _pptoas
 from .pplib import (DataBunch, Dconst, file_is_type, fit_phase_shift,
-                    gaussian_profile, get_noise, guess_fit_freq, rotate_data,
+                    gaussian_profile, get_noise, guess_fit_freq,
+                    make_constant_portrait, rotate_data, smart_smooth,
                     unload_new_archive)
 
 rm_baseline = _pptoas.rm_baseline       # ppalign.py imports it from pptoas
+
+
+def _names(metafile):
+    with open(metafile, "r") as fh:
+        return [line.strip() for line in fh if line.strip()]
+
+
+def psradd_archives(metafile, outfile, palign=False):
+    """ppalign.py:30-47 without psradd: the channel-weight-weighted mean of
+    the metafile's archives, written to outfile as an initial guess for
+    align_archives.  Each archive is loaded tscrunched and not dedispersed,
+    as total intensity or (the first file has four polarisations) as Stokes;
+    a file of another shape is reported and skipped.  The mean is one
+    engine.align_accum call.  palign=True first rotates each archive
+    achromatically by fit_phase_shift(prof_i, prof_0, Ns=nbin).phase, the
+    profiles those of the dedispersed loads, every phase from one
+    engine.phase_shift_batch call.  The file carries the first archive's
+    metadata and DM (dispersed) and the summed channel weights.  psradd
+    aligns by the archives' predictors; no predictor alignment is done
+    here."""
+    from . import psrfits
+    names = _names(metafile)
+    pol = psrfits.archive_meta(names[0])["npol"] == 4
+    kw = dict(state="Stokes", pscrunch=False) if pol else dict(pscrunch=True)
+    first, rows, wts, profs = None, [], [], []
+    for name in names:
+        try:
+            d = _pptoas.load_data(name, tscrunch=True, quiet=True, **kw)
+        except (RuntimeError, IndexError, NotImplementedError) as exc:
+            print("%s: cannot be loaded (%s).  Skipping it." % (name, exc))
+            continue
+        if first is not None and (d.nchan, d.nbin) != (first.nchan,
+                                                       first.nbin):
+            print("%s: %d x %d, not %d x %d channels x bins.  Skipping it." %
+                  (name, d.nchan, d.nbin, first.nchan, first.nbin))
+            continue
+        if first is None:
+            first = d
+        rows.append(np.asarray(d.subints)[0])
+        wts.append(np.asarray(d.weights, dtype=np.float64)[0])
+        if palign:
+            profs.append(_pptoas.load_data(name, dedisperse=True,
+                                           tscrunch=True, pscrunch=True,
+                                           quiet=True).prof)
+    npol, nchan, nbin = rows[0].shape
+    dev = engine.device(None)
+    phases = np.zeros(len(rows))
+    if palign:
+        phases = engine.phase_shift_batch(
+            np.array(profs), profs[0], Ns=nbin, dev=dev)[:, 0].cpu().numpy()
+    # the polarisations ride on the channel axis: one call
+    out = torch.zeros((npol * nchan, nbin), dtype=torch.float64, device=dev)
+    wsum = torch.zeros(npol * nchan, dtype=torch.float64, device=dev)
+    engine.align_accum(
+        np.array(rows).reshape(len(rows), npol * nchan, nbin),
+        np.repeat(phases[:, None], npol * nchan, axis=1),
+        np.tile(np.array(wts), (1, npol)), out, wsum, dev=dev)
+    out /= torch.where(wsum > 0, wsum, 1.0)[:, None]
+    unload_new_archive(out.reshape(1, npol, nchan, nbin), first, outfile,
+                       DM=first.DM, weights=wsum[:nchan].cpu().numpy()[None],
+                       quiet=True, dev=dev)
+    return phases
+
+
+def psrsmooth_archive(archive, options="-W"):
+    """ppalign.py:50-62 without psrsmooth: archive + ".sm" is the archive
+    with every profile as stored (no baseline removed), every polarisation,
+    through pplib.smart_smooth(search="batched"), at most eight levels.
+    This is this project's stationary db8 transform and search, not
+    psrsmooth's wavelet code; "-W" (what ppalign -s passes) is the only
+    option taken.  The source's metadata, DM and weights are kept; a channel
+    whose total-intensity (first polarisation) row came back zero, the
+    smoother's verdict that nothing passes its chi^2 gate, gets weight 0."""
+    if options.strip() != "-W":
+        raise NotImplementedError("psrsmooth options %r: only '-W'"
+                                  % (options,))
+    d = _pptoas.load_data(archive, rm_baseline=False, quiet=True)
+    x = np.asarray(d.subints).astype(np.float64)
+    nsub, npol, nchan, nbin = x.shape
+    sm = smart_smooth(x.reshape(-1, nbin), search="batched",
+                      try_nlevels=min(8, int(np.log2(nbin))))
+    sm = np.asarray(sm).reshape(x.shape)
+    weights = np.array(d.weights, dtype=np.float64)
+    weights[~sm[:, 0].any(axis=-1)] = 0.0
+    outfile = archive + ".sm"
+    unload_new_archive(sm, archive, outfile, weights=weights, quiet=True)
+    return outfile
 
 
 def normalize_portrait(port, method="rms", weights=None, return_norms=False):
@@ -536,3 +624,123 @@ def align_archives(metafile, initial_guess, fit_dm=True, tscrunch=False,
             quiet=quiet, dev=dev)
     return DataBunch(port=aligned_port, total_weights=total_weights,
                      nsub_fit=R.n)
+
+
+def main(argv=None):
+    """ppalign.py's command line (ppalign.py:283-420).  The initial guess:
+    -I's archive; without it the plain average of psradd_archives; with -g a
+    constant portrait of one Gaussian component.  A one-channel -I stands
+    for "a constant portrait of the first archive's average profile".  The
+    temporary template is written beside the output file and removed."""
+    from optparse import OptionParser
+    from . import psrfits
+    parser = OptionParser("Usage: %prog -M <metafile> [options]")
+    parser.add_option("-M", "--metafile", action="store", metavar="metafile",
+                      dest="metafile", default=None,
+                      help="Metafile of archives to average together.")
+    parser.add_option("-I", "--init", action="store",
+                      metavar="initial_guess", dest="initial_guess",
+                      default=None,
+                      help="Archive containing initial alignment guess.  The "
+                      "plain weighted average is used if -I is not used.")
+    parser.add_option("-g", "--width", action="store", metavar="fwhm",
+                      dest="fwhm", default=None,
+                      help="Use a single Gaussian component of given FWHM to "
+                      "align archives.  Overides -I.")
+    parser.add_option("-D", "--no_DM", action="store_false", dest="fit_dm",
+                      default=True,
+                      help="Align the subintegrations/archives with a fit "
+                      "for phase only.")
+    parser.add_option("-T", "--tscr", action="store_true", dest="tscrunch",
+                      default=False,
+                      help="Tscrunch archives for the iterations.")
+    parser.add_option("-p", "--poln", action="store_false", dest="pscrunch",
+                      default=True,
+                      help="Output average Stokes portraits, not just total "
+                      "intensity.")
+    parser.add_option("-C", "--cutoff", action="store", metavar="SNR_cutoff",
+                      dest="SNR_cutoff", default=0.0,
+                      help="S/N ratio cutoff to apply to input archives. "
+                      "[default=0.0]")
+    parser.add_option("-o", "--outfile", action="store", metavar="outfile",
+                      dest="outfile", default=None,
+                      help="Name of averaged output archive. "
+                      "[default=metafile.algnd.fits]")
+    parser.add_option("-P", "--palign", action="store_true", dest="palign",
+                      default=False,
+                      help="Phase-align the archives of the initial average "
+                      "if -I is not used. [default=False]")
+    parser.add_option("-N", "--norm", action="store",
+                      metavar="normalization", dest="norm", default=None,
+                      help="Normalize the final averaged data by channel "
+                      "('None' [default], 'mean', 'max', 'prof', 'rms', or "
+                      "'abs').")
+    parser.add_option("-s", "--smooth", action="store_true", dest="smooth",
+                      default=False,
+                      help="Output a second averaged archive, smoothed with "
+                      "smart_smooth. [default=False]")
+    parser.add_option("-r", "--rot", action="store", metavar="phase",
+                      dest="rot_phase", default=0.0,
+                      help="Additional rotation to add to averaged archive. "
+                      "[default=0.0]")
+    parser.add_option("--place", action="store", metavar="place",
+                      dest="place", default=None,
+                      help="Roughly place pulse to be at the phase given.  "
+                      "Overrides --rot. [default=None]")
+    parser.add_option("--niter", action="store", metavar="int", dest="niter",
+                      default=1,
+                      help="Number of iterations to complete. [default=1]")
+    parser.add_option("--verbose", action="store_false", dest="quiet",
+                      default=True, help="More to stdout.")
+    options, _ = parser.parse_args(argv)
+    if options.metafile is None or not int(options.niter):
+        print("\nppalign.py - Aligns and averages homogeneous archives by "
+              "fitting DMs and phases\n")
+        parser.print_help()
+        print("")
+        parser.exit()
+    metafile, quiet = options.metafile, options.quiet
+    outfile = options.outfile
+    if outfile is None:
+        outfile = metafile + ".algnd.fits"
+    rot_phase, place = np.float64(options.rot_phase), None
+    if options.place is not None:
+        rot_phase, place = 0.0, np.float64(options.place)
+    initial_guess, tmp_file = options.initial_guess, None
+    new_tmp = os.path.join(
+        os.path.dirname(os.path.abspath(outfile)),
+        "ppalign.%d.tmp.fits" % np.random.randint(100, 1000))
+    try:
+        if initial_guess is None and options.fwhm is None:
+            tmp_file = new_tmp
+            psradd_archives(metafile, outfile=tmp_file, palign=options.palign)
+        elif options.fwhm:
+            tmp_file = new_tmp
+            archive = _names(metafile)[0]
+            nbin = psrfits.archive_meta(archive)["nbin"]
+            make_constant_portrait(
+                archive, tmp_file,
+                profile=gaussian_profile(nbin, 0.5, float(options.fwhm)),
+                DM=0.0, dmc=False, weights=None, quiet=quiet)
+        elif psrfits.archive_meta(initial_guess)["nchan"] == 1:
+            tmp_file = new_tmp
+            make_constant_portrait(_names(metafile)[0], tmp_file,
+                                   profile=None, DM=0.0, dmc=False,
+                                   weights=None, quiet=quiet)
+        if tmp_file is not None:
+            initial_guess = tmp_file
+        align_archives(metafile, initial_guess=initial_guess,
+                       fit_dm=options.fit_dm, tscrunch=options.tscrunch,
+                       pscrunch=options.pscrunch,
+                       SNR_cutoff=float(options.SNR_cutoff), outfile=outfile,
+                       norm=options.norm, rot_phase=rot_phase, place=place,
+                       niter=int(options.niter), quiet=quiet)
+        if options.smooth:
+            psrsmooth_archive(outfile, options="-W")
+    finally:
+        if tmp_file is not None and os.path.exists(tmp_file):
+            os.remove(tmp_file)
+
+
+if __name__ == "__main__":
+    main()

@@ -1068,14 +1068,8 @@ def wavelet_smooth(port, wavelet="db8", nlevel=5, threshtype="hard", fact=1.0,
 def _wavelet_snr(score, rchi2_tol):
     """The figure of merit of fit_wavelet_smooth_function from one
     (signal, noise, red_chi2) triple."""
-    signal, noise, red_chi2 = score
-    if signal:
-        snr = signal / noise if noise else np.inf
-    else:
-        snr = 0.0
-    if abs(red_chi2 - 1.0) > rchi2_tol:
-        snr = 0.0
-    return -snr
+    from . import _swt
+    return _swt.wavelet_snr(score, rchi2_tol)
 
 
 def fit_wavelet_smooth_function(fact, prof, wavelet, nlevel, threshtype,
@@ -1106,9 +1100,17 @@ def smart_smooth(port, try_nlevels=None, rchi2_tol=0.1, **kwargs):
     single profile as a [1, nbin] array, as the reference has it) and
     all-zero rows return as in the reference; a length that is not a power
     of two tries one level.  kwargs: threshtype, wavelet ('db8' only) and evaluator (not
-    in the reference: replaces the device evaluator, see _swt)."""
+    in the reference: replaces the device evaluator, see _swt).
+    search (not in the reference) = "brute" is the above; "batched" gives
+    the same result from at most four evaluator calls whatever the number
+    of rows: analyse, ev.search (the grid table and every (profile, level)'s
+    fmin finish, on the device one workgroup each, k_swt_search), and one
+    smoothing call for all rows at their best (level, fact)."""
     import scipy.optimize as opt
     from . import _swt
+    search = kwargs.get("search", "brute")
+    if search not in ("brute", "batched"):
+        raise ValueError("search must be 'brute' or 'batched'")
     if try_nlevels == 0:
         return port
     port = np.asarray(port, dtype=np.float64)
@@ -1137,6 +1139,16 @@ def smart_smooth(port, try_nlevels=None, rchi2_tol=0.1, **kwargs):
     grid = np.mgrid[slice(0.0, 3.0, complex(Ns))]
     ncase = len(todo) * try_nlevels * Ns
     h = ev.analyse(rows[todo], try_nlevels, ncase)
+    if search == "batched":
+        fact_mins, fun_vals, _ = ev.search(h, soft, rchi2_tol, grid)
+        levels = np.argmin(fun_vals, axis=1)
+        ips = np.arange(len(todo))
+        out, srows = ev.score(h, [(ip, lev + 1, soft)
+                                  for ip, lev in zip(ips, levels)],
+                              fact_mins[ips, levels], smooth=True)
+        keep = ~(np.abs(out[:, 2] - 1.0) > rchi2_tol)
+        smooth_port[np.asarray(todo)[keep]] = srows[keep]
+        return smooth_port[0] if one_prof else smooth_port
     cases = [(ip, lev, soft) for ip in range(len(todo))
              for lev in range(1, try_nlevels + 1) for _ in range(Ns)]
     table = ev.score(h, cases, np.tile(grid, len(todo) * try_nlevels))[0]
@@ -1439,6 +1451,30 @@ def unload_new_archive(data, arch, outfile, DM=None, dmc=0, weights=None,
         dev=dev, fd_poln=fd_poln)
     if not quiet:
         print("\nUnloaded %s.\n" % outfile)
+
+
+def make_constant_portrait(archive, outfile, profile=None, DM=0.0, dmc=False,
+                           weights=None, quiet=False):
+    """pplib.py:993-1029 without PSRCHIVE: outfile is the fold-mode PSRFITS
+    file archive with every (sub-int, polarisation, channel) holding
+    profile, header DM as given, unit weights unless weights [nsub, nchan]
+    is.  profile=None takes the archive's dedispersed, tscrunched total-
+    intensity mean profile (load_data's prof).  A profile of another length
+    than the archive's nbin raises AssertionError, as the reference does."""
+    from . import psrfits
+    m = psrfits.archive_meta(archive)
+    shape = tuple(int(m[k]) for k in ("nsub", "npol", "nchan", "nbin"))
+    if profile is None:
+        profile = load_data(archive, dedisperse=True, tscrunch=True,
+                            pscrunch=True, quiet=True).prof
+    assert len(profile) == shape[3], \
+        "len(profile) != number of bins in dummy archive"
+    if weights is None:
+        weights = np.ones((shape[0], shape[2]))
+    data = np.empty(shape)
+    data[:] = np.asarray(profile, dtype=np.float64)
+    unload_new_archive(data, archive, outfile, DM=DM, dmc=dmc,
+                       weights=weights, quiet=quiet)
 
 
 # ------------------------------------------------------------- TOA output --
@@ -1794,6 +1830,28 @@ class DataPortrait(object):
         self.unnorm_noise_stdsxs = np.copy(self.noise_stdsxs)
         self.portx = normalize_portrait(self.portx, method, weights=weightsx,
                                         return_norms=False)
+        self.noise_stdsxs = get_noise(self.portx, chans=True)
+        self.flux_profx = self.portx.mean(axis=1)
+
+    def smooth_portrait(self, smart=False, **kwargs):
+        """pplib.py:422-446: the full and the condensed portrait through
+        wavelet_smooth, or with smart through smart_smooth (at most eight
+        levels; search="batched" unless kwargs say otherwise: every
+        channel's search in one launch), the noise levels re-measured and
+        the flux profiles recomputed.  kwargs go to the smoother."""
+        def smooth(port):
+            if not smart:
+                return wavelet_smooth(port, **kwargs)
+            kw = dict(search="batched")
+            kw.update(kwargs)
+            return smart_smooth(
+                port, try_nlevels=min(8, int(np.log2(self.nbin))), **kw)
+
+        self.port = smooth(self.port)
+        self.noise_stds = np.array(self.noise_stds, dtype=float)
+        self.noise_stds[0, 0] = get_noise(self.port, chans=True)
+        self.flux_prof = self.port.mean(axis=1)
+        self.portx = smooth(self.portx)
         self.noise_stdsxs = get_noise(self.portx, chans=True)
         self.flux_profx = self.portx.mean(axis=1)
 

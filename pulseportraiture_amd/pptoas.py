@@ -477,6 +477,23 @@ class GetTOAs(object):
             model = None
         return md, model
 
+    def _drop_unweighted(self, d):
+        """Channels the archive template gives no weight hold no model (its
+        rows there are zero: ppalign's empty channels, the rows
+        psrsmooth_archive's smoother rejected): they leave the data's
+        ok_ichans and are not fitted, as get_narrowband_TOAs leaves them
+        out (pptoas.py:1041-1042).  The reference's wideband fit divides by
+        such a row's zero power.  Nothing changes where the data give those
+        channels no weight either."""
+        mw = np.asarray(self._archive_template()[0].weights)[0]
+        if len(mw) != d.nchan or (mw != 0).all():
+            return
+        for isub in d.ok_isubs:
+            oc = np.asarray(d.ok_ichans[isub], dtype=int)
+            keep = mw[oc] != 0
+            if not keep.all():
+                d.ok_ichans[isub] = oc[keep]
+
     def _archive_models(self, d, ok_isubs):
         """_base_models for an archive template (pptoas.py:358-377, 385-387):
         one portrait, index 0 for every sub-int, used as it is with fit_scat
@@ -899,6 +916,8 @@ class GetTOAs(object):
         except _SkipArchive:
             _sp.__exit__(None, None, None)
             return None
+        if getattr(self, "is_FITS_model", False):
+            self._drop_unweighted(d)
         models_ev = None
         if isinstance(models, torch.Tensor) and models.is_cuda:
             models_ev = torch.cuda.Event()
