@@ -1734,10 +1734,68 @@ int ppf_phase_shift_batch(ppf_ctx *ctx, int32_t nprof, int32_t nbin, int32_t in_
     return PPF_OK;
 }
 
-int ppf_gauss_portrait_batch(ppf_ctx *ctx, int32_t nport, int32_t nchan, int32_t nbin,
-                             int32_t ngauss, const char *model_code, const double *params,
-                             const double *scattering_index, const double *freqs,
-                             const double *nu_ref, double *out, void *stream) {
+namespace {
+// the three digits of a Gaussian model's evolution code into code[3]: PPF_OK
+// or the error set
+int parse_model_code(ppf_ctx *ctx, const char *model_code, int code[3]) {
+    if (!model_code) return fail(ctx, PPF_EINVAL, "model_code is NULL");
+    for (int i = 0; i < 3; ++i) {
+        const char c = model_code[i];
+        if (c != '0' && c != '1')   // evolve_parameter's KeyError (pplib.py:1082-1084)
+            return fail(ctx, PPF_EINVAL, "model_code '%.3s': digit %d must be '0' or '1'", model_code, i);
+        code[i] = c - '0';
+    }
+    return PPF_OK;
+}
+
+// the join arguments of the joined Gaussian entry points, checked on the
+// host: PPF_OK or the error set
+int check_join(ppf_ctx *ctx, int64_t nrow, int32_t njoin, const int32_t *join_id, const double *join_params,
+               const double *P) {
+    if (njoin < 0) return fail(ctx, PPF_EINVAL, "njoin=%d", njoin);
+    if (nrow > 0 && (!join_id || !P || (njoin > 0 && !join_params)))
+        return fail(ctx, PPF_EINVAL, "join_id / join_params / P is NULL");
+    for (int64_t i = 0; i < nrow; ++i)
+        if (join_id[i] < -1 || join_id[i] >= njoin)
+            return fail(ctx, PPF_EINVAL, "join_id[%lld] = %d: -1 or an archive in [0, %d)", (long long)i,
+                        join_id[i], njoin);
+    return PPF_OK;
+}
+
+// j.join_id: the device copy of join_id (nrow entries) in the context's
+// scratch.  The call is synchronous: the caller holds ctx->lscr_mu until its
+// stream is done.
+int join_id_to_scratch(ppf_ctx *ctx, const int32_t *join_id, int64_t nrow, hipStream_t st, ppf::GaussJoin &j) {
+    const size_t jb = sizeof(int32_t) * (size_t)nrow;
+    int rc;
+    if ((rc = lscr_reserve(ctx, align256(jb)))) return rc;
+    hipError_t e = hipMemcpyAsync(ctx->lscr, join_id, jb, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return hip_fail(ctx, e, "hipMemcpyAsync(join_id)");
+    j.join_id = (const int32_t *)ctx->lscr;
+    return PPF_OK;
+}
+
+// ppf_gauss_portrait_batch (jn == nullptr) and ppf_gauss_portrait_join_batch.
+// Each keeps its order of checks: the plain call looks at the context first,
+// the joined one after its own length, shape and join checks.
+int gauss_portrait_run(ppf_ctx *ctx, int32_t nport, int32_t nchan, int32_t nbin, int32_t ngauss,
+                       const char *model_code, const double *params, const double *scattering_index,
+                       const double *freqs, const double *nu_ref, const ppf::GaussJoin *jn,
+                       const int32_t *join_id, double *out, void *stream) {
+    const bool bad = nport < 0 || nchan < 1 || ngauss < 0 ||
+                     (nport > 0 && (!params || !scattering_index || !freqs || !nu_ref || !out));
+    int rc;
+    if (jn) {
+        // the rotation needs the even-length LDS transforms (the reference's
+        // irfft returns nbin - 1 bins at odd nbin: it cannot rotate those either)
+        if ((nbin & 1) || nbin < 32 || nbin > 8192 || !nbin_supported(nbin))
+            return fail(ctx, PPF_EUNSUP, "nbin=%d: even lengths in [32, 8192] (the LDS row transforms)", nbin);
+        if (bad) return fail(ctx, PPF_EINVAL, "bad gauss_portrait arguments");
+        if ((rc = check_join(ctx, (int64_t)(nport > 0 ? nport : 0) * nchan, jn->njoin, join_id, jn->join_params,
+                             jn->P)))
+            return rc;
+        if (jn->njoin == 0 || nport == 0) jn = nullptr;   // the plain model
+    }
     if (!ctx) return PPF_EINVAL;
     // rows past the LDS transforms (round 6): the Gaussians are evaluated
     // per bin in LDS (nbin doubles); the scattering convolution of even rows
@@ -1747,24 +1805,14 @@ int ppf_gauss_portrait_batch(ppf_ctx *ctx, int32_t nport, int32_t nchan, int32_t
     const bool lng = !nbin_supported(nbin);
     if (lng && (nbin <= 4095 || (size_t)nbin * sizeof(double) > 150u * 1024u))
         return fail(ctx, PPF_EUNSUP, "nbin=%d unsupported", nbin);
-    if (nport < 0 || nchan < 1 || ngauss < 0 ||
-        (nport > 0 && (!params || !scattering_index || !freqs || !nu_ref || !out)))
-        return fail(ctx, PPF_EINVAL, "bad gauss_portrait arguments");
-    if (!model_code) return fail(ctx, PPF_EINVAL, "model_code is NULL");
+    if (bad) return fail(ctx, PPF_EINVAL, "bad gauss_portrait arguments");
     ppf::GaussArgs a{};
-    for (int i = 0; i < 3; ++i) {
-        const char c = model_code[i];
-        if (c != '0' && c != '1')   // evolve_parameter's KeyError (pplib.py:1082-1084)
-            return fail(ctx, PPF_EINVAL, "model_code '%.3s': digit %d must be '0' or '1'",
-                        model_code, i);
-        a.code[i] = c - '0';
-    }
+    if ((rc = parse_model_code(ctx, model_code, a.code))) return rc;
     if (nport == 0) return PPF_OK;
     hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
     hipStream_t st = (hipStream_t)stream;
     const double2 *T = nullptr, *T2 = nullptr;
-    int rc;
     bool lscat = false;
     if (lng) {
         // the models' tau (params[p][1]) on the host: a scattered one at
@@ -1788,6 +1836,14 @@ int ppf_gauss_portrait_batch(ppf_ctx *ctx, int32_t nport, int32_t nchan, int32_t
     a.T = T; a.T2 = T2; a.out = out;
     a.Te = T; a.T2e = T2;
     if (!lng && (nbin & 1) && (rc = twiddles(ctx, nbin - 1, st, &a.Te, &a.T2e))) return rc;
+    if (jn) {
+        std::lock_guard<std::mutex> lk(ctx->lscr_mu);
+        ppf::GaussJoin j = *jn;
+        if ((rc = join_id_to_scratch(ctx, join_id, (int64_t)nport * nchan, st, j))) return rc;
+        if ((e = ppf::launch_gauss_port_join(a, j, st)) != hipSuccess) return hip_fail(ctx, e, "k_gauss_port_join");
+        if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(ctx, e, "hipStreamSynchronize");
+        return PPF_OK;
+    }
     if (!lscat) {
         if ((e = ppf::launch_gauss_port(a, st)) != hipSuccess) return hip_fail(ctx, e, "k_gauss_port");
         return PPF_OK;
@@ -1806,22 +1862,15 @@ int ppf_gauss_portrait_batch(ppf_ctx *ctx, int32_t nport, int32_t nchan, int32_t
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(ctx, e, "hipStreamSynchronize");
     return PPF_OK;
 }
-
-namespace {
-// the join arguments of the joined Gaussian entry points, checked on the
-// host: PPF_OK or the error set
-int check_join(ppf_ctx *ctx, int64_t nrow, int32_t njoin, const int32_t *join_id, const double *join_params,
-               const double *P) {
-    if (njoin < 0) return fail(ctx, PPF_EINVAL, "njoin=%d", njoin);
-    if (nrow > 0 && (!join_id || !P || (njoin > 0 && !join_params)))
-        return fail(ctx, PPF_EINVAL, "join_id / join_params / P is NULL");
-    for (int64_t i = 0; i < nrow; ++i)
-        if (join_id[i] < -1 || join_id[i] >= njoin)
-            return fail(ctx, PPF_EINVAL, "join_id[%lld] = %d: -1 or an archive in [0, %d)", (long long)i,
-                        join_id[i], njoin);
-    return PPF_OK;
-}
 }  // namespace
+
+int ppf_gauss_portrait_batch(ppf_ctx *ctx, int32_t nport, int32_t nchan, int32_t nbin,
+                             int32_t ngauss, const char *model_code, const double *params,
+                             const double *scattering_index, const double *freqs,
+                             const double *nu_ref, double *out, void *stream) {
+    return gauss_portrait_run(ctx, nport, nchan, nbin, ngauss, model_code, params, scattering_index, freqs, nu_ref,
+                              nullptr, nullptr, out, stream);
+}
 
 int ppf_gauss_portrait_join_batch(ppf_ctx *ctx, int32_t nport, int32_t nchan, int32_t nbin,
                                   int32_t ngauss, const char *model_code, const double *params,
@@ -1829,46 +1878,10 @@ int ppf_gauss_portrait_join_batch(ppf_ctx *ctx, int32_t nport, int32_t nchan, in
                                   const double *nu_ref, int32_t njoin, const int32_t *join_id,
                                   const double *join_params, const double *P, double *out,
                                   void *stream) {
-    // the rotation needs the even-length LDS transforms (the reference's
-    // irfft returns nbin - 1 bins at odd nbin: it cannot rotate those either)
-    if ((nbin & 1) || nbin < 32 || nbin > 8192 || !nbin_supported(nbin))
-        return fail(ctx, PPF_EUNSUP, "nbin=%d: even lengths in [32, 8192] (the LDS row transforms)", nbin);
-    if (nport < 0 || nchan < 1 || ngauss < 0 ||
-        (nport > 0 && (!params || !scattering_index || !freqs || !nu_ref || !out)))
-        return fail(ctx, PPF_EINVAL, "bad gauss_portrait arguments");
-    int rc;
-    if ((rc = check_join(ctx, (int64_t)(nport > 0 ? nport : 0) * nchan, njoin, join_id, join_params, P))) return rc;
-    if (njoin == 0 || nport == 0)
-        return ppf_gauss_portrait_batch(ctx, nport, nchan, nbin, ngauss, model_code, params, scattering_index,
-                                        freqs, nu_ref, out, stream);
-    if (!ctx) return PPF_EINVAL;
-    if (!model_code) return fail(ctx, PPF_EINVAL, "model_code is NULL");
-    ppf::GaussArgs a{};
-    for (int i = 0; i < 3; ++i) {
-        const char c = model_code[i];
-        if (c != '0' && c != '1')
-            return fail(ctx, PPF_EINVAL, "model_code '%.3s': digit %d must be '0' or '1'", model_code, i);
-        a.code[i] = c - '0';
-    }
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return hip_fail(ctx, e, "hipSetDevice");
-    hipStream_t st = (hipStream_t)stream;
-    if ((rc = twiddles(ctx, nbin, st, &a.T, &a.T2))) return rc;
-    a.nport = nport; a.nchan = nchan; a.nbin = nbin; a.log2N = rfft_log2(nbin);
-    a.ngauss = ngauss; a.npar = 2 + 6 * ngauss;
-    a.params = params; a.scat_index = scattering_index; a.freqs = freqs; a.nu_ref = nu_ref;
-    a.out = out; a.Te = a.T; a.T2e = a.T2;
-    // the device copy of join_id in the context's scratch: a synchronous call
-    const size_t jb = sizeof(int32_t) * (size_t)nport * nchan;
-    std::lock_guard<std::mutex> lk(ctx->lscr_mu);
-    if ((rc = lscr_reserve(ctx, align256(jb)))) return rc;
-    if ((e = hipMemcpyAsync(ctx->lscr, join_id, jb, hipMemcpyHostToDevice, st)) != hipSuccess)
-        return hip_fail(ctx, e, "hipMemcpyAsync(join_id)");
     ppf::GaussJoin j{};
-    j.njoin = njoin; j.join_id = (const int32_t *)ctx->lscr; j.join_params = join_params; j.P = P;
-    if ((e = ppf::launch_gauss_port_join(a, j, st)) != hipSuccess) return hip_fail(ctx, e, "k_gauss_port_join");
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(ctx, e, "hipStreamSynchronize");
-    return PPF_OK;
+    j.njoin = njoin; j.join_params = join_params; j.P = P;
+    return gauss_portrait_run(ctx, nport, nchan, nbin, ngauss, model_code, params, scattering_index, freqs, nu_ref,
+                              &j, join_id, out, stream);
 }
 
 namespace {
@@ -1918,17 +1931,11 @@ int gauss_lsq_run(ppf_ctx *ctx, int32_t nfit, int32_t nchan, int32_t nbin, int32
     if (nfit < 0 || nchan < 1 || ngauss < 0 || nfree < 0)
         return fail(ctx, PPF_EINVAL, "bad gauss_lsq shape");
     if (in_dtype != PPF_F32 && in_dtype != PPF_F64) return fail(ctx, PPF_EINVAL, "in_dtype");
-    if (!model_code) return fail(ctx, PPF_EINVAL, "model_code is NULL");
     ppf::GaussLsqArgs a{};
-    for (int i = 0; i < 3; ++i) {
-        const char c = model_code[i];
-        if (c != '0' && c != '1')
-            return fail(ctx, PPF_EINVAL, "model_code '%.3s': digit %d must be '0' or '1'", model_code, i);
-        a.code[i] = c - '0';
-    }
+    int rc;
+    if ((rc = parse_model_code(ctx, model_code, a.code))) return rc;
     const int npar = 2 + 6 * ngauss;
     const int njoin = jn ? jn->njoin : 0, next = npar + 2 * njoin;   // the scattering index's entry
-    int rc;
     if (jn && (rc = check_join(ctx, (int64_t)(nfit > 0 ? nfit : 0) * nchan, njoin, join_id, jn->join_params, jn->P)))
         return rc;
     if (nfree > 0 && (!free_idx || (nfit > 0 && !delta))) return fail(ctx, PPF_EINVAL, "free_idx / delta is NULL");
@@ -1968,14 +1975,9 @@ int gauss_lsq_run(ppf_ctx *ctx, int32_t nfit, int32_t nchan, int32_t nbin, int32
     a.data = data; a.inv_errs = inv_errs;
     a.rows = (double *)(ws + L.rows); a.part = (double *)(ws + L.part); a.gram = gram;
     if (njoin > 0) {
-        // the device copy of join_id in the context's scratch: a synchronous call
-        const size_t jb = sizeof(int32_t) * (size_t)nfit * nchan;
         std::lock_guard<std::mutex> lk(ctx->lscr_mu);
-        if ((rc = lscr_reserve(ctx, align256(jb)))) return rc;
-        if ((e = hipMemcpyAsync(ctx->lscr, join_id, jb, hipMemcpyHostToDevice, st)) != hipSuccess)
-            return hip_fail(ctx, e, "hipMemcpyAsync(join_id)");
         ppf::GaussJoin j = *jn;
-        j.join_id = (const int32_t *)ctx->lscr;
+        if ((rc = join_id_to_scratch(ctx, join_id, (int64_t)nfit * nchan, st, j))) return rc;
         if ((e = ppf::launch_gauss_lsq_join(a, j, st)) != hipSuccess)
             return hip_fail(ctx, e, "k_gauss_rows_join / k_gauss_gram_join");
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(ctx, e, "hipStreamSynchronize");

@@ -700,6 +700,105 @@ __device__ __forceinline__ double2 irfft_prebin(double2 Xk, double2 XNk, double2
     return cmk(e.x - o.y, e.y + o.x);            // E + i O
 }
 
+// ===========================================================================
+// The harmonic-pair core of the block row kernels (one workgroup per row:
+// rfft in LDS -> a factor per harmonic -> irfft).  A thread holds harmonic
+// k = tid + kBlock i in slot i of Xk[KMAX]; at even nbin k < nbin / 2 and slot
+// i of Xn holds its partner nbin / 2 - k of the packed transform's pre-pass
+// (the Nyquist term with k = 0); at odd nbin k <= nbin / 2 and Xn is unused.
+// Every thread of the block calls these.
+// ===========================================================================
+// odd nbin: Y_k (k <= nbin / 2) into the Hermitian full-length buffer of the
+// inverse transform, whose real part is then the row (the imaginary part of
+// Y_0 drops out, as numpy.fft.irfft ignores it)
+__device__ __forceinline__ void herm_put(double2 *buf, int nbin, int k, double2 Y) {
+    buf[k] = Y;
+    if (k) buf[nbin - k] = cconj(Y);
+}
+
+// forward half: Xk / Xn = f(X, k) of the row's harmonics (the row as load_row
+// + lds_fft_n(rfft_len(nbin)) left it), the imaginary parts of DC and Nyquist
+// dropped as numpy.fft.irfft does.  A barrier before LDS is written again.
+template <int KMAX, class F>
+__device__ __forceinline__ void harm_fwd(const double2 *lds, int nbin, const double2 *__restrict__ T2,
+                                         double2 (&Xk)[KMAX], double2 (&Xn)[KMAX], F f) {
+    const int N = nbin >> 1;
+    const bool odd = nbin & 1;
+    const int KH = odd ? N + 1 : N;
+#pragma unroll
+    for (int i = 0; i < KMAX; ++i) {
+        const int k = threadIdx.x + i * kBlock;
+        if (k < KH) {
+            double2 X1 = f(rbin(lds, nbin, T2, k), k);
+            double2 X2 = cmk(0.0, 0.0);
+            if (!odd) X2 = f(rfft_bin(lds, N, T2, N - k), N - k);
+            if (k == 0) { X1.y = 0.0; X2.y = 0.0; }   // DC and Nyquist: real parts only
+            Xk[i] = X1;
+            Xn[i] = X2;
+        }
+    }
+}
+
+// inverse half: the harmonics back into LDS (herm_put at odd nbin, the packed
+// pre-pass at even) and the inverse transform; the row is then lds[j].x / nbin
+// (odd) or the nbin / 2 packed points lds[j] / (nbin / 2) (even)
+template <int KMAX, bool MX>
+__device__ __forceinline__ void harm_inv(double2 *lds, int nbin, const double2 *__restrict__ T,
+                                         const double2 *__restrict__ T2, const double2 (&Xk)[KMAX],
+                                         const double2 (&Xn)[KMAX]) {
+    const bool odd = nbin & 1;
+    const int KH = odd ? (nbin >> 1) + 1 : nbin >> 1;
+#pragma unroll
+    for (int i = 0; i < KMAX; ++i) {
+        const int k = threadIdx.x + i * kBlock;
+        if (k < KH) {
+            if (odd) herm_put(lds, nbin, k, Xk[i]);
+            else lds[k] = irfft_prebin(Xk[i], Xn[i], T2[k]);
+        }
+    }
+    __syncthreads();
+    lds_fft_n<MX>(lds, rfft_len(nbin), T, true);
+}
+
+// inverse half of an odd row as the reference's irfft without a length takes
+// it: 2 N = nbin - 1 samples from X_0..X_N, X_N as the Nyquist term (its
+// imaginary part dropped): the even-length packed inverse with the twiddles
+// Te / T2e of nbin - 1; the N packed points lds[j] / N
+template <int KMAX, bool MX>
+__device__ __forceinline__ void harm_inv_ref(double2 *lds, int nbin, const double2 *__restrict__ Te,
+                                             const double2 *__restrict__ T2e, double2 (&Xk)[KMAX],
+                                             double2 (&Xn)[KMAX]) {
+    const int N = nbin >> 1;
+#pragma unroll
+    for (int i = 0; i < KMAX; ++i) {
+        const int k = threadIdx.x + i * kBlock;
+        if (k <= N) lds[k] = Xk[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < KMAX; ++i) {
+        const int k = threadIdx.x + i * kBlock;
+        if (k < N) {
+            Xk[i] = lds[k];
+            Xn[i] = lds[N - k];
+            if (k == 0) Xn[i].y = 0.0;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < KMAX; ++i) {
+        const int k = threadIdx.x + i * kBlock;
+        if (k < N) lds[k] = irfft_prebin(Xk[i], Xn[i], T2e[k]);
+    }
+    __syncthreads();
+    lds_fft_n<MX>(lds, N, Te, true);
+}
+
+// the n packed points of an inverse transform, scaled, to a row of the output
+__device__ __forceinline__ void store_packed(double2 *o, const double2 *lds, int n, double sc) {
+    for (int j = threadIdx.x; j < n; j += kBlock) o[j] = cscale(lds[j], sc);
+}
+
 // ---------------------------------------------------------------------------
 // scipy trust-ncg replica (scipy/optimize/_trustregion.py:_minimize_trust_region
 // with _trustregion_ncg.py:CGSteihaugSubproblem), on the fitted subspace.

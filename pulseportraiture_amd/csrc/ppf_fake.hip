@@ -34,6 +34,7 @@
 
 #include "ppf_device.hpp"
 #include "ppf_internal.hpp"
+#include "ppf_launch.hpp"
 #include "ppf_quant.hpp"
 
 namespace ppf {
@@ -150,8 +151,8 @@ __global__ __launch_bounds__(kBlock) void k_fake(FakeArgs a) {
 hipError_t launch_fake(const FakeArgs &a, hipStream_t st) {
     const size_t lds = (size_t)(a.nbin >> 1) * sizeof(double2);
     const unsigned grid = (unsigned)((int64_t)a.nsub * a.npol * a.nchan);
-    if (is_pow2(a.nbin >> 1)) hipLaunchKernelGGL(k_fake<false>, dim3(grid), dim3(kBlock), lds, st, a);
-    else hipLaunchKernelGGL(k_fake<true>, dim3(grid), dim3(kBlock), lds, st, a);
+    dispatch_mx(!is_pow2(a.nbin >> 1),
+                [&](auto MX) { hipLaunchKernelGGL(k_fake<MX()>, dim3(grid), dim3(kBlock), lds, st, a); });
     return hipGetLastError();
 }
 

@@ -29,37 +29,9 @@
 #include "ppf_device.hpp"
 #include "ppf_gaussrow.hpp"
 #include "ppf_internal.hpp"
+#include "ppf_launch.hpp"
 
 namespace ppf {
-
-template <int KMAX, bool MX>
-__global__ __launch_bounds__(kBlock) void k_gauss_rows(GaussLsqArgs a) {
-#pragma clang fp contract(off)
-    extern __shared__ __attribute__((aligned(16))) double2 lds[];
-    __shared__ double red[kWaves * 2];
-    const int nbin = a.nbin, N = nbin >> 1, ncol = a.nfree + 1;
-    const int col = blockIdx.x % ncol;
-    const int n = (blockIdx.x / ncol) % a.nchan, fit = blockIdx.x / (ncol * a.nchan);
-    const double *prm = a.params + (int64_t)fit * a.npar;
-    const double f = a.freqs[(int64_t)fit * a.nchan + n], nu_ref = a.nu_ref[fit];
-    int pj = -1;
-    double dj = 0.0;
-    if (col < a.nfree) {
-        pj = a.free_idx[col];
-        dj = a.delta[(int64_t)fit * a.nfree + col];
-    }
-    const double tau = pj == 1 ? prm[1] + dj : prm[1];
-    const double alpha = pj == a.npar ? a.scat_index[fit] + dj : a.scat_index[fit];
-    const GpRow kind = gp_build_row<KMAX, MX, true>(lds, red, nbin, a.ngauss, a.code[0], a.code[1], a.code[2], prm,
-                                              pj, dj, tau, alpha, f, nu_ref, a.T, a.T2, a.T, a.T2);
-    double2 *o = reinterpret_cast<double2 *>(a.rows) + (int64_t)blockIdx.x * N;
-    if (kind == kGpPacked) {
-        const double sc = 1.0 / (double)N;
-        for (int j = threadIdx.x; j < N; j += kBlock) o[j] = cscale(lds[j], sc);
-        return;
-    }
-    for (int j = threadIdx.x; j < N; j += kBlock) o[j] = lds[j];   // nbin is even here
-}
 
 // the rotation of a row of archive id (>= 0) at frequency f, rotate_data's
 // order of operations (pplib.py:2478-2504); jp: the fit's join parameters,
@@ -74,20 +46,33 @@ __device__ __forceinline__ double join_rot(const double *jp, int id, int pq, dou
     return phi + D * fterm;
 }
 
-// k_gauss_rows of the joined model (even nbin): free_idx indexes [params,
-// join params, scattering index].  A column that perturbs a join parameter
-// of another archive than the row's equals m(p): its workgroup builds
-// nothing, and k_gauss_gram_join reads no row there.
-template <int KMAX, bool MX>
-__global__ __launch_bounds__(kBlock) void k_gauss_rows_join(GaussLsqArgs a, GaussJoin jn) {
+// lds as gp_build_row left it (even nbin) to the row o of nbin doubles
+__device__ __forceinline__ void gauss_store_even(double2 *o, const double2 *lds, int N, GpRow kind) {
+    if (kind == kGpPacked) {
+        store_packed(o, lds, N, 1.0 / (double)N);
+        return;
+    }
+    for (int j = threadIdx.x; j < N; j += kBlock) o[j] = lds[j];
+}
+
+// k_gauss_rows and, JOIN, k_gauss_rows_join (even nbin): free_idx then
+// indexes [params, join params, scattering index].  A column that perturbs a
+// join parameter of another archive than the row's equals m(p): its
+// workgroup builds nothing, and k_gauss_gram_join reads no row there.  A row
+// of no archive (join_id < 0) is built by the unrotated code.
+template <int KMAX, bool MX, bool JOIN>
+__device__ __forceinline__ void gauss_rows_body(const GaussLsqArgs &a, const GaussJoin &jn) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) double2 lds[];
     __shared__ double red[kWaves * 2];
     const int nbin = a.nbin, N = nbin >> 1, ncol = a.nfree + 1;
     const int col = blockIdx.x % ncol;
     const int n = (blockIdx.x / ncol) % a.nchan, fit = blockIdx.x / (ncol * a.nchan);
-    const int id = jn.join_id[(int64_t)fit * a.nchan + n];
-    const int next = a.npar + 2 * jn.njoin;
+    int id = -1, next = a.npar;   // the row's archive; the scattering index's entry
+    if constexpr (JOIN) {
+        id = jn.join_id[(int64_t)fit * a.nchan + n];
+        next = a.npar + 2 * jn.njoin;
+    }
     int pj = -1;
     double dj = 0.0;
     if (col < a.nfree) {
@@ -101,21 +86,25 @@ __global__ __launch_bounds__(kBlock) void k_gauss_rows_join(GaussLsqArgs a, Gaus
     const double tau = pj == 1 ? prm[1] + dj : prm[1];
     const double alpha = pj == next ? a.scat_index[fit] + dj : a.scat_index[fit];
     GpRow kind;
-    if (id >= 0) {
+    if (JOIN && id >= 0) {
         const double rot = join_rot(jn.join_params + (int64_t)fit * 2 * jn.njoin, id, pq, dj, jn.P[fit], f, nu_ref);
-        kind = gp_build_row<KMAX, MX, true, true>(lds, red, nbin, a.ngauss, a.code[0], a.code[1], a.code[2], prm, pj,
+        kind = gp_build_row<KMAX, MX, true, JOIN>(lds, red, nbin, a.ngauss, a.code[0], a.code[1], a.code[2], prm, pj,
                                                   dj, tau, alpha, f, nu_ref, a.T, a.T2, a.T, a.T2, rot);
     } else {
         kind = gp_build_row<KMAX, MX, true>(lds, red, nbin, a.ngauss, a.code[0], a.code[1], a.code[2], prm, pj, dj,
                                             tau, alpha, f, nu_ref, a.T, a.T2, a.T, a.T2);
     }
-    double2 *o = reinterpret_cast<double2 *>(a.rows) + (int64_t)blockIdx.x * N;
-    if (kind == kGpPacked) {
-        const double sc = 1.0 / (double)N;
-        for (int j = threadIdx.x; j < N; j += kBlock) o[j] = cscale(lds[j], sc);
-        return;
-    }
-    for (int j = threadIdx.x; j < N; j += kBlock) o[j] = lds[j];
+    gauss_store_even(reinterpret_cast<double2 *>(a.rows) + (int64_t)blockIdx.x * N, lds, N, kind);
+}
+
+template <int KMAX, bool MX>
+__global__ __launch_bounds__(kBlock) void k_gauss_rows(GaussLsqArgs a) {
+    gauss_rows_body<KMAX, MX, false>(a, GaussJoin{});
+}
+
+template <int KMAX, bool MX>
+__global__ __launch_bounds__(kBlock) void k_gauss_rows_join(GaussLsqArgs a, GaussJoin jn) {
+    gauss_rows_body<KMAX, MX, true>(a, jn);
 }
 
 // k_gauss_port of the joined model (even nbin within the LDS transforms): a
@@ -140,13 +129,7 @@ __global__ __launch_bounds__(kBlock) void k_gauss_port_join(GaussArgs a, GaussJo
         kind = gp_build_row<KMAX, MX, false>(lds, red, nbin, a.ngauss, a.code[0], a.code[1], a.code[2], prm, -1, 0.0,
                                              prm[1], a.scat_index[p], f, nu_ref, a.T, a.T2, a.Te, a.T2e);
     }
-    double2 *o = reinterpret_cast<double2 *>(a.out) + (int64_t)blockIdx.x * N;
-    if (kind == kGpPacked) {
-        const double sc = 1.0 / (double)N;
-        for (int j = threadIdx.x; j < N; j += kBlock) o[j] = cscale(lds[j], sc);
-        return;
-    }
-    for (int j = threadIdx.x; j < N; j += kBlock) o[j] = lds[j];
+    gauss_store_even(reinterpret_cast<double2 *>(a.out) + (int64_t)blockIdx.x * N, lds, N, kind);
 }
 
 // tile pair index -> (ti <= tj), row-major over the upper triangle
@@ -269,32 +252,13 @@ __global__ __launch_bounds__(kBlock) void k_gauss_gram_fin(GaussLsqArgs a, int n
     if (ti != tj) G[(int64_t)j * ncol + i] = s;   // a diagonal tile holds both triangles itself
 }
 
-static inline int kmax_pow2(int N) {
-    int q = (N + kBlock - 1) / kBlock, k = 1;
-    while (k < q) k <<= 1;
-    return k;
-}
-
-#define GROWS(K)                                                                        \
-    do {                                                                                \
-        if (mx) hipLaunchKernelGGL((k_gauss_rows<K, true>), g, b, lds, st, a);          \
-        else hipLaunchKernelGGL((k_gauss_rows<K, false>), g, b, lds, st, a);            \
-    } while (0)
-
 hipError_t launch_gauss_lsq(const GaussLsqArgs &a, hipStream_t st) {
     const size_t lds = (size_t)(a.nbin / 2) * sizeof(double2);
     const int ncol = a.nfree + 1;
     dim3 g((unsigned)((int64_t)a.nfit * a.nchan * ncol)), b(kBlock);
-    const bool mx = !is_pow2(a.nbin / 2);
-    switch (kmax_pow2(a.nbin / 2)) {
-        case 1: GROWS(1); break;
-        case 2: GROWS(2); break;
-        case 4: GROWS(4); break;
-        case 8: GROWS(8); break;
-        case 16: GROWS(16); break;
-        default: return hipErrorInvalidValue;
-    }
-    hipError_t e = hipGetLastError();
+    hipError_t e = dispatch_kmax_mx(a.nbin / 2, !is_pow2(a.nbin / 2), [&](auto K, auto MX) {
+        hipLaunchKernelGGL((k_gauss_rows<K(), MX()>), g, b, lds, st, a);
+    });
     if (e != hipSuccess) return e;
     const int nchunk = a.nchan * a.nseg;
     hipLaunchKernelGGL(k_gauss_gram, dim3((unsigned)nchunk, (unsigned)a.npair, (unsigned)a.nfit), b, 0, st, a);
@@ -303,26 +267,13 @@ hipError_t launch_gauss_lsq(const GaussLsqArgs &a, hipStream_t st) {
     return hipGetLastError();
 }
 
-#define GROWSJ(K)                                                                       \
-    do {                                                                                \
-        if (mx) hipLaunchKernelGGL((k_gauss_rows_join<K, true>), g, b, lds, st, a, j);  \
-        else hipLaunchKernelGGL((k_gauss_rows_join<K, false>), g, b, lds, st, a, j);    \
-    } while (0)
-
 hipError_t launch_gauss_lsq_join(const GaussLsqArgs &a, const GaussJoin &j, hipStream_t st) {
     const size_t lds = (size_t)(a.nbin / 2) * sizeof(double2);
     const int ncol = a.nfree + 1;
     dim3 g((unsigned)((int64_t)a.nfit * a.nchan * ncol)), b(kBlock);
-    const bool mx = !is_pow2(a.nbin / 2);
-    switch (kmax_pow2(a.nbin / 2)) {
-        case 1: GROWSJ(1); break;
-        case 2: GROWSJ(2); break;
-        case 4: GROWSJ(4); break;
-        case 8: GROWSJ(8); break;
-        case 16: GROWSJ(16); break;
-        default: return hipErrorInvalidValue;
-    }
-    hipError_t e = hipGetLastError();
+    hipError_t e = dispatch_kmax_mx(a.nbin / 2, !is_pow2(a.nbin / 2), [&](auto K, auto MX) {
+        hipLaunchKernelGGL((k_gauss_rows_join<K(), MX()>), g, b, lds, st, a, j);
+    });
     if (e != hipSuccess) return e;
     const int nchunk = a.nchan * a.nseg;
     hipLaunchKernelGGL(k_gauss_gram_join, dim3((unsigned)nchunk, (unsigned)a.npair, (unsigned)a.nfit), b, 0, st, a,
@@ -332,26 +283,13 @@ hipError_t launch_gauss_lsq_join(const GaussLsqArgs &a, const GaussJoin &j, hipS
     return hipGetLastError();
 }
 
-#define GPORTJ(K)                                                                       \
-    do {                                                                                \
-        if (mx) hipLaunchKernelGGL((k_gauss_port_join<K, true>), g, b, lds, st, a, j);  \
-        else hipLaunchKernelGGL((k_gauss_port_join<K, false>), g, b, lds, st, a, j);    \
-    } while (0)
-
 // even nbin within the LDS transforms (checked by the caller)
 hipError_t launch_gauss_port_join(const GaussArgs &a, const GaussJoin &j, hipStream_t st) {
     const size_t lds = (size_t)(a.nbin / 2) * sizeof(double2);
     dim3 g((unsigned)((int64_t)a.nport * a.nchan)), b(kBlock);
-    const bool mx = !is_pow2(a.nbin / 2);
-    switch (kmax_pow2(a.nbin / 2)) {
-        case 1: GPORTJ(1); break;
-        case 2: GPORTJ(2); break;
-        case 4: GPORTJ(4); break;
-        case 8: GPORTJ(8); break;
-        case 16: GPORTJ(16); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_kmax_mx(a.nbin / 2, !is_pow2(a.nbin / 2), [&](auto K, auto MX) {
+        hipLaunchKernelGGL((k_gauss_port_join<K(), MX()>), g, b, lds, st, a, j);
+    });
 }
 
 }  // namespace ppf

@@ -128,39 +128,19 @@ __device__ __forceinline__ GpRow gp_build_row(double2 *lds, double *red, int nbi
         __syncthreads();
         lds_fft_n<MX>(lds, N, T, false);
         double2 Xk[KMAX], Xn[KMAX];
-#pragma unroll
-        for (int i = 0; i < KMAX; ++i) {
-            const int k = threadIdx.x + i * kBlock;
-            if (k < N) {
-                double2 X1 = rfft_bin(lds, N, T2, k);
-                double2 X2 = rfft_bin(lds, N, T2, N - k);
-                if (tn != 0.0) {
-                    X1 = cmul(X1, scat_recip((2.0 * kPi * (double)k) * tn));
-                    X2 = cmul(X2, scat_recip((2.0 * kPi * (double)(N - k)) * tn));
-                }
-                if (k == 0) { X1.y = 0.0; X2.y = 0.0; }   // the scattering irfft: DC, Nyquist real
-                X1 = cmul(X1, cexp2pi((double)k * rot));
-                X2 = cmul(X2, cexp2pi((double)(N - k) * rot));
-                if (k == 0) { X1.y = 0.0; X2.y = 0.0; }   // the rotation's irfft
-                Xk[i] = X1;
-                Xn[i] = X2;
-            }
-        }
+        harm_fwd<KMAX>(lds, nbin, T2, Xk, Xn, [&](double2 X, int k) {
+            if (tn != 0.0) X = cmul(X, scat_recip((2.0 * kPi * (double)k) * tn));
+            if (k == 0 || k == N) X.y = 0.0;   // the scattering irfft: DC, Nyquist real
+            return cmul(X, cexp2pi((double)k * rot));   // (the rotation's irfft: harm_fwd)
+        });
         __syncthreads();
-#pragma unroll
-        for (int i = 0; i < KMAX; ++i) {
-            const int k = threadIdx.x + i * kBlock;
-            if (k < N) lds[k] = irfft_prebin(Xk[i], Xn[i], T2[k]);
-        }
-        __syncthreads();
-        lds_fft_n<MX>(lds, N, T, true);
+        harm_inv<KMAX, MX>(lds, nbin, T, T2, Xk, Xn);
         return kGpPacked;
     }
     if (tau != 0.0) {
         // taus = (tau / nbin) * (freqs / nu_ref)**alpha; B_k = 1 / (1 + 2 pi i k tau_n)
         const double tn = tau / (double)nbin * pow(f / nu_ref, alpha);
         const bool odd = nbin & 1;
-        const int KH = odd ? N + 1 : N;
         __syncthreads();
         if (odd) {
             // the real row (doubles) -> complex points in place: all reads first
@@ -180,59 +160,17 @@ __device__ __forceinline__ GpRow gp_build_row(double2 *lds, double *red, int nbi
         }
         lds_fft_n<MX>(lds, rfft_len(nbin), T, false);
         double2 Xk[KMAX], Xn[KMAX];
-#pragma unroll
-        for (int i = 0; i < KMAX; ++i) {
-            const int k = threadIdx.x + i * kBlock;
-            if (k < KH) {
-                double2 X1 = odd ? lds[k] : rfft_bin(lds, N, T2, k);
-                double2 X2 = odd ? cmk(0.0, 0.0) : rfft_bin(lds, N, T2, N - k);
-                if (tn != 0.0) {
-                    X1 = cmul(X1, scat_recip((2.0 * kPi * (double)k) * tn));
-                    if (!odd) X2 = cmul(X2, scat_recip((2.0 * kPi * (double)(N - k)) * tn));
-                }
-                if (k == 0) { X1.y = 0.0; X2.y = 0.0; }   // irfft keeps DC, Nyquist real parts
-                Xk[i] = X1;
-                Xn[i] = X2;
-            }
-        }
+        harm_fwd<KMAX>(lds, nbin, T2, Xk, Xn, [&](double2 X, int k) {
+            return tn != 0.0 ? cmul(X, scat_recip((2.0 * kPi * (double)k) * tn)) : X;
+        });
         __syncthreads();
         if (odd) {
-            // the reference's irfft takes no length (pplib.py:957): 2 N =
-            // nbin - 1 bins from X_0..X_N, X_N as the Nyquist term (its
-            // imaginary part dropped); the even-length packed inverse with
-            // the nbin - 1 twiddles, the row's last column zero
-#pragma unroll
-            for (int i = 0; i < KMAX; ++i) {
-                const int k = threadIdx.x + i * kBlock;
-                if (k < KH) lds[k] = Xk[i];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < KMAX; ++i) {
-                const int k = threadIdx.x + i * kBlock;
-                if (k < N) {
-                    Xk[i] = lds[k];
-                    Xn[i] = lds[N - k];
-                    if (k == 0) Xn[i].y = 0.0;
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < KMAX; ++i) {
-                const int k = threadIdx.x + i * kBlock;
-                if (k < N) lds[k] = irfft_prebin(Xk[i], Xn[i], T2e[k]);
-            }
-            __syncthreads();
-            lds_fft_n<MX>(lds, N, Te, true);
+            // the reference's irfft takes no length (pplib.py:957): nbin - 1
+            // bins, the row's last column zero
+            harm_inv_ref<KMAX, MX>(lds, nbin, Te, T2e, Xk, Xn);
             return kGpPackedOdd;
         }
-#pragma unroll
-        for (int i = 0; i < KMAX; ++i) {
-            const int k = threadIdx.x + i * kBlock;
-            if (k < KH) lds[k] = irfft_prebin(Xk[i], Xn[i], T2[k]);
-        }
-        __syncthreads();
-        lds_fft_n<MX>(lds, rfft_len(nbin), T, true);
+        harm_inv<KMAX, MX>(lds, nbin, T, T2, Xk, Xn);
         return kGpPacked;
     }
     __syncthreads();

@@ -18,18 +18,13 @@
 #include "ppf_device.hpp"
 #include "ppf_gaussrow.hpp"
 #include "ppf_internal.hpp"
+#include "ppf_launch.hpp"
 
 namespace ppf {
 
 // (load_row and rbin, the row loading and the rFFT bin every block-FFT kernel
-// starts from, are in ppf_device.hpp: ppf_noisefit.hip takes them too)
-// odd nbin: Y_k (k <= nbin / 2) into the Hermitian full-length buffer of the
-// inverse transform, whose real part is then the row (the imaginary part of
-// Y_0 drops out, as numpy.fft.irfft ignores it)
-__device__ __forceinline__ void herm_put(double2 *buf, int nbin, int k, double2 Y) {
-    buf[k] = Y;
-    if (k) buf[nbin - k] = cconj(Y);
-}
+// starts from, and the harmonic-pair core of the rfft -> factor -> irfft
+// kernels, harm_fwd / harm_inv, are in ppf_device.hpp)
 
 // ===========================================================================
 // twiddles: T[t] = exp(-2 pi i t/N), T2[k] = exp(-i pi k/N), t,k < N
@@ -1048,85 +1043,41 @@ __global__ __launch_bounds__(kBlock) void k_guess(GuessArgs a) {
 // ===========================================================================
 // k_rotate: out = irfft(rfft(in) * exp(2 pi i k phase_row))
 // ===========================================================================
+// the row's rfft times exp(2 pi i k ph) in Xk / Xn (harm_fwd), LDS free again
+template <int KMAX, bool MX>
+__device__ __forceinline__ void rotate_fwd(double2 *lds, const void *in, int dtype, int64_t row, int nbin, double ph,
+                                           const double2 *T, const double2 *T2, double2 (&Xk)[KMAX],
+                                           double2 (&Xn)[KMAX]) {
+    load_row(lds, in, dtype, row, nbin);
+    __syncthreads();
+    lds_fft_n<MX>(lds, rfft_len(nbin), T, false);
+    harm_fwd<KMAX>(lds, nbin, T2, Xk, Xn, [ph](double2 X, int k) { return cmul(X, cexp2pi((double)k * ph)); });
+    __syncthreads();
+}
+
 template <int KMAX, bool MX>
 __global__ __launch_bounds__(kBlock) void k_rotate(RotateArgs a) {
     extern __shared__ __attribute__((aligned(16))) double2 lds[];
     const int N = a.nbin >> 1;
     const bool odd = a.nbin & 1;
-    const int KH = odd ? N + 1 : N;        // harmonic slots: k < KH
     const int64_t row = blockIdx.x;
-    load_row(lds, a.in, a.dtype, row, a.nbin);
-    __syncthreads();
-    lds_fft_n<MX>(lds, rfft_len(a.nbin), a.T, false);
     double2 Xk[KMAX], Xn[KMAX];
-    const double ph = a.phases[row];
-    // harmonics handled by this thread: k = tid + 256 i, k < N (pre-pass
-    // pairs k, N-k); odd nbin: k <= N, no pairs
-#pragma unroll
-    for (int i = 0; i < KMAX; ++i) {
-        int k = threadIdx.x + i * kBlock;
-        if (k < KH) {
-            double2 X1 = cmul(rbin(lds, a.nbin, a.T2, k), cexp2pi((double)k * ph));
-            double2 X2 = cmk(0.0, 0.0);
-            if (!odd) X2 = cmul(rfft_bin(lds, N, a.T2, N - k), cexp2pi((double)(N - k) * ph));
-            if (k == 0) { X1.y = 0.0; X2.y = 0.0; }   // DC and Nyquist: real parts only
-            Xk[i] = X1;
-            Xn[i] = X2;
-        }
-    }
-    __syncthreads();
+    rotate_fwd<KMAX, MX>(lds, a.in, a.dtype, row, a.nbin, a.phases[row], a.T, a.T2, Xk, Xn);
+    double2 *o2 = reinterpret_cast<double2 *>(a.out) + row * (int64_t)N;
     if (odd && a.ref_len) {
-        // the reference's irfft without a length: 2 N = nbin - 1 samples
-        // from X_0..X_N, X_N as the Nyquist term (imaginary part dropped):
-        // the even-length packed inverse with the nbin - 1 twiddles (as
-        // k_gauss_port's scattered rows)
-#pragma unroll
-        for (int i = 0; i < KMAX; ++i) {
-            const int k = threadIdx.x + i * kBlock;
-            if (k < KH) lds[k] = Xk[i];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < KMAX; ++i) {
-            const int k = threadIdx.x + i * kBlock;
-            if (k < N) {
-                Xk[i] = lds[k];
-                Xn[i] = lds[N - k];
-                if (k == 0) Xn[i].y = 0.0;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < KMAX; ++i) {
-            const int k = threadIdx.x + i * kBlock;
-            if (k < N) lds[k] = irfft_prebin(Xk[i], Xn[i], a.T2e[k]);
-        }
-        __syncthreads();
-        lds_fft_n<MX>(lds, N, a.Te, true);
-        const double sc = 1.0 / (double)N;
-        double2 *o = reinterpret_cast<double2 *>(a.out) + row * (int64_t)N;
-        for (int j = threadIdx.x; j < N; j += kBlock) o[j] = cscale(lds[j], sc);
+        // the reference's irfft without a length: nbin - 1 samples
+        harm_inv_ref<KMAX, MX>(lds, a.nbin, a.Te, a.T2e, Xk, Xn);
+        store_packed(o2, lds, N, 1.0 / (double)N);
         return;
     }
-#pragma unroll
-    for (int i = 0; i < KMAX; ++i) {
-        int k = threadIdx.x + i * kBlock;
-        if (k < KH) {
-            if (odd) herm_put(lds, a.nbin, k, Xk[i]);
-            else lds[k] = irfft_prebin(Xk[i], Xn[i], a.T2[k]);
-        }
-    }
-    __syncthreads();
-    lds_fft_n<MX>(lds, rfft_len(a.nbin), a.T, true);
+    harm_inv<KMAX, MX>(lds, a.nbin, a.T, a.T2, Xk, Xn);
     if (odd) {
         const double sc = 1.0 / (double)a.nbin;
         double *o = reinterpret_cast<double *>(a.out) + row * (int64_t)a.nbin;
         for (int j = threadIdx.x; j < a.nbin; j += kBlock) o[j] = lds[j].x * sc;
         return;
     }
-    const double sc = 1.0 / (double)N;
-    double2 *o = reinterpret_cast<double2 *>(a.out) + row * (int64_t)N;
-    for (int j = threadIdx.x; j < N; j += kBlock) o[j] = cscale(lds[j], sc);
+    store_packed(o2, lds, N, 1.0 / (double)N);
 }
 
 // ===========================================================================
@@ -1151,32 +1102,14 @@ __global__ __launch_bounds__(kBlock) void k_inst_resp(InstRespArgs a) {
     lds_fft_n<MX>(lds, N, a.T, false);
     double2 Xk[KMAX], Xn[KMAX];
     const double w = a.widths[row];
-    // harmonics of this thread: k = tid + 256 i < N, paired with N - k
-    // (k = 0 with the Nyquist term)
-#pragma unroll
-    for (int i = 0; i < KMAX; ++i) {
-        const int k = threadIdx.x + i * kBlock;
-        if (k < N) {
-            double f1 = sinc_pi((double)k * w), f2 = sinc_pi((double)(N - k) * w);
-            if (a.table) { f1 *= a.table[k]; f2 *= a.table[N - k]; }
-            double2 X1 = cscale(rfft_bin(lds, N, a.T2, k), f1);
-            double2 X2 = cscale(rfft_bin(lds, N, a.T2, N - k), f2);
-            if (k == 0) { X1.y = 0.0; X2.y = 0.0; }   // DC and Nyquist: real parts only
-            Xk[i] = X1;
-            Xn[i] = X2;
-        }
-    }
+    harm_fwd<KMAX>(lds, a.nbin, a.T2, Xk, Xn, [&](double2 X, int k) {
+        double f = sinc_pi((double)k * w);
+        if (a.table) f *= a.table[k];
+        return cscale(X, f);
+    });
     __syncthreads();
-#pragma unroll
-    for (int i = 0; i < KMAX; ++i) {
-        const int k = threadIdx.x + i * kBlock;
-        if (k < N) lds[k] = irfft_prebin(Xk[i], Xn[i], a.T2[k]);
-    }
-    __syncthreads();
-    lds_fft_n<MX>(lds, N, a.T, true);
-    const double sc = 1.0 / (double)N;
-    double2 *o = reinterpret_cast<double2 *>(a.out) + row * (int64_t)N;
-    for (int j = threadIdx.x; j < N; j += kBlock) o[j] = cscale(lds[j], sc);
+    harm_inv<KMAX, MX>(lds, a.nbin, a.T, a.T2, Xk, Xn);
+    store_packed(reinterpret_cast<double2 *>(a.out) + row * (int64_t)N, lds, N, 1.0 / (double)N);
 }
 
 // ===========================================================================
@@ -1396,26 +1329,12 @@ __global__ __launch_bounds__(kBlock) void k_gauss_port(GaussArgs a) {
 // ===========================================================================
 // host-side launchers
 // ===========================================================================
-// per-thread harmonic slots of the block kernels' KMAX instantiations (1, 2,
-// 4, 8, 16): the smallest that holds ceil(N / kBlock)
-static inline int kmax_pow2(int N) {
-    int q = (N + kBlock - 1) / kBlock, k = 1;
-    while (k < q) k <<= 1;
-    return k;
-}
+// (the <KMAX, MX> and <MX> instantiations are picked by ppf_launch.hpp)
 static inline int log2i(int n) {
     int l = 0;
     while ((1 << l) < n) ++l;
     return l;
 }
-
-// launch KER<A, MX> with MX = mx (the mixed-radix FFT compiled in only when
-// nbin / 2 is not a power of two; lds_fft_n)
-#define MXL(mx, KER, A, ...)                                          \
-    do {                                                              \
-        if (mx) hipLaunchKernelGGL((KER<A, true>), __VA_ARGS__);      \
-        else hipLaunchKernelGGL((KER<A, false>), __VA_ARGS__);        \
-    } while (0)
 
 hipError_t launch_twiddles(int N, double2 *T, double2 *T2, hipStream_t st) {
     hipLaunchKernelGGL(k_twiddles, dim3((N + 255) / 256), dim3(256), 0, st, N, T, T2);
@@ -1423,8 +1342,9 @@ hipError_t launch_twiddles(int N, double2 *T, double2 *T2, hipStream_t st) {
 }
 hipError_t launch_rfft_rows(const RfftArgs &a, int64_t nrows, hipStream_t st) {
     size_t lds = (size_t)rfft_len(a.nbin) * sizeof(double2);
-    if (is_pow2(rfft_len(a.nbin))) hipLaunchKernelGGL(k_rfft_rows<false>, dim3((unsigned)nrows), dim3(kBlock), lds, st, a);
-    else hipLaunchKernelGGL(k_rfft_rows<true>, dim3((unsigned)nrows), dim3(kBlock), lds, st, a);
+    dispatch_mx(!is_pow2(rfft_len(a.nbin)), [&](auto MX) {
+        hipLaunchKernelGGL(k_rfft_rows<MX()>, dim3((unsigned)nrows), dim3(kBlock), lds, st, a);
+    });
     return hipGetLastError();
 }
 template <int L2>
@@ -1561,8 +1481,8 @@ hipError_t launch_guess(const GuessArgs &a, hipStream_t st) {
     if (a.gsh) {
         // the brute grid in global memory (long rows: gspec given, no
         // transform runs in the kernel)
-        if (a.gspec || is_pow2(rfft_len(a.nbin))) hipLaunchKernelGGL((k_guess<false, 0, true>), g, b, lds, st, a);
-        else hipLaunchKernelGGL((k_guess<true, 0, true>), g, b, lds, st, a);
+        dispatch_mx(!a.gspec && !is_pow2(rfft_len(a.nbin)),
+                    [&](auto MX) { hipLaunchKernelGGL((k_guess<MX(), 0, true>), g, b, lds, st, a); });
     } else if (a.czB && is_pow2(rfft_len(a.nbin))) {
         switch (a.czP) {
             case 512: hipLaunchKernelGGL((k_guess<false, 9>), g, b, lds, st, a); break;
@@ -1570,10 +1490,9 @@ hipError_t launch_guess(const GuessArgs &a, hipStream_t st) {
             case 2048: hipLaunchKernelGGL((k_guess<false, 11>), g, b, lds, st, a); break;
             default: return hipErrorInvalidValue;
         }
-    } else if (is_pow2(rfft_len(a.nbin))) {
-        hipLaunchKernelGGL((k_guess<false, 0>), g, b, lds, st, a);
     } else {
-        hipLaunchKernelGGL((k_guess<true, 0>), g, b, lds, st, a);
+        dispatch_mx(!is_pow2(rfft_len(a.nbin)),
+                    [&](auto MX) { hipLaunchKernelGGL((k_guess<MX(), 0>), g, b, lds, st, a); });
     }
     return hipGetLastError();
 }
@@ -1586,45 +1505,24 @@ hipError_t launch_gauss_port(const GaussArgs &a, hipStream_t st) {
         hipLaunchKernelGGL((k_gauss_port<1, false>), g, b, (size_t)a.nbin * sizeof(double), st, a);
         return hipGetLastError();
     }
-    const bool mx = !is_pow2(rfft_len(a.nbin));
-    switch (kmax_pow2(a.nbin / 2 + (a.nbin & 1))) {
-        case 1: MXL(mx, k_gauss_port, 1, g, b, lds, st, a); break;
-        case 2: MXL(mx, k_gauss_port, 2, g, b, lds, st, a); break;
-        case 4: MXL(mx, k_gauss_port, 4, g, b, lds, st, a); break;
-        case 8: MXL(mx, k_gauss_port, 8, g, b, lds, st, a); break;
-        case 16: MXL(mx, k_gauss_port, 16, g, b, lds, st, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_kmax_mx(a.nbin / 2 + (a.nbin & 1), !is_pow2(rfft_len(a.nbin)), [&](auto K, auto MX) {
+        hipLaunchKernelGGL((k_gauss_port<K(), MX()>), g, b, lds, st, a);
+    });
 }
 hipError_t launch_rotate(const RotateArgs &a, int64_t nrows, hipStream_t st) {
     size_t lds = (size_t)rfft_len(a.nbin) * sizeof(double2);
     dim3 g((unsigned)nrows), b(kBlock);
-    const bool mx = !is_pow2(rfft_len(a.nbin));
-    switch (kmax_pow2(a.nbin / 2 + (a.nbin & 1))) {
-        case 1: MXL(mx, k_rotate, 1, g, b, lds, st, a); break;
-        case 2: MXL(mx, k_rotate, 2, g, b, lds, st, a); break;
-        case 4: MXL(mx, k_rotate, 4, g, b, lds, st, a); break;
-        case 8: MXL(mx, k_rotate, 8, g, b, lds, st, a); break;
-        case 16: MXL(mx, k_rotate, 16, g, b, lds, st, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_kmax_mx(a.nbin / 2 + (a.nbin & 1), !is_pow2(rfft_len(a.nbin)), [&](auto K, auto MX) {
+        hipLaunchKernelGGL((k_rotate<K(), MX()>), g, b, lds, st, a);
+    });
 }
 hipError_t launch_inst_resp(const InstRespArgs &a, int64_t nrows, hipStream_t st) {
     const int N = a.nbin / 2;                // even nbin (checked by the caller)
     size_t lds = (size_t)N * sizeof(double2);
     dim3 g((unsigned)nrows), b(kBlock);
-    const bool mx = !is_pow2(N);
-    switch (kmax_pow2(N)) {
-        case 1: MXL(mx, k_inst_resp, 1, g, b, lds, st, a); break;
-        case 2: MXL(mx, k_inst_resp, 2, g, b, lds, st, a); break;
-        case 4: MXL(mx, k_inst_resp, 4, g, b, lds, st, a); break;
-        case 8: MXL(mx, k_inst_resp, 8, g, b, lds, st, a); break;
-        case 16: MXL(mx, k_inst_resp, 16, g, b, lds, st, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_kmax_mx(N, !is_pow2(N), [&](auto K, auto MX) {
+        hipLaunchKernelGGL((k_inst_resp<K(), MX()>), g, b, lds, st, a);
+    });
 }
 // ===========================================================================
 // ppalign accumulation.  k_align_part: workgroup = (channel n, group g of
@@ -1749,21 +1647,10 @@ hipError_t launch_align(const AlignArgs &a, hipStream_t st) {
         hipError_t e = launch_align_part_w(a, st);
         if (e != hipSuccess) return e;
     }
-    const bool mx = !is_pow2(rfft_len(a.nbin));
-    switch (kmax_pow2(a.nbin / 2 + (a.nbin & 1))) {
-        case 1: if (!wave) MXL(mx, k_align_part, 1, gp, b, lds, st, a);
-                MXL(mx, k_align_fin, 1, gf, b, lds, st, a); break;
-        case 2: if (!wave) MXL(mx, k_align_part, 2, gp, b, lds, st, a);
-                MXL(mx, k_align_fin, 2, gf, b, lds, st, a); break;
-        case 4: if (!wave) MXL(mx, k_align_part, 4, gp, b, lds, st, a);
-                MXL(mx, k_align_fin, 4, gf, b, lds, st, a); break;
-        case 8: if (!wave) MXL(mx, k_align_part, 8, gp, b, lds, st, a);
-                MXL(mx, k_align_fin, 8, gf, b, lds, st, a); break;
-        case 16: if (!wave) MXL(mx, k_align_part, 16, gp, b, lds, st, a);
-                 MXL(mx, k_align_fin, 16, gf, b, lds, st, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_kmax_mx(a.nbin / 2 + (a.nbin & 1), !is_pow2(rfft_len(a.nbin)), [&](auto K, auto MX) {
+        if (!wave) hipLaunchKernelGGL((k_align_part<K(), MX()>), gp, b, lds, st, a);
+        hipLaunchKernelGGL((k_align_fin<K(), MX()>), gf, b, lds, st, a);
+    });
 }
 
 // ===========================================================================
@@ -1778,36 +1665,10 @@ __global__ __launch_bounds__(kBlock) void k_resid_chi2(ResidArgs a) {
     __shared__ double red[kWaves * 4];
     const int N = a.nbin >> 1;
     const bool odd = a.nbin & 1;
-    const int KH = odd ? N + 1 : N;
     const int64_t row = blockIdx.x;
-    load_row(lds, a.in, a.dtype, row, a.nbin);
-    __syncthreads();
-    lds_fft_n<MX>(lds, rfft_len(a.nbin), a.T, false);
     double2 Xk[KMAX], Xn[KMAX];
-    const double ph = a.phases[row];
-#pragma unroll
-    for (int i = 0; i < KMAX; ++i) {
-        int k = threadIdx.x + i * kBlock;
-        if (k < KH) {
-            double2 X1 = cmul(rbin(lds, a.nbin, a.T2, k), cexp2pi((double)k * ph));
-            double2 X2 = cmk(0.0, 0.0);
-            if (!odd) X2 = cmul(rfft_bin(lds, N, a.T2, N - k), cexp2pi((double)(N - k) * ph));
-            if (k == 0) { X1.y = 0.0; X2.y = 0.0; }
-            Xk[i] = X1;
-            Xn[i] = X2;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < KMAX; ++i) {
-        int k = threadIdx.x + i * kBlock;
-        if (k < KH) {
-            if (odd) herm_put(lds, a.nbin, k, Xk[i]);
-            else lds[k] = irfft_prebin(Xk[i], Xn[i], a.T2[k]);
-        }
-    }
-    __syncthreads();
-    lds_fft_n<MX>(lds, rfft_len(a.nbin), a.T, true);
+    rotate_fwd<KMAX, MX>(lds, a.in, a.dtype, row, a.nbin, a.phases[row], a.T, a.T2, Xk, Xn);
+    harm_inv<KMAX, MX>(lds, a.nbin, a.T, a.T2, Xk, Xn);
     const double sc = 1.0 / (double)N, s = a.scales[row];
     const double *m = a.model + (int64_t)a.model_row[row] * a.nbin;
     double acc[1] = {0.0};
@@ -1830,39 +1691,33 @@ __global__ __launch_bounds__(kBlock) void k_resid_chi2(ResidArgs a) {
 hipError_t launch_resid_chi2(const ResidArgs &a, int64_t nrows, hipStream_t st) {
     size_t lds = (size_t)rfft_len(a.nbin) * sizeof(double2);
     dim3 g((unsigned)nrows), b(kBlock);
-    const bool mx = !is_pow2(rfft_len(a.nbin));
-    switch (kmax_pow2(a.nbin / 2 + (a.nbin & 1))) {
-        case 1: MXL(mx, k_resid_chi2, 1, g, b, lds, st, a); break;
-        case 2: MXL(mx, k_resid_chi2, 2, g, b, lds, st, a); break;
-        case 4: MXL(mx, k_resid_chi2, 4, g, b, lds, st, a); break;
-        case 8: MXL(mx, k_resid_chi2, 8, g, b, lds, st, a); break;
-        case 16: MXL(mx, k_resid_chi2, 16, g, b, lds, st, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_kmax_mx(a.nbin / 2 + (a.nbin & 1), !is_pow2(rfft_len(a.nbin)), [&](auto K, auto MX) {
+        hipLaunchKernelGGL((k_resid_chi2<K(), MX()>), g, b, lds, st, a);
+    });
 }
 
 hipError_t launch_noise(const NoiseArgs &a, int64_t nrows, hipStream_t st) {
     size_t lds = (size_t)rfft_len(a.nbin) * sizeof(double2);
-    if (is_pow2(rfft_len(a.nbin))) hipLaunchKernelGGL(k_noise<false>, dim3((unsigned)nrows), dim3(kBlock), lds, st, a);
-    else hipLaunchKernelGGL(k_noise<true>, dim3((unsigned)nrows), dim3(kBlock), lds, st, a);
+    dispatch_mx(!is_pow2(rfft_len(a.nbin)), [&](auto MX) {
+        hipLaunchKernelGGL(k_noise<MX()>, dim3((unsigned)nrows), dim3(kBlock), lds, st, a);
+    });
     return hipGetLastError();
 }
 hipError_t launch_phase_shift(const PhaseShiftArgs &a, int nprof, hipStream_t st) {
     size_t lds = (size_t)((a.Dspec ? 0 : rfft_len(a.nbin)) + a.nbin / 2 + 2) * sizeof(double2) +
                  (a.gsh ? 0 : (size_t)(a.Ns + 8) * sizeof(double));
-    if (a.gsh) {   // the brute grid in global memory
-        if (a.Dspec || is_pow2(rfft_len(a.nbin)))
-            hipLaunchKernelGGL((k_phase_shift<false, true>), dim3((unsigned)nprof), dim3(kBlock), lds, st, a);
-        else hipLaunchKernelGGL((k_phase_shift<true, true>), dim3((unsigned)nprof), dim3(kBlock), lds, st, a);
-    } else if (is_pow2(rfft_len(a.nbin))) hipLaunchKernelGGL(k_phase_shift<false>, dim3((unsigned)nprof), dim3(kBlock), lds, st, a);
-    else hipLaunchKernelGGL(k_phase_shift<true>, dim3((unsigned)nprof), dim3(kBlock), lds, st, a);
+    const dim3 g((unsigned)nprof), b(kBlock);
+    const bool mx = !is_pow2(rfft_len(a.nbin));
+    if (a.gsh)     // the brute grid in global memory
+        dispatch_mx(mx && !a.Dspec, [&](auto MX) { hipLaunchKernelGGL((k_phase_shift<MX(), true>), g, b, lds, st, a); });
+    else dispatch_mx(mx, [&](auto MX) { hipLaunchKernelGGL(k_phase_shift<MX()>, g, b, lds, st, a); });
     return hipGetLastError();
 }
 hipError_t launch_synth(const SynthArgs &a, hipStream_t st) {
     size_t lds = (size_t)rfft_len(a.nbin) * sizeof(double2);
-    if (is_pow2(rfft_len(a.nbin))) hipLaunchKernelGGL(k_synth<false>, dim3((unsigned)(a.nsub * a.nchan)), dim3(kBlock), lds, st, a);
-    else hipLaunchKernelGGL(k_synth<true>, dim3((unsigned)(a.nsub * a.nchan)), dim3(kBlock), lds, st, a);
+    dispatch_mx(!is_pow2(rfft_len(a.nbin)), [&](auto MX) {
+        hipLaunchKernelGGL(k_synth<MX()>, dim3((unsigned)(a.nsub * a.nchan)), dim3(kBlock), lds, st, a);
+    });
     return hipGetLastError();
 }
 
@@ -1968,12 +1823,9 @@ hipError_t launch_spline_port(const SplineArgs &a, hipStream_t st) {
     const int N0 = a.nbin_model >> 1, N1 = a.nbin >> 1;
     const int NM = N0 > N1 ? N0 : N1;
     const size_t lds = a.nbin == a.nbin_model ? 16 : (size_t)(NM + N1 + 1) * sizeof(double2);
-    if (is_pow2(N0) && is_pow2(N1))
-        hipLaunchKernelGGL(k_spline_port<false>, dim3((unsigned)((int64_t)a.nport * a.nchan)), dim3(kBlock),
-                           lds, st, a);
-    else
-        hipLaunchKernelGGL(k_spline_port<true>, dim3((unsigned)((int64_t)a.nport * a.nchan)), dim3(kBlock),
-                           lds, st, a);
+    dispatch_mx(!(is_pow2(N0) && is_pow2(N1)), [&](auto MX) {
+        hipLaunchKernelGGL(k_spline_port<MX()>, dim3((unsigned)((int64_t)a.nport * a.nchan)), dim3(kBlock), lds, st, a);
+    });
     return hipGetLastError();
 }
 

@@ -27,6 +27,7 @@
 
 #include "ppf_device.hpp"
 #include "ppf_internal.hpp"
+#include "ppf_launch.hpp"
 
 namespace ppf {
 
@@ -206,16 +207,14 @@ __global__ __launch_bounds__(kBlock) void k_spec_fit(NoiseFitArgs a) {
 
 hipError_t launch_noise_fit(const NoiseFitArgs &a, int64_t nrows, hipStream_t st) {
     const size_t lds = (size_t)rfft_len(a.nbin) * sizeof(double2) + (size_t)(a.nbin / 2 + 1) * sizeof(double);
-    const bool mx = !is_pow2(rfft_len(a.nbin));
-    const void *kern = mx ? reinterpret_cast<const void *>(k_noise_fit<true>)
-                          : reinterpret_cast<const void *>(k_noise_fit<false>);
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    if (mx) hipLaunchKernelGGL(k_noise_fit<true>, dim3((unsigned)nrows), dim3(kBlock), lds, st, a);
-    else hipLaunchKernelGGL(k_noise_fit<false>, dim3((unsigned)nrows), dim3(kBlock), lds, st, a);
-    return hipGetLastError();
+    hipError_t e = hipSuccess;
+    dispatch_mx(!is_pow2(rfft_len(a.nbin)), [&](auto MX) {
+        if (lds > 48 * 1024)
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_noise_fit<MX()>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess) hipLaunchKernelGGL(k_noise_fit<MX()>, dim3((unsigned)nrows), dim3(kBlock), lds, st, a);
+    });
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 hipError_t launch_spec_fit(const NoiseFitArgs &a, int64_t nrows, hipStream_t st) {

@@ -117,7 +117,7 @@ def dsum_kernel(nbin, nchan):
 
 
 def kmax(nbin):
-    """kmax_pow2(nbin / 2 + (nbin & 1)) (ppf_kernels.hip): the per-thread
+    """kmax_pow2(nbin / 2 + (nbin & 1)) (ppf_launch.hpp): the per-thread
     harmonic slots of the k_rotate, k_resid_chi2, k_inst_resp and
     k_gauss_port instantiation, the smallest power of two that holds
     ceil(harmonics / kBlock)."""

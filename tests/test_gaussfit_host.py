@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import gausshost as H
 import oracle as O
 from pulseportraiture_amd import _gaussfit, _lib, pplib
 
@@ -209,3 +210,28 @@ def test_gauss_lsq_validates_on_the_host():
     with pytest.raises(KeyError):
         engine.gauss_lsq("0x0", np.zeros((1, 8)), [0.0], [[1.0]], [1.0], [0],
                          [[1e-8]], np.zeros((1, 1, 64)), np.ones((1, 1, 64)))
+
+
+def test_plain_gauss_entry_points_pin_their_refusals():
+    """ppf_gauss_portrait_batch and ppf_gauss_lsq_batch: the code and the
+    ppf_last_error text of each refused call (gausshost.check).  The portrait
+    call looks at the context first, the least-squares call last."""
+    E, U, OK = _lib.PPF_EINVAL, _lib.PPF_EUNSUP, _lib.PPF_OK
+    digit = "model_code '0x0': digit 1 must be '0' or '1'"
+    span = "nbin=%d: even lengths in [32, 8192] (the LDS row transforms)"
+    H.check("port", E, digit, code=b"0x0")
+    H.check("port", E, "model_code is NULL", code=None)
+    H.check("port", U, "nbin=31 unsupported", null_rc=E, nbin=31)
+    # 8194 bins are long rows to the portrait builder: an empty batch is fine
+    ctx = H.live_context()
+    assert H.call("port", ctx, nrow=0, nbin=8194)[0] == (E if ctx is None else OK)
+    H.check("lsq", E, digit, code=b"0x0")
+    H.check("lsq", E, "model_code is NULL", code=None)
+    for nbin in (31, 33, 8194):
+        H.check("lsq", U, span % nbin, nbin=nbin)
+    H.check("lsq", U, "nfree=128: at most 127 free parameters", nfree=128,
+            free_idx=range(128), delta=[1.0] * 128, ngauss=30)
+    H.check("lsq", E, "free_idx[1] = 2: strictly increasing in [0, 8]",
+            free_idx=(2, 2))
+    H.check("lsq", E, "delta[0][1] = 0: a finite non-zero step",
+            delta=(1e-8, 0.0))

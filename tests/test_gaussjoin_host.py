@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import gausshost as H
 import joincases as J
 import oracle as O
 from pulseportraiture_amd import _gaussfit, _lib, pplib
@@ -264,3 +265,29 @@ def test_metafile_of_missing_or_foreign_archives_is_refused(tmp_path):
         pplib.DataPortrait(str(meta))
     with pytest.raises(NotImplementedError):       # ppspline joins: not built
         ppspline.DataPortrait(_three())
+
+
+@pytest.mark.parametrize("entry", ["port_join", "lsq_join"])
+def test_joined_gauss_entry_points_pin_their_refusals(entry):
+    """The code and the ppf_last_error text of each refused call
+    (gausshost.check), two archives joined unless said otherwise."""
+    E, U = _lib.PPF_EINVAL, _lib.PPF_EUNSUP
+    digit = "model_code '0x0': digit 1 must be '0' or '1'"
+    H.check(entry, E, digit, code=b"0x0")
+    H.check(entry, E, digit, code=b"0x0", njoin=0, join_id=(-1, -1))
+    H.check(entry, E, "model_code is NULL", code=None)
+    H.check(entry, E, "njoin=-1", njoin=-1)
+    H.check(entry, E, "join_id[1] = 2: -1 or an archive in [0, 2)",
+            join_id=(0, 2))
+    for nbin in (31, 33, 8194):
+        H.check(entry, U, "nbin=%d: even lengths in [32, 8192] (the LDS row "
+                "transforms)" % nbin, nbin=nbin)
+    if entry == "port_join":
+        return
+    H.check(entry, U, "nfree=128: at most 127 free parameters", nfree=128,
+            free_idx=range(128), delta=[1.0] * 128, ngauss=30)
+    # the scattering index is entry npar + 2 njoin = 12 of the free indices
+    H.check(entry, E, "free_idx[1] = 2: strictly increasing in [0, 12]",
+            free_idx=(2, 2))
+    H.check(entry, E, "delta[0][1] = 0: a finite non-zero step",
+            delta=(1e-8, 0.0))
