@@ -160,6 +160,49 @@ __device__ __forceinline__ double readlane_d(double v, int l) {
     return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
 }
 
+// XCD-aware block -> (sub-int, channel block) of the spectrum pass: blocks b
+// and b+8 share an XCD, so each XCD keeps only its channel blocks' model rows
+// in its L2.  Mode 1 walks an XCD's channel blocks sub-int by sub-int (a model
+// larger than the L2s is then re-read for every sub-int: 134 MB per C5
+// sub-int); mode 2 walks every sub-int (of nsub) for one channel block before
+// the next, so the workgroups resident on an XCD share one block of model
+// rows.  (The block-FFT kernels know mode 1 only: they pass xcd_swizzle != 0.)
+__device__ __forceinline__ void block_map(int xcd_swizzle, int nblk, int &s, int &cb, int nsub = 0) {
+    if (xcd_swizzle == 2) {
+        const int per = nblk / 8, x = blockIdx.x % 8, r = blockIdx.x / 8;
+        cb = x * per + r / nsub;
+        s = r % nsub;
+    } else if (xcd_swizzle) {
+        const int per = nblk / 8, x = blockIdx.x % 8, r = blockIdx.x / 8;
+        cb = x * per + r % per;
+        s = r / per;
+    } else {
+        s = blockIdx.x / nblk;
+        cb = blockIdx.x % nblk;
+    }
+}
+
+// What the spectrum pass leaves per channel row, chan[4]: errs_FT = sigma_n
+// sqrt(nbin / 2) from the given sigma err (given) or from pn, the power at
+// harmonics >= kc (get_noise_PS, pplib.py:2312-2332), and 1 / errs_FT^2,
+// which also scales the row's X; then store() with pd = sum_{k>=1} |D_k|^2
+// and mpow = sum_{k>=1} |M_k|^2.
+struct RowScale {
+    double errs_FT, inv_e2;
+    __device__ __forceinline__ RowScale(double pn, bool given, double err, int NH, int kc, int nbin) {
+        const double sqrt_half_nbin = sqrt((double)nbin / 2.0);
+        if (given) errs_FT = err * sqrt_half_nbin;
+        else errs_FT = sqrt(pn / (double)(NH - kc) / (double)nbin) * sqrt_half_nbin;
+        inv_e2 = 1.0 / (errs_FT * errs_FT);
+    }
+    __device__ __forceinline__ void store(double *chan, double pd, double mpow) const {
+        chan[0] = errs_FT;
+        chan[1] = inv_e2;
+        chan[2] = pd * inv_e2;        // Sd_n
+        chan[3] = mpow * inv_e2;      // S_n at tau = 0
+    }
+};
+
 // wave-scope ordering of LDS traffic (no hardware barrier: a wave's LDS
 // operations are processed in issue order; this keeps the compiler from
 // moving them across the exchange point)

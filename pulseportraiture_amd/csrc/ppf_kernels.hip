@@ -73,21 +73,11 @@ __global__ __launch_bounds__(kBlock) void k_xspec(XspecArgs a) {
     }
     const double2 *T = TWL ? lds + N : a.T;
     const double2 *T2 = TWL ? lds + 2 * N : a.T2;
-    // XCD-aware block -> (sub-int, channel block): blocks b and b+8 share an
-    // XCD, so each XCD keeps only its channel blocks' model rows in its L2
     int s, cb;
-    if (a.xcd_swizzle) {
-        const int per = a.nblk / 8, x = blockIdx.x % 8, r = blockIdx.x / 8;
-        cb = x * per + r % per;
-        s = r / per;
-    } else {
-        s = blockIdx.x / a.nblk;
-        cb = blockIdx.x % a.nblk;
-    }
+    block_map(a.xcd_swizzle != 0, a.nblk, s, cb);     // (mode 1 only)
     const int c0 = cb * a.cb, c1 = min(a.nchan, c0 + a.cb);
     const int mi = a.model_index ? a.model_index[s] : 0;
     const uint8_t *mask = a.mask ? a.mask + (int64_t)s * a.nchan : nullptr;
-    const double sqrt_half_nbin = sqrt((double)(2 * N) / 2.0);
     const RowT *rows = reinterpret_cast<const RowT *>(a.data);
 
     auto skip_masked = [&](int n) {
@@ -139,10 +129,7 @@ __global__ __launch_bounds__(kBlock) void k_xspec(XspecArgs a) {
             }
         }
         block_sum<2>(acc, red);                 // buf is not modified here
-        double errs_FT;
-        if (a.errs) errs_FT = a.errs[crow] * sqrt_half_nbin;
-        else errs_FT = sqrt(acc[0] / (double)(NH - a.kc) / (double)(2 * N)) * sqrt_half_nbin;
-        const double inv_e2 = 1.0 / (errs_FT * errs_FT);
+        const RowScale rs(acc[0], a.errs != nullptr, a.errs ? a.errs[crow] : 0.0, NH, a.kc, 2 * N);
         double2 *Xrow = a.X + (int64_t)(a.xslot ? a.xslot[s] : s) * NH * a.nchan + n;   // X[slot][k][n]
         const int64_t xs = a.nchan;
         double mpow[1] = {0.0};
@@ -156,87 +143,85 @@ __global__ __launch_bounds__(kBlock) void k_xspec(XspecArgs a) {
                     Xrow[0] = cmk(0.0, 0.0);       // F0_fact = 0 (pplib.py:82)
                 } else {
                     mpow[0] += cabs2(M);
-                    Xrow[k * xs] = cscale(cmulc(rfft_bin(buf, N, T2, k), M), inv_e2);
+                    Xrow[k * xs] = cscale(cmulc(rfft_bin(buf, N, T2, k), M), rs.inv_e2);
                 }
             }
         }
         block_sum<1>(mpow, red);
-        if (tid == 0) {
-            double *chan = a.chan + crow * 4;
-            chan[0] = errs_FT;
-            chan[1] = inv_e2;
-            chan[2] = acc[1] * inv_e2;     // Sd_n
-            chan[3] = mpow[0] * inv_e2;    // S_n at tau = 0
-        }
+        if (tid == 0) rs.store(a.chan + crow * 4, acc[1], mpow[0]);
         n = nn;
     }
 }
 
 // ===========================================================================
 // k_xspec_any: k_xspec for nbin / 2 not a power of two (mixed-radix LDS FFT,
-// lds_fft_n): the same per-row arithmetic, rows loaded straight into LDS
+// lds_fft_n): the same per-row arithmetic, rows loaded straight into LDS.
+// k_xspec_spec: the same on rows whose rFFT was taken beforehand (a.spec, the
+// long-row transforms of ppf_longfft.hip: even nbin > 8192, odd > 4095;
+// round 6) -- noise, Sd_n, S_n and X from the stored bins, no LDS transform
+// and no swizzle.  One body: prep(crow) readies the row, bin(crow, k) reads
+// its bin k.  (As callables: with a bool template argument instead, the
+// compiler stopped inlining lds_fft into every kernel of this file.)
 // ===========================================================================
-template <int DT>
-__global__ __launch_bounds__(kBlock) void k_xspec_any(XspecArgs a) {
-    extern __shared__ __attribute__((aligned(16))) double2 lds[];
-    __shared__ double red[kWaves * 4];
+template <class Prep, class Bin>
+__device__ __forceinline__ void xspec_rows_body(const XspecArgs &a, int swz, double *red, Prep &&prep, Bin &&bin) {
     const int N = a.nbin >> 1, NH = N + 1;
     const int tid = threadIdx.x;
     int s, cb;
-    if (a.xcd_swizzle) {
-        const int per = a.nblk / 8, x = blockIdx.x % 8, r = blockIdx.x / 8;
-        cb = x * per + r % per;
-        s = r / per;
-    } else {
-        s = blockIdx.x / a.nblk;
-        cb = blockIdx.x % a.nblk;
-    }
+    block_map(swz, a.nblk, s, cb);
     if (a.needx && !a.needx[s]) return;
     const int c0 = cb * a.cb, c1 = min(a.nchan, c0 + a.cb);
     const int mi = a.model_index ? a.model_index[s] : 0;
     const uint8_t *mask = a.mask ? a.mask + (int64_t)s * a.nchan : nullptr;
-    const double sqrt_half_nbin = sqrt((double)a.nbin / 2.0);
     for (int n = c0; n < c1; ++n) {
         const int64_t crow = (int64_t)s * a.nchan + n;
         if (mask && !mask[n]) {
             if (tid < 4) a.chan[crow * 4 + tid] = 0.0;
             continue;
         }
-        load_row(lds, a.data, DT, crow, a.nbin);
-        __syncthreads();
-        lds_fft_n(lds, rfft_len(a.nbin), a.T, false);
+        prep(crow);
         double acc[2] = {0.0, 0.0};
         for (int k = tid; k <= N; k += kBlock) {
-            const double p2 = cabs2(rbin(lds, a.nbin, a.T2, k));
+            const double p2 = cabs2(bin(crow, k));
             if (k >= a.kc) acc[0] += p2;
             if (k >= 1) acc[1] += p2;
         }
         block_sum<2>(acc, red);
-        double errs_FT;
-        if (a.errs) errs_FT = a.errs[crow] * sqrt_half_nbin;
-        else errs_FT = sqrt(acc[0] / (double)(NH - a.kc) / (double)a.nbin) * sqrt_half_nbin;
-        const double inv_e2 = 1.0 / (errs_FT * errs_FT);
+        const RowScale rs(acc[0], a.errs != nullptr, a.errs ? a.errs[crow] : 0.0, NH, a.kc, a.nbin);
         double2 *Xrow = a.X + (int64_t)(a.xslot ? a.xslot[s] : s) * NH * a.nchan + n;
         const double2 *Mrow = a.Mft + ((int64_t)mi * a.nchan + n) * NH;
         double mpow[1] = {0.0};
         for (int k = tid; k <= N; k += kBlock) {
             if (k == 0) {
-                Xrow[0] = cmk(0.0, 0.0);
+                Xrow[0] = cmk(0.0, 0.0);       // F0_fact = 0 (pplib.py:82)
             } else {
                 const double2 M = Mrow[k];
                 mpow[0] += cabs2(M);
-                Xrow[(int64_t)k * a.nchan] = cscale(cmulc(rbin(lds, a.nbin, a.T2, k), M), inv_e2);
+                Xrow[(int64_t)k * a.nchan] = cscale(cmulc(bin(crow, k), M), rs.inv_e2);
             }
         }
         block_sum<1>(mpow, red);          // (its barriers also end this row's reads)
-        if (tid == 0) {
-            double *chan = a.chan + crow * 4;
-            chan[0] = errs_FT;
-            chan[1] = inv_e2;
-            chan[2] = acc[1] * inv_e2;
-            chan[3] = mpow[0] * inv_e2;
-        }
+        if (tid == 0) rs.store(a.chan + crow * 4, acc[1], mpow[0]);
     }
+}
+
+template <int DT>
+__global__ __launch_bounds__(kBlock) void k_xspec_any(XspecArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double2 lds[];
+    __shared__ double red[kWaves * 4];
+    xspec_rows_body(a, a.xcd_swizzle != 0, red,
+                    [&](int64_t crow) {
+                        load_row(lds, a.data, DT, crow, a.nbin);
+                        __syncthreads();
+                        lds_fft_n(lds, rfft_len(a.nbin), a.T, false);
+                    },
+                    [&](int64_t, int k) { return rbin(lds, a.nbin, a.T2, k); });
+}
+
+__global__ __launch_bounds__(kBlock) void k_xspec_spec(XspecArgs a) {
+    __shared__ double red[kWaves * 4];
+    const int NH = (a.nbin >> 1) + 1;
+    xspec_rows_body(a, 0, red, [](int64_t) {}, [&](int64_t crow, int k) { return a.spec[crow * NH + k]; });
 }
 
 // the guess profiles of long rows: prof[s][t] = sum_b gP[s][b][t] (the
@@ -254,63 +239,6 @@ hipError_t launch_gsum(int nsub, int nblkd, int nbin, const double *gP, double *
     hipLaunchKernelGGL(k_gsum, dim3((unsigned)((nbin + kBlock - 1) / kBlock), (unsigned)nsub), dim3(kBlock), 0,
                        st, nblkd, nbin, gP, prof);
     return hipGetLastError();
-}
-
-// ===========================================================================
-// k_xspec_spec: k_xspec_any's per-row arithmetic on rows whose rFFT was
-// taken beforehand (a.spec, the long-row transforms of ppf_longfft.hip:
-// even nbin > 8192, odd > 4095; round 6) -- noise, Sd_n, S_n and X from the
-// stored bins, no LDS transform
-// ===========================================================================
-__global__ __launch_bounds__(kBlock) void k_xspec_spec(XspecArgs a) {
-    __shared__ double red[kWaves * 4];
-    const int N = a.nbin >> 1, NH = N + 1;
-    const int tid = threadIdx.x;
-    const int s = blockIdx.x / a.nblk, cb = blockIdx.x % a.nblk;
-    if (a.needx && !a.needx[s]) return;
-    const int c0 = cb * a.cb, c1 = min(a.nchan, c0 + a.cb);
-    const int mi = a.model_index ? a.model_index[s] : 0;
-    const uint8_t *mask = a.mask ? a.mask + (int64_t)s * a.nchan : nullptr;
-    const double sqrt_half_nbin = sqrt((double)a.nbin / 2.0);
-    for (int n = c0; n < c1; ++n) {
-        const int64_t crow = (int64_t)s * a.nchan + n;
-        if (mask && !mask[n]) {
-            if (tid < 4) a.chan[crow * 4 + tid] = 0.0;
-            continue;
-        }
-        const double2 *D = a.spec + crow * NH;
-        double acc[2] = {0.0, 0.0};
-        for (int k = tid; k <= N; k += kBlock) {
-            const double p2 = cabs2(D[k]);
-            if (k >= a.kc) acc[0] += p2;
-            if (k >= 1) acc[1] += p2;
-        }
-        block_sum<2>(acc, red);
-        double errs_FT;
-        if (a.errs) errs_FT = a.errs[crow] * sqrt_half_nbin;
-        else errs_FT = sqrt(acc[0] / (double)(NH - a.kc) / (double)a.nbin) * sqrt_half_nbin;
-        const double inv_e2 = 1.0 / (errs_FT * errs_FT);
-        double2 *Xrow = a.X + (int64_t)(a.xslot ? a.xslot[s] : s) * NH * a.nchan + n;
-        const double2 *Mrow = a.Mft + ((int64_t)mi * a.nchan + n) * NH;
-        double mpow[1] = {0.0};
-        for (int k = tid; k <= N; k += kBlock) {
-            if (k == 0) {
-                Xrow[0] = cmk(0.0, 0.0);
-            } else {
-                const double2 M = Mrow[k];
-                mpow[0] += cabs2(M);
-                Xrow[(int64_t)k * a.nchan] = cscale(cmulc(D[k], M), inv_e2);
-            }
-        }
-        block_sum<1>(mpow, red);
-        if (tid == 0) {
-            double *chan = a.chan + crow * 4;
-            chan[0] = errs_FT;
-            chan[1] = inv_e2;
-            chan[2] = acc[1] * inv_e2;
-            chan[3] = mpow[0] * inv_e2;
-        }
-    }
 }
 
 hipError_t launch_xspec_spec(const XspecArgs &a, hipStream_t st) {
@@ -1347,38 +1275,20 @@ hipError_t launch_rfft_rows(const RfftArgs &a, int64_t nrows, hipStream_t st) {
     });
     return hipGetLastError();
 }
-template <int L2>
-static void launch_xspec_t(const XspecArgs &a, hipStream_t st) {
-    constexpr int N = 1 << L2;
-    size_t lds = (size_t)N * sizeof(double2) * (N <= 1024 ? 3 : 1);
-    dim3 g((unsigned)((int64_t)a.nsub * a.nblk)), b(kBlock);
-    if (a.dtype == 0) hipLaunchKernelGGL((k_xspec<L2, 0>), g, b, lds, st, a);
-    else hipLaunchKernelGGL((k_xspec<L2, 1>), g, b, lds, st, a);
-}
-
 hipError_t launch_xspec(const XspecArgs &a, hipStream_t st) {
-    switch (a.log2N) {
-        case 4: launch_xspec_t<4>(a, st); break;
-        case 5: launch_xspec_t<5>(a, st); break;
-        case 6: launch_xspec_t<6>(a, st); break;
-        case 7: launch_xspec_t<7>(a, st); break;
-        case 8: launch_xspec_t<8>(a, st); break;
-        case 9: launch_xspec_t<9>(a, st); break;
-        case 10: launch_xspec_t<10>(a, st); break;
-        case 11: launch_xspec_t<11>(a, st); break;
-        case 12: launch_xspec_t<12>(a, st); break;
-        case 0: {      // nbin / 2 not a power of two
-            // wave per row (k_xspec_wm) up to N = 1024; the block kernel above
-            if (xspec_wm_supported(a.nbin) && a.cb <= 64) return launch_xspec_wm(a, st);
-            dim3 g((unsigned)((int64_t)a.nsub * a.nblk)), b(kBlock);
-            const size_t lds = (size_t)rfft_len(a.nbin) * sizeof(double2);
-            if (a.dtype == 0) hipLaunchKernelGGL((k_xspec_any<0>), g, b, lds, st, a);
-            else hipLaunchKernelGGL((k_xspec_any<1>), g, b, lds, st, a);
-            break;
-        }
-        default: return hipErrorInvalidValue;
+    dim3 g((unsigned)((int64_t)a.nsub * a.nblk)), b(kBlock);
+    if (a.log2N == 0) {      // nbin / 2 not a power of two
+        // wave per row (k_xspec_wm) up to N = 1024; the block kernel above
+        if (xspec_wm_supported(a.nbin) && a.cb <= 64) return launch_xspec_wm(a, st);
+        const size_t lds = (size_t)rfft_len(a.nbin) * sizeof(double2);
+        dispatch_dt(a.dtype, [&](auto DT) { hipLaunchKernelGGL((k_xspec_any<DT()>), g, b, lds, st, a); });
+        return hipGetLastError();
     }
-    return hipGetLastError();
+    return dispatch_log2n_dt<4, 12>(a.log2N, a.dtype, [&](auto L2, auto DT) {
+        constexpr int N = 1 << L2();
+        const size_t lds = (size_t)N * sizeof(double2) * (N <= 1024 ? 3 : 1);
+        hipLaunchKernelGGL((k_xspec<L2(), DT()>), g, b, lds, st, a);
+    });
 }
 bool dsum_wave_supported(int nbin) { return nbin >= 256 && nbin <= 2048 && is_pow2(nbin); }
 
@@ -1402,47 +1312,26 @@ hipError_t launch_dsum(const DsumArgs &a_in, hipStream_t st) {
     } else {
         a.nuref = nullptr;
     }
-    if (dsum_wave_supported(a.nbin)) {
-        switch (__builtin_ctz((unsigned)a.nbin) * 2 + a.dtype) {
-            case 16: launch_dsum_w<0, 8>(a, st); break;
-            case 17: launch_dsum_w<1, 8>(a, st); break;
-            case 18: launch_dsum_w<0, 9>(a, st); break;
-            case 19: launch_dsum_w<1, 9>(a, st); break;
-            case 20: launch_dsum_w<0, 10>(a, st); break;
-            case 21: launch_dsum_w<1, 10>(a, st); break;
-            case 22: launch_dsum_w<0, 11>(a, st); break;
-            case 23: launch_dsum_w<1, 11>(a, st); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
+    if (dsum_wave_supported(a.nbin))
+        return dispatch_log2n_dt<8, 11>(__builtin_ctz((unsigned)a.nbin), a.dtype,
+                                        [&](auto L2, auto DT) { launch_dsum_w<DT(), L2()>(a, st); });
     dim3 g((unsigned)((int64_t)a.nsub * a.nblkd)), b(kBlock);
-    if (a.nbin <= 2048 && a.cbd <= 128) {
-        // wave-per-row pass at the other nbin <= 2048 (k_dsum_wn), NBMAX 1024 or 2048
-        const int nbm = a.nbin <= 1024 ? 1024 : 2048;
-        const size_t row = (size_t)kWaves * nbm * (a.dtype == 0 ? 4 : 8);
-        const size_t lds = row > (size_t)nbm * 8 ? row : (size_t)nbm * 8;
-        if (nbm == 1024) {
-            if (a.dtype == 0) hipLaunchKernelGGL((k_dsum_wn<0, 1024>), g, b, lds, st, a);
-            else hipLaunchKernelGGL((k_dsum_wn<1, 1024>), g, b, lds, st, a);
-        } else {
-            if (a.dtype == 0) hipLaunchKernelGGL((k_dsum_wn<0, 2048>), g, b, lds, st, a);
-            else hipLaunchKernelGGL((k_dsum_wn<1, 2048>), g, b, lds, st, a);
+    dispatch_dt(a.dtype, [&](auto DT) {
+        if (a.nbin <= 2048 && a.cbd <= 128) {
+            // wave-per-row pass at the other nbin <= 2048 (k_dsum_wn), NBMAX 1024 or 2048
+            const int nbm = a.nbin <= 1024 ? 1024 : 2048;
+            const size_t row = (size_t)kWaves * nbm * (DT() == 0 ? 4 : 8);
+            const size_t lds = row > (size_t)nbm * 8 ? row : (size_t)nbm * 8;
+            if (nbm == 1024) hipLaunchKernelGGL((k_dsum_wn<DT(), 1024>), g, b, lds, st, a);
+            else hipLaunchKernelGGL((k_dsum_wn<DT(), 2048>), g, b, lds, st, a);
+            return;
         }
-        return hipGetLastError();
-    }
-    const int jb = a.nbin >= 2048 ? 8 : (a.nbin + kBlock - 1) / kBlock;
-    if (a.dtype == 0) {
-        if (jb >= 8) hipLaunchKernelGGL((k_dsum<0, 8>), g, b, 0, st, a);
-        else if (jb >= 4) hipLaunchKernelGGL((k_dsum<0, 4>), g, b, 0, st, a);
-        else if (jb >= 2) hipLaunchKernelGGL((k_dsum<0, 2>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((k_dsum<0, 1>), g, b, 0, st, a);
-    } else {
-        if (jb >= 8) hipLaunchKernelGGL((k_dsum<1, 8>), g, b, 0, st, a);
-        else if (jb >= 4) hipLaunchKernelGGL((k_dsum<1, 4>), g, b, 0, st, a);
-        else if (jb >= 2) hipLaunchKernelGGL((k_dsum<1, 2>), g, b, 0, st, a);
-        else hipLaunchKernelGGL((k_dsum<1, 1>), g, b, 0, st, a);
-    }
+        const int jb = a.nbin >= 2048 ? 8 : (a.nbin + kBlock - 1) / kBlock;
+        if (jb >= 8) hipLaunchKernelGGL((k_dsum<DT(), 8>), g, b, 0, st, a);
+        else if (jb >= 4) hipLaunchKernelGGL((k_dsum<DT(), 4>), g, b, 0, st, a);
+        else if (jb >= 2) hipLaunchKernelGGL((k_dsum<DT(), 2>), g, b, 0, st, a);
+        else hipLaunchKernelGGL((k_dsum<DT(), 1>), g, b, 0, st, a);
+    });
     return hipGetLastError();
 }
 

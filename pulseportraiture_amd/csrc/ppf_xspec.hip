@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "ppf_internal.hpp"
+#include "ppf_launch.hpp"
 #include "ppf_state.hpp"
 #include "ppf_wfft.hpp"
 #include "ppf_wfft2.hpp"
@@ -54,27 +55,6 @@ typedef double vd2 __attribute__((ext_vector_type(2)));
 typedef float vf4 __attribute__((ext_vector_type(4)));
 // scheduling fence: nothing is moved across it
 #define SCHED_CUT() __builtin_amdgcn_sched_barrier(0)
-
-// XCD-aware block -> (sub-int, channel block): blocks b and b+8 share an
-// XCD, so each XCD keeps only its channel blocks' model rows in its L2.
-// Mode 1 walks an XCD's channel blocks sub-int by sub-int (a model larger
-// than the L2s is then re-read for every sub-int: 134 MB per C5 sub-int);
-// mode 2 walks every sub-int (of nsub) for one channel block before the next,
-// so the workgroups resident on an XCD share one block of model rows.
-__device__ __forceinline__ void block_map(int xcd_swizzle, int nblk, int &s, int &cb, int nsub = 0) {
-    if (xcd_swizzle == 2) {
-        const int per = nblk / 8, x = blockIdx.x % 8, r = blockIdx.x / 8;
-        cb = x * per + r / nsub;
-        s = r % nsub;
-    } else if (xcd_swizzle) {
-        const int per = nblk / 8, x = blockIdx.x % 8, r = blockIdx.x / 8;
-        cb = x * per + r % per;
-        s = r / per;
-    } else {
-        s = blockIdx.x / nblk;
-        cb = blockIdx.x % nblk;
-    }
-}
 
 // real-FFT post-pass of the pair (k, N-k), k = lane + 64 i, from the wave's
 // LDS spectrum; w = exp(-i pi k / N)
@@ -104,6 +84,11 @@ __host__ __device__ constexpr int tw_slots() {
 // wave's next row is already in flight during the FFT, and vmcnt counts in
 // order, so a twiddle load issued after that prefetch would wait for it
 // (the s_waitcnt vmcnt(0) before every stage's first twiddle use).
+// (the caller's next barrier publishes the copy)
+template <int LOG2N, int NTHREADS>
+__device__ __forceinline__ void stage_twiddles(double2 *twl, const double2 *T) {
+    for (int i = threadIdx.x; i < tw_slots<LOG2N>(); i += NTHREADS) twl[i] = T[i];
+}
 // wave buffer + 2 side slots
 template <int LOG2N>
 __host__ __device__ constexpr int xspec_slw() { return wfft::buf_slots<LOG2N>() + 2; }
@@ -136,7 +121,7 @@ void k_xspec_w(XspecArgs a) {
     block_map(a.xcd_swizzle, a.nblk, s, cb, a.nsub);
     if (a.needx && !a.needx[s]) return;               // uniform: moment-mode sub-int (or no slot)
     double2 *twl = lds + kXSW * SL;
-    for (int i = threadIdx.x; i < tw_slots<LOG2N>(); i += 64 * kXSW) twl[i] = a.T[i];
+    stage_twiddles<LOG2N, 64 * kXSW>(twl, a.T);
     __syncthreads();
     const double2 *tw = twl;
     // rounds: in round r wave w takes channel cb*CB + r*kXSW + w
@@ -360,7 +345,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void k
     constexpr int SIDE2 = SLW - 2;     // 1/sigma~_n^2 of the row (.x)
     constexpr int KPW = N / 2 / XW;    // folded harmonics (MFMA K) per wave
     constexpr int MPT = (NH + 511) / 512;   // model-row elements per thread
-    constexpr int TWN = tw_slots<LOG2N>();
     using ElT = typename std::conditional<DT == 0, float, double>::type;
     // data rows move as 16-B vectors: VE elements per load, NLD loads per lane
     using VecT = typename std::conditional<DT == 0, vf4, vd2>::type;
@@ -370,7 +354,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void k
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double2 *buf = lds + wave * SLW;
     double2 *mrow = lds + XW * SLW;    // model row M_n[0..N], [NH] = (sum |M|^2, 0)
-    double2 *tw = mrow + NH + 1;       // FFT twiddles T[0..TWN)
+    double2 *tw = mrow + NH + 1;       // FFT twiddles T[0..tw_slots))
 
     int g, cb;
     block_map(a.xcd_swizzle, a.nblk, g, cb);
@@ -482,7 +466,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void k
         return act && n < cend && __builtin_amdgcn_readlane(ch_use, n - cbase) != 0;
     };
 
-    for (int i = tid; i < TWN; i += 512) tw[i] = a.T[i];
+    stage_twiddles<LOG2N, 512>(tw, a.T);
     int n = cbase;
     mload(n);
     mstore();
@@ -1684,25 +1668,17 @@ bool xspec_wm_supported(int nbin) {
 hipError_t launch_xspec_wm(const XspecArgs &a, hipStream_t st) {
     const int NF = rfft_len(a.nbin);
     dim3 g((unsigned)((int64_t)a.nsub * a.nblk)), b(64 * kWmW);
-    if (a.nbin & 1) {
-        const size_t lds = ((size_t)kWmW * (NF + 1) + NF) * sizeof(double2);
-        if (NF <= 512) {
-            if (a.dtype == 0) hipLaunchKernelGGL((k_xspec_wo<0, 512>), g, b, lds, st, a);
-            else hipLaunchKernelGGL((k_xspec_wo<1, 512>), g, b, lds, st, a);
+    dispatch_dt(a.dtype, [&](auto DT) {
+        if (a.nbin & 1) {
+            const size_t lds = ((size_t)kWmW * (NF + 1) + NF) * sizeof(double2);
+            if (NF <= 512) hipLaunchKernelGGL((k_xspec_wo<DT(), 512>), g, b, lds, st, a);
+            else hipLaunchKernelGGL((k_xspec_wo<DT(), 1024>), g, b, lds, st, a);
         } else {
-            if (a.dtype == 0) hipLaunchKernelGGL((k_xspec_wo<0, 1024>), g, b, lds, st, a);
-            else hipLaunchKernelGGL((k_xspec_wo<1, 1024>), g, b, lds, st, a);
+            const size_t lds = ((size_t)kWmW * (NF + 2) + NF) * sizeof(double2);
+            if (NF <= 512) hipLaunchKernelGGL((k_xspec_wm<DT(), 512>), g, b, lds, st, a);
+            else hipLaunchKernelGGL((k_xspec_wm<DT(), 1024>), g, b, lds, st, a);
         }
-        return hipGetLastError();
-    }
-    const size_t lds = ((size_t)kWmW * (NF + 2) + NF) * sizeof(double2);
-    if (NF <= 512) {
-        if (a.dtype == 0) hipLaunchKernelGGL((k_xspec_wm<0, 512>), g, b, lds, st, a);
-        else hipLaunchKernelGGL((k_xspec_wm<1, 512>), g, b, lds, st, a);
-    } else {
-        if (a.dtype == 0) hipLaunchKernelGGL((k_xspec_wm<0, 1024>), g, b, lds, st, a);
-        else hipLaunchKernelGGL((k_xspec_wm<1, 1024>), g, b, lds, st, a);
-    }
+    });
     return hipGetLastError();
 }
 
@@ -1755,18 +1731,7 @@ bool xspec_wave_supported(int log2N, int cb) {
 }
 
 hipError_t launch_xspec_wave(const XspecArgs &a, hipStream_t st) {
-    switch (a.log2N * 2 + a.dtype) {
-        case 14: launch_w<7, 0>(a, st); break;
-        case 15: launch_w<7, 1>(a, st); break;
-        case 16: launch_w<8, 0>(a, st); break;
-        case 17: launch_w<8, 1>(a, st); break;
-        case 18: launch_w<9, 0>(a, st); break;
-        case 19: launch_w<9, 1>(a, st); break;
-        case 20: launch_w<10, 0>(a, st); break;
-        case 21: launch_w<10, 1>(a, st); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_log2n_dt<7, 10>(a.log2N, a.dtype, [&](auto L2, auto DT) { launch_w<L2(), DT()>(a, st); });
 }
 
 // ===========================================================================
@@ -1789,7 +1754,7 @@ __global__ __launch_bounds__(64 * kNoiseW) void k_noise_w(NoiseArgs a, int64_t n
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double2 *buf = lds + wave * SL;
     double2 *tw = lds + kNoiseW * SL;
-    for (int i = threadIdx.x; i < tw_slots<LOG2N>(); i += 64 * kNoiseW) tw[i] = a.T[i];
+    stage_twiddles<LOG2N, 64 * kNoiseW>(tw, a.T);
     __syncthreads();
     const double2 w_seed = a.T2[lane], w_step = a.T2[64];
     const RowT *rows = reinterpret_cast<const RowT *>(a.in);
@@ -1837,18 +1802,7 @@ static void launch_nw(const NoiseArgs &a, int64_t nrows, hipStream_t st) {
 bool noise_wave_supported(int log2N) { return log2N >= 7 && log2N <= 10; }
 
 hipError_t launch_noise_wave(const NoiseArgs &a, int64_t nrows, hipStream_t st) {
-    switch (a.log2N * 2 + a.dtype) {
-        case 14: launch_nw<7, 0>(a, nrows, st); break;
-        case 15: launch_nw<7, 1>(a, nrows, st); break;
-        case 16: launch_nw<8, 0>(a, nrows, st); break;
-        case 17: launch_nw<8, 1>(a, nrows, st); break;
-        case 18: launch_nw<9, 0>(a, nrows, st); break;
-        case 19: launch_nw<9, 1>(a, nrows, st); break;
-        case 20: launch_nw<10, 0>(a, nrows, st); break;
-        case 21: launch_nw<10, 1>(a, nrows, st); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_log2n_dt<7, 10>(a.log2N, a.dtype, [&](auto L2, auto DT) { launch_nw<L2(), DT()>(a, nrows, st); });
 }
 
 // ===========================================================================
@@ -1877,7 +1831,7 @@ __global__ __launch_bounds__(64 * kXW) void k_align_part_w(AlignArgs a) {
     const double2 w_seed = a.T2[lane], w_step = a.T2[64];
     const RowT *rows = reinterpret_cast<const RowT *>(a.in);
     double2 *twl = lds + kXW * SL;
-    for (int i = threadIdx.x; i < tw_slots<LOG2N>(); i += 64 * kXW) twl[i] = a.T[i];
+    stage_twiddles<LOG2N, 64 * kXW>(twl, a.T);
     __syncthreads();
     const double2 *tw = twl;
     double2 Alo[NP], Ahi[NP], Am = cmk(0.0, 0.0);
@@ -1966,18 +1920,7 @@ static void launch_align_w_t(const AlignArgs &a, hipStream_t st) {
 bool align_wave_supported(int log2N) { return log2N >= 7 && log2N <= 10; }
 
 hipError_t launch_align_part_w(const AlignArgs &a, hipStream_t st) {
-    switch (a.log2N * 2 + a.dtype) {
-        case 14: launch_align_w_t<7, 0>(a, st); break;
-        case 15: launch_align_w_t<7, 1>(a, st); break;
-        case 16: launch_align_w_t<8, 0>(a, st); break;
-        case 17: launch_align_w_t<8, 1>(a, st); break;
-        case 18: launch_align_w_t<9, 0>(a, st); break;
-        case 19: launch_align_w_t<9, 1>(a, st); break;
-        case 20: launch_align_w_t<10, 0>(a, st); break;
-        case 21: launch_align_w_t<10, 1>(a, st); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_log2n_dt<7, 10>(a.log2N, a.dtype, [&](auto L2, auto DT) { launch_align_w_t<L2(), DT()>(a, st); });
 }
 
 hipError_t launch_btab(int N, double *Bt, hipStream_t st) {
@@ -2000,18 +1943,7 @@ static void launch_xg(const XmomArgs &a, bool full, hipStream_t st) {
 }
 
 hipError_t launch_xmom(const XmomArgs &a, bool full, hipStream_t st) {
-    switch (a.log2N * 2 + a.dtype) {
-        case 14: launch_xg<7, 0>(a, full, st); break;
-        case 15: launch_xg<7, 1>(a, full, st); break;
-        case 16: launch_xg<8, 0>(a, full, st); break;
-        case 17: launch_xg<8, 1>(a, full, st); break;
-        case 18: launch_xg<9, 0>(a, full, st); break;
-        case 19: launch_xg<9, 1>(a, full, st); break;
-        case 20: launch_xg<10, 0>(a, full, st); break;
-        case 21: launch_xg<10, 1>(a, full, st); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_log2n_dt<7, 10>(a.log2N, a.dtype, [&](auto L2, auto DT) { launch_xg<L2(), DT()>(a, full, st); });
 }
 
 hipError_t launch_model_pow(const double2 *Mft, int nchan, int nharm, int nmodel, double *out,

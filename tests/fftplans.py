@@ -88,8 +88,8 @@ def xspec_wm_supported(nbin):
 
 def xspec_path(nbin, nchan):
     """The spectrum pass of a fit at nbin whose transform length is not a
-    power of two: launch_xspec's case 0 (ppf_kernels.hip; cb = min(nchan,
-    32) of fit_layout, ppf_api.cpp) and the 512 / 1024 split of
+    power of two: launch_xspec's log2N == 0 arm (ppf_kernels.hip; cb =
+    min(nchan, 32) of fit_layout, ppf_api.cpp) and the 512 / 1024 split of
     launch_xspec_wm (ppf_xspec.hip): "wm512", "wm1024" (even nbin,
     k_xspec_wm), "wo512", "wo1024" (odd nbin, k_xspec_wo), k_xspec_any
     otherwise ("any-even", "any-odd")."""

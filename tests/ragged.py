@@ -81,9 +81,18 @@ CASES = (
      _case("blk", 512, 17, PDT, **_SC), _case("blk", 512, 31, PD),
      _case("blk", 4096, 45, PD), _case("blk", 128, 45, PD)] +
     # rows past the LDS transforms
-    [_case("long", 8194, 5, PD, guess=True)])
+    [_case("long", 8194, 5, PD, guess=True)] +
+    # 256 channels = 8 spectrum blocks of 32: the smallest count at which the
+    # XCD-aware block map (xcd_swizzle) turns on, one case per spectrum kernel
+    # that takes it, X consumed by the fit: k_xspec_w, k_xspec_wm (moments
+    # from X), k_xspec_wo, k_xspec, k_xspec_any
+    [_case("swz", 256, 256, PDTA, **_SC),
+     _case("swz", 100, 256, PD, mom_x=True),
+     _case("swz", 35, 256, PD), _case("swz", 64, 256, PD),
+     _case("swz", 2050, 256, PD)])
 
 CASE_NAMES = [c["name"] for c in CASES]
+SWIZZLED = [c["name"] for c in CASES if c["family"] == "swz"]
 
 # the cases whose four masks the host test fits twice each (well-posedness);
 # the others fit mask 1 only there

@@ -156,7 +156,9 @@ def test_block_last_masked():
 def test_degenerate_families():
     assert len(D.FAMILIES) == 12 and set(D.FAMILIES) <= set(R.CASE_NAMES)
     fam = [R.case(n)["family"] for n in D.FAMILIES]
-    assert set(fam) == {c["family"] for c in R.CASES}
+    # ("swz" has no kernel of its own: the other families' spectrum kernels
+    # at 256 channels, on the swizzled block map)
+    assert set(fam) == {c["family"] for c in R.CASES} - {"swz"}
     for n in D.SCIPY + D.ONLY + (D.NO_X,):
         assert n in R.CASE_NAMES
     c = R.case(D.NO_X)

@@ -35,8 +35,11 @@ def test_ragged_batch_matches_oracle(name):
     through k_dsum_w, the fused k_xmom_g, forced moments from X, k_xspec_w +
     k_pass, the k_pass warm start at strides 2 and 4 with a one-channel
     last group, the mixed-radix and odd-nbin wave passes (unpaired rows),
-    the block-FFT k_xspec (fewer than 32 channels; 4096 and 128 bins) and
-    rows past the LDS transforms."""
+    the block-FFT k_xspec (fewer than 32 channels; 4096 and 128 bins),
+    rows past the LDS transforms, and 256 channels (8 spectrum blocks: the
+    XCD-aware block map, mode 1) on k_xspec_w, k_xspec_wm, k_xspec_wo,
+    k_xspec and k_xspec_any.  (Mode 2 of the block map needs more than 32 MB
+    of model spectra: the full-shape scattering parity check covers it.)"""
     c = R.case(name)
     r = R.device_fit(c)
     for i in range(R.inputs(c)["nsub"]):
@@ -44,11 +47,12 @@ def test_ragged_batch_matches_oracle(name):
 
 
 @pytest.mark.parametrize("name", ["w2_guess-250x2048-pd-cut-f32",
-                                  "warm-257x256-pdta-cut-f32"])
+                                  "warm-257x256-pdta-cut-f32"] + R.SWIZZLED)
 def test_ragged_single_equals_batch(name):
     """Each sub-int fitted alone is bitwise the batch's (as
     test_batch_equals_single_and_is_deterministic at 64 channels), with a
-    ragged last block and differing masks."""
+    ragged last block and differing masks; the 256-channel cases: on the
+    swizzled block map, which a single sub-int takes as well."""
     c = R.case(name)
     full = R.device_fit(c)
     for i in range(R.inputs(c)["nsub"]):

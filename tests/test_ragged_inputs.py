@@ -20,6 +20,7 @@ EXPECTED = {
     "wo": {(1001, 33), (1001, 37)},
     "blk": {(512, 3), (512, 17), (512, 31), (4096, 45), (128, 45)},
     "long": {(8194, 5)},
+    "swz": {(256, 256), (100, 256), (35, 256), (64, 256), (2050, 256)},
 }
 
 
@@ -43,6 +44,11 @@ def test_case_table_is_complete():
                 c["nchan"] == n} == {R.PD, R.PDTA}
     for n in R.ALL_MASKS_ON_HOST:
         assert n in by
+    # the swizzled block map: 32-channel blocks, a multiple of 8 of them
+    assert len(R.SWIZZLED) == 5
+    for n in R.SWIZZLED:
+        assert by[n]["nchan"] % 32 == 0 and by[n]["nchan"] // 32 % 8 == 0
+    assert by["swz-256x100-pd-cut-f32"]["mom_x"] is True
     # estimated and given errors both occur
     given = [R.inputs(c)["errs"] is not None for c in R.CASES
              if c["nbin"] <= 512]
