@@ -545,6 +545,7 @@ struct FitCall {
     unsigned *kinds;
     int32_t *cls;
     double *rec;
+    int pf_skip;                 // solve(): the post-fit kernels with nothing to do (ppf::kPfSkip*)
 
     template <class U>
     U *at(size_t off) const { return (U *)(ws + off); }
@@ -895,13 +896,19 @@ int FitCall::solve(const ppf::SolveArgs &sa) {
         }
         if (*ctx->host_active == 0 || iter > maxiter + 2) break;
     }
+    // the post-fit kernels to launch: without a streaming fit every fitted
+    // sub-int is a moment fit (k_postfit_mom alone); without a moment fit,
+    // where the counts say so, k_postfit alone
+    pf_skip = !any_pass ? ppf::kPfSkipFull : (!any_mom ? ppf::kPfSkipMom : 0);
     return PPF_OK;
 }
 
 // stage 3's end: the output transform, covariances, scales and chi2
 int FitCall::postfit(const ppf::SolveArgs &sa) {
     EvPair *pe = solv_begin(2);
-    const hipError_t e = ppf::launch_postfit(sa, st);
+    ppf::SolveArgs pa = sa;
+    pa.pf_skip = pf_skip;
+    const hipError_t e = ppf::launch_postfit(pa, st);
     if (e != hipSuccess) return hip_fail(ctx, e, "k_postfit");
     solv_end(pe);
     return PPF_OK;

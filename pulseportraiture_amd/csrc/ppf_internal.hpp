@@ -193,7 +193,13 @@ struct SolveArgs {
     unsigned *rc_count;          // sub-ints k_tr_mom sent back for a new moment centre
     int32_t *rc_list;            // [nsub] their indices (slot order of the atomic)
     const double *rec;           // [nsub][kRecN] (k_classify): usable channels, mean frequency
+    // launch_postfit: the post-fit kernels the batch has no sub-int for
+    // (kPfSkip*, from k_tr_init's kind counts; 0: both run)
+    int pf_skip;
 };
+// k_postfit_mom takes the sub-ints without scattering and the unfitted ones,
+// k_postfit the scattering fits (and everything where k_postfit_mom is skipped)
+enum { kPfSkipMom = 1, kPfSkipFull = 2 };
 
 struct RotateArgs {
     int nbin, log2N, dtype;

@@ -16,6 +16,9 @@
 //   k_postfit                     one workgroup per sub-int: zero-covariance
 //                                 frequencies, output transform, Schur
 //                                 covariance, scales, channel S/N, chi2
+//   k_postfit_mom                 the same for the sub-ints without
+//                                 scattering: the (phi, DM, GM) block only,
+//                                 channel powers once per channel
 // Splitting the cold trust-region / post-fit code out of the streaming pass
 // keeps the pass at <= 128 VGPRs (>= 4 waves/SIMD) with every harmonic load
 // of a channel row in flight.
@@ -1712,6 +1715,92 @@ __device__ __noinline__ void nz_solve(const double *c, int nzcase, int option, d
     *no_root_out = no_root ? 1 : 0;
 }
 
+#ifdef PPF_PF_PROF
+// section cycle counters of k_postfit, thread 0 of each workgroup (profiling
+// builds only: tools/pfprof.py)
+__device__ unsigned long long g_pfprof[8];
+#define PF_INIT() unsigned long long pf_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long pf_t = __builtin_amdgcn_s_memtime()
+#define PF(i) do { const unsigned long long pf_n = __builtin_amdgcn_s_memtime(); pf_acc[i] += pf_n - pf_t; pf_t = pf_n; } while (0)
+#define PF_DONE() do { if (tid == 0) for (int ti = 0; ti < 8; ++ti) atomicAdd(&g_pfprof[ti], pf_acc[ti]); } while (0)
+#else
+#define PF_INIT()
+#define PF(i)
+#define PF_DONE()
+#endif
+// the record of a sub-int that was not fitted (PPF_ST_NOFIT, PPF_ST_NOSPACE)
+template <int PB>
+__device__ __forceinline__ void postfit_nofit(const SolveArgs &a, int s, const TRState &S) {
+    const int tid = threadIdx.x;
+    ppf_result *res = a.results + s;
+    if (tid == 0) {
+        for (int i = 0; i < 32; ++i) reinterpret_cast<double *>(res)[i] = 0.0;
+        res->status = S.status;
+        // a sub-int without a usable channel has no mean frequency (0 / 0)
+        // and k_guess's phase is NaN: the record then holds the caller's
+        // initial phase, so that every field of it is finite
+        const double pg = S.phi_guess;
+        res->phi_guess = fabs(pg) <= kDblMax ? pg : a.init[(int64_t)s * 5];
+    }
+    for (int n = tid; n < a.nchan; n += PB) {
+        const int64_t o2 = (int64_t)s * a.nchan + n;
+        a.scales[o2] = 0.0; a.scale_errs[o2] = 0.0; a.channel_snrs[o2] = 0.0;
+    }
+}
+
+// what thread 0 of k_postfit_mom hands to postfit_record
+struct PostfitOut {
+    double phi_out, tau_out, Sd, fun, dof, phi_guess, snr2;
+    double x[5], nu_out[3], nu_fit[3];
+    int status, nfev, k, nchanx, nf, idx[5];
+    bool no_root, sing;
+};
+
+// k_postfit_mom's result record and covariance block of a fitted sub-int
+// (thread 0); Xinv: the inverse at parameter positions, [5][5].  The same
+// fields, in the same order, as the record k_postfit writes at its end: a
+// change of ppf_result goes into both.
+__device__ __forceinline__ void postfit_record(const SolveArgs &a, int s, const TRState &S,
+                                               const PostfitOut &o, const double *Xinv) {
+    ppf_result *res = a.results + s;
+    double pe[5] = {0, 0, 0, 0, 0};
+    double *cov = a.covariance + (int64_t)s * 25;
+    for (int i2 = 0; i2 < 25; ++i2) cov[i2] = 0.0;
+    for (int i2 = 0; i2 < o.nf; ++i2) {
+        for (int j2 = 0; j2 < o.nf; ++j2) cov[i2 * 5 + j2] = 2.0 * Xinv[o.idx[i2] * 5 + o.idx[j2]];
+        pe[o.idx[i2]] = sqrt(2.0 * Xinv[o.idx[i2] * 5 + o.idx[i2]]);
+    }
+    double params[5] = {o.phi_out, o.x[1], o.x[2], o.tau_out, o.x[4]};
+    for (int i2 = 0; i2 < 5; ++i2) { res->params[i2] = params[i2]; res->param_errs[i2] = pe[i2]; }
+    for (int i2 = 0; i2 < 3; ++i2) { res->nu_out[i2] = o.nu_out[i2]; res->nu_fit[i2] = o.nu_fit[i2]; }
+    res->chi2 = o.Sd + o.fun;
+    res->red_chi2 = (o.Sd + o.fun) / o.dof;
+    res->snr = sqrt(o.snr2);
+    res->fun = o.fun;
+    res->Sd = o.Sd;
+    res->phi_guess = o.phi_guess;
+    res->nfeval = (double)o.nfev;
+    int st2 = o.status;
+    if (o.no_root) st2 |= PPF_ST_NO_ROOT;
+    if (o.sing) st2 |= PPF_ST_SINGULAR;
+    if (!(o.fun == o.fun)) st2 |= PPF_ST_NONFINITE;
+    res->status = (double)st2;
+    res->niter = (double)o.k;
+    res->dof = o.dof;
+    res->nchanx = (double)o.nchanx;
+    res->x_fit_phi = o.x[0];
+    res->x_fit_tau = o.x[3];
+    // passes over X: one per evaluation (k_pass) or one per moment
+    // (re)centre (k_moments); subset evaluations count their fraction of the
+    // channel groups
+    double npass = S.mmode ? (double)S.nmom + 1.0 : (double)o.nfev;
+    if (!S.mmode && S.nsubev > 0) {
+        const int ng = (a.nchan + 63) / 64, nsel = (ng + S.sub0 - 1) / S.sub0;
+        npass -= (double)S.nsubev * (1.0 - (double)nsel / (double)ng);
+    }
+    res->npass = npass;
+    res->reserved[0] = res->reserved[1] = 0.0;
+}
+
 // PB threads per sub-int.  64 (one wave) lets four sub-ints share a CU at
 // the kernel's one wave per SIMD, so the serial parts (the zero-covariance
 // root finding, the covariance inversion by thread 0) of four sub-ints
@@ -1726,21 +1815,12 @@ __global__ __launch_bounds__(PB) void k_postfit(SolveArgs a) {
     __shared__ double sh_acc[NZ_MAX + 8];
     const int s = blockIdx.x, tid = threadIdx.x;
     const TRState &S = a.state[s];
-    ppf_result *res = a.results + s;
-    if (S.status == PPF_ST_NOFIT || S.status == PPF_ST_NOSPACE) {
-        if (tid == 0) {
-            for (int i = 0; i < 32; ++i) reinterpret_cast<double *>(res)[i] = 0.0;
-            res->status = S.status;
-            // a sub-int without a usable channel has no mean frequency (0 / 0)
-            // and k_guess's phase is NaN: the record then holds the caller's
-            // initial phase, so that every field of it is finite
-            const double pg = S.phi_guess;
-            res->phi_guess = fabs(pg) <= kDblMax ? pg : a.init[(int64_t)s * 5];
-        }
-        for (int n = tid; n < a.nchan; n += PB) {
-            const int64_t o2 = (int64_t)s * a.nchan + n;
-            a.scales[o2] = 0.0; a.scale_errs[o2] = 0.0; a.channel_snrs[o2] = 0.0;
-        }
+    const bool unfit = S.status == PPF_ST_NOFIT || S.status == PPF_ST_NOSPACE;
+    // where k_postfit_mom runs too, the unfitted sub-ints and those without
+    // scattering are its share (uniform per workgroup)
+    if (!(a.pf_skip & kPfSkipMom) && (unfit || !S.scat)) return;
+    if (unfit) {
+        postfit_nofit<PB>(a, s, S);
         return;
     }
     struct { const double *fr; const uint8_t *mask; int nchan; } v;
@@ -1757,6 +1837,7 @@ __global__ __launch_bounds__(PB) void k_postfit(SolveArgs a) {
     const int status = S.status, nfev = S.nfev, k = S.k;
     const bool scat = S.scat != 0;
     const double nu_mean = S.nu_mean, dof = S.dof, phi_guess = S.phi_guess;
+    PF_INIT();
     // Sd = sum_n |D_n|^2 / sigma~_n^2 over the usable channels
     // (pptoaslib.py:1031), from the spectrum kernels' chan[]
     double sdv[1] = {0.0};
@@ -1798,6 +1879,7 @@ __global__ __launch_bounds__(PB) void k_postfit(SolveArgs a) {
         gg.g_alpha = sm[2] != 0.0;
     };
     gates(g, tau_fit_lin, x[4]);
+    PF(0);
 
     // ---- zero-covariance frequencies (pptoaslib.py:776-950) -------------------------
     double nu_out[3];
@@ -1890,6 +1972,7 @@ __global__ __launch_bounds__(PB) void k_postfit(SolveArgs a) {
             }
         }
         blk_sum<NZ_MAX + 8, PB>(accv, red);
+        PF(1);
         if (tid == 0) {
             for (int i = 0; i < NZ_MAX + 8; ++i) sh_acc[i] = accv[i];
             int nr_flag = 0;
@@ -1902,6 +1985,7 @@ __global__ __launch_bounds__(PB) void k_postfit(SolveArgs a) {
         nz[0] = sh_misc[4]; nz[1] = sh_misc[5]; nz[2] = sh_misc[6];
         no_root = sh_misc[7] != 0.0;
         __syncthreads();
+        PF(2);
     }
     if (need_nz)
         for (int i = 0; i < 3; ++i)
@@ -1953,6 +2037,7 @@ __global__ __launch_bounds__(PB) void k_postfit(SolveArgs a) {
             }
     }
     blk_sum<31, PB>(cv, red);
+    PF(3);
     int sing = 0;
     if (tid == 0) {
         double Xm[5][5], Xi[5][5];
@@ -1972,6 +2057,7 @@ __global__ __launch_bounds__(PB) void k_postfit(SolveArgs a) {
     }
     __syncthreads();
     sing = (int)sh_misc[8];
+    PF(4);
     double Xinv[5][5];
     for (int i2 = 0; i2 < 5; ++i2)
         for (int j2 = 0; j2 < 5; ++j2) Xinv[i2][j2] = sh_Xinv[i2 * 5 + j2];
@@ -2009,7 +2095,12 @@ __global__ __launch_bounds__(PB) void k_postfit(SolveArgs a) {
         sn[0] += csnr * csnr;
     }
     blk_sum<1, PB>(sn, red);
+    PF(5);
     if (tid == 0) {
+        // (written out here, not through postfit_record: with the helper
+        // this kernel measured 1.96 instead of 1.92 ms per 10,000 scattering
+        // sub-ints, profiles/r15/ab_status.txt)
+        ppf_result *res = a.results + s;
         double pe[5] = {0, 0, 0, 0, 0};
         double *cov = a.covariance + (int64_t)s * 25;
         for (int i2 = 0; i2 < 25; ++i2) cov[i2] = 0.0;
@@ -2038,10 +2129,9 @@ __global__ __launch_bounds__(PB) void k_postfit(SolveArgs a) {
         res->nchanx = (double)nchanx;
         res->x_fit_phi = x[0];
         res->x_fit_tau = x[3];
-        // full passes over X: one per evaluation (k_pass) or one per moment
-        // (re)centre (k_moments)
-        // passes over X: subset evaluations count their fraction of the
-        // channel groups
+        // passes over X: one per evaluation (k_pass) or one per moment
+        // (re)centre (k_moments); subset evaluations count their fraction of
+        // the channel groups
         double npass = S.mmode ? (double)S.nmom + 1.0 : (double)nfev;
         if (!S.mmode && S.nsubev > 0) {
             const int ng = (a.nchan + 63) / 64, nsel = (ng + S.sub0 - 1) / S.sub0;
@@ -2050,6 +2140,283 @@ __global__ __launch_bounds__(PB) void k_postfit(SolveArgs a) {
         res->npass = npass;
         res->reserved[0] = res->reserved[1] = 0.0;
     }
+    PF(6);
+    PF_DONE();
+}
+
+// ---------------------------------------------------------------------------
+// k_postfit_mom: k_postfit for the sub-ints without scattering (!S.scat: only
+// phi / DM / GM fitted, tau = 0), every sub-int of a moment fit.  Their stats
+// hold C, C', C'' and S alone (k_tr_mom stores zeros in the scattering
+// slots), every t and u of make_fac is zero, and so is every product
+// chan_derivs / chan_hess form with them: those exact zeros are left out, the
+// 3 x 3 (phi, DM, GM) block is what remains.  A surviving expression is
+// written as k_postfit writes it, so that it contracts into the same fused
+// operations and the records agree bit for bit.
+// ---------------------------------------------------------------------------
+// nu^-2 and nu^-4 of a channel, each only where asked for (0 otherwise: the
+// flag-mask guards keep it from every result).  Out of line: one copy of the
+// pow code for the table fill and for the sub-ints too wide for the table.
+__device__ __noinline__ double2 pf_powers(double nu, bool want2, bool want4) {
+    double2 w;
+    w.x = want2 ? pow(nu, -2.0) : 0.0;
+    w.y = want4 ? pow(nu, -4.0) : 0.0;
+    return w;
+}
+
+// entry (i, j) of chan_hess's H_n without its scattering terms: with
+// dS = d2S = 0 three of its five terms are exact zeros, and the compiler
+// contracts the other two as written here (the second product fused onto
+// the rounded first)
+__device__ __forceinline__ double mom_hess(double C, double iS, double d2c, double dci, double dcj) {
+    return -2.0 * fma(dci * dcj, iS, C * d2c * iS);
+}
+
+// the covariance inversion of thread 0, out of line: its pivoting locals
+// stay out of the per-channel loops' registers
+__device__ __noinline__ bool pf_invert(double (*Xm)[5], double (*Xi)[5], int nf) {
+    return invert_small(Xm, Xi, nf);
+}
+
+template <int PB>
+__global__ __launch_bounds__(PB) void k_postfit_mom(SolveArgs a) {
+    // the one-wave form serves up to 2048 channels (launch_postfit) and
+    // tabulates nu^-2 | nu^-4 per channel, [2][nchan]; a lane reads back only
+    // what it wrote (every loop below walks n = tid, tid + PB, ...).  The
+    // wide form recomputes them in every loop.
+    constexpr bool tab = PB == 64;
+    extern __shared__ double sh_pw[];
+    __shared__ double red[kWaves * 12];
+    __shared__ double sh_Xinv[25];
+    __shared__ double sh_misc[16];
+    __shared__ double sh_acc[8];             // nz_solve reads c[0..7] in cases 0x3, 0x5, 0x7
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const TRState &S = a.state[s];
+    const bool unfit = S.status == PPF_ST_NOFIT || S.status == PPF_ST_NOSPACE;
+    if (!unfit && S.scat) return;            // k_postfit's share (uniform per workgroup)
+    if (unfit) {
+        postfit_nofit<PB>(a, s, S);
+        return;
+    }
+    const int nchan = a.nchan;
+    const double *fr = a.freqs + (int64_t)s * nchan;
+    const uint8_t *mask = a.mask ? a.mask + (int64_t)s * nchan : nullptr;
+    const int flagmask = S.flagmask & 0x7;
+    int idx[5] = {0, 0, 0, 0, 0}, nf = 0;
+    for (int i = 0; i < 3; ++i)
+        if (flagmask >> i & 1) idx[nf++] = i;
+    double x[5];
+    for (int i = 0; i < 5; ++i) x[i] = S.x[i];
+    const double fun = S.f;
+    const int status = S.status, nfev = S.nfev, k = S.k;
+    const double nu_mean = S.nu_mean, dof = S.dof, phi_guess = S.phi_guess;
+    PF_INIT();
+    // Sd = sum_n |D_n|^2 / sigma~_n^2 over the usable channels
+    double sdv[1] = {0.0};
+    {
+        const double *chan = a.chan + (int64_t)s * nchan * 4;
+        for (int n = tid; n < nchan; n += PB)
+            if (!mask || mask[n]) sdv[0] += chan[n * 4 + 2];
+    }
+    blk_sum<1, PB>(sdv, red);
+    const double Sd = sdv[0];
+    const int nchanx = S.nchanx;
+    const double P = a.P[s];
+    const double nu_fit[3] = {S.nu_fit[0], S.nu_fit[1], S.nu_fit[2]};
+    const double *st_fit = a.stats + ((int64_t)s * 2 + S.slot_cur) * nchan * 10;
+    const double tau_fit_lin = a.log10_tau ? pow(10.0, x[3]) : x[3];
+
+    double nu_out[3];
+    bool need_nz = false;
+    for (int i = 0; i < 3; ++i) {
+        nu_out[i] = a.nu_outs[(int64_t)s * 3 + i];
+        if (!(nu_out[i] == nu_out[i]) || nu_out[i] == 0.0) need_nz = true;
+    }
+    int nzcase = flagmask;
+    if (a.mode == PPF_MODE_LEGACY2) nzcase = 0x3;
+    const bool closed = nzcase == 0x3 || nzcase == 0x5 || nzcase == 0x7;
+    const bool nz_run = need_nz && closed;
+    // the channel powers some fitted parameter or the zero-covariance case reads
+    const bool want2 = (flagmask & 2) || (nz_run && nzcase == 0x3);
+    const bool want4 = (flagmask & 4) != 0;
+    if constexpr (tab)
+        for (int n = tid; n < nchan; n += PB) {
+            if (mask && !mask[n]) continue;
+            const double2 w = pf_powers(fr[n], want2, want4);
+            sh_pw[n] = w.x;
+            sh_pw[nchan + n] = w.y;
+        }
+    auto powers = [&](int n) {
+        if constexpr (tab) return make_double2(sh_pw[n], sh_pw[nchan + n]);
+        else return pf_powers(fr[n], want2, want4);
+    };
+    PF(0);
+
+    // ---- zero-covariance frequencies: the cases a (phi, DM, GM) mask reaches
+    double nz[3] = {nu_fit[0], nu_fit[1], nu_fit[2]};
+    bool no_root = false;
+    if (nz_run) {
+        double accv[8];
+        for (int i = 0; i < 8; ++i) accv[i] = 0.0;
+        const double rDM = pow(nu_fit[0], -2.0), rGM = pow(nu_fit[1], -4.0);
+        for (int n = tid; n < nchan; n += PB) {
+            if (mask && !mask[n]) continue;
+            const double *st = st_fit + (int64_t)n * 10;
+            const double C = st[0], Cp = st[1], Cpp = st[2], iS = 1.0 / st[6];
+            const double2 w = powers(n);
+            const double w2 = w.x, w4 = w.y;
+            // Hd[1][0] = Hg[2][0] = Hd[1][1] = Hg[2][2] of k_postfit
+            const double h0 = mom_hess(C, iS, Cpp, Cp, Cp);
+            double *c = accv;
+            switch (nzcase) {
+                case 0x3: c[0] += w2 * h0; c[1] += h0; break;
+                case 0x5: c[0] += w4 * h0; c[1] += h0; break;
+                case 0x7:
+                    if (a.option == 0) {
+                        const double dphi2 = kDconst * kDconst * (w4 - rGM) / P;
+                        const double rd2 = mom_hess(C, iS, Cpp * dphi2, Cp, Cp * dphi2);
+                        const double rg2 = h0 * dphi2;
+                        c[0] += w4 * h0; c[1] += h0; c[2] += w2 * rd2; c[3] += rd2;
+                        c[4] += w4 * rg2; c[5] += rg2; c[6] += w2 * h0; c[7] += h0;
+                    } else {
+                        const double dphi1 = kDconst * (w2 - rDM) / P;
+                        const double rg1 = mom_hess(C, iS, Cpp * dphi1, Cp, Cp * dphi1);
+                        const double rd1 = h0 * dphi1;
+                        c[0] += w4 * h0; c[1] += h0; c[2] += w2 * rg1; c[3] += rg1;
+                        c[4] += w4 * rd1; c[5] += rd1; c[6] += w2 * h0; c[7] += h0;
+                    }
+                    break;
+                default: break;
+            }
+        }
+        blk_sum<8, PB>(accv, red);
+        PF(1);
+        if (tid == 0) {
+            for (int i = 0; i < 8; ++i) sh_acc[i] = accv[i];
+            int nr_flag = 0;
+            nz_solve(sh_acc, nzcase, a.option, nu_mean, nz, &nr_flag);
+            sh_misc[4] = nz[0]; sh_misc[5] = nz[1]; sh_misc[6] = nz[2];
+            sh_misc[7] = nr_flag ? 1.0 : 0.0;
+        }
+        __syncthreads();
+        nz[0] = sh_misc[4]; nz[1] = sh_misc[5]; nz[2] = sh_misc[6];
+        no_root = sh_misc[7] != 0.0;
+        __syncthreads();
+        PF(2);
+    }
+    if (need_nz)
+        for (int i = 0; i < 3; ++i)
+            if (!(nu_out[i] == nu_out[i]) || nu_out[i] == 0.0) nu_out[i] = nz[i];
+    if (a.mode == PPF_MODE_LEGACY2) { nu_out[1] = nu_out[0]; nu_out[2] = nu_fit[2]; }
+    if (a.is_toa) {
+        if (flagmask & 2) nu_out[1] = nu_out[0];
+        else if (flagmask & 4) nu_out[0] = nu_out[1];
+    }
+
+    // ---- output transform (pptoaslib.py:1100-1114) -----------------------------------
+    double phi_inf = x[0] + kDconst * x[1] * (0.0 - pow(nu_fit[0], -2.0)) / P +
+                     kDconst * kDconst * x[2] * (0.0 - pow(nu_fit[1], -4.0)) / P;
+    double phi_out = phi_inf + (kDconst / P) * x[1] * pow(nu_out[0], -2.0) +
+                     (kDconst * kDconst / P) * x[2] * pow(nu_out[1], -4.0);
+    if (fabs(phi_out) >= 0.5) phi_out = phi_out - floor(phi_out);
+    if (phi_out >= 0.5) phi_out -= 1.0;
+    double tau_out_lin = tau_fit_lin * pow(nu_out[2] / nu_fit[2], x[4]);
+    double tau_out = a.log10_tau ? log10(tau_out_lin) : tau_out_lin;
+
+    // ---- covariance at the output reference frequencies: the (phi, DM, GM)
+    //      block of k_postfit's sums, upper triangle in its order
+    const double oDM = pow(nu_out[0], -2.0), oGM = pow(nu_out[1], -4.0);
+    double cv[12];
+    for (int i = 0; i < 12; ++i) cv[i] = 0.0;
+    for (int n = tid; n < nchan; n += PB) {
+        if (mask && !mask[n]) continue;
+        const double *st = st_fit + (int64_t)n * 10;
+        const double C = st[0], Cp = st[1], Cpp = st[2], S6 = st[6];
+        const double2 w = powers(n);
+        const double dphi[3] = {1.0, kDconst * (w.x - oDM) / P, kDconst * kDconst * (w.y - oGM) / P};
+        double U[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) U[i] = (flagmask >> i & 1) ? -2.0 * (Cp * dphi[i]) : 0.0;
+        const double cinv = 1.0 / (2.0 * S6);
+        int q = 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = i; j < 3; ++j) {
+                if ((flagmask >> i & 1) && (flagmask >> j & 1)) {
+                    cv[q] += -2.0 * (C * (Cpp * dphi[i] * dphi[j]) / S6);
+                    cv[6 + q] += U[i] * U[j] * cinv;
+                }
+                ++q;
+            }
+    }
+    blk_sum<12, PB>(cv, red);
+    PF(3);
+    int sing = 0;
+    if (tid == 0) {
+        double Xm[5][5], Xi[5][5];
+        double full[3][3];
+        int q = 0;
+        for (int i = 0; i < 3; ++i)
+            for (int j = i; j < 3; ++j) { full[i][j] = full[j][i] = cv[q] - cv[6 + q]; ++q; }
+        for (int i2 = 0; i2 < nf; ++i2)
+            for (int j2 = 0; j2 < nf; ++j2) Xm[i2][j2] = full[idx[i2]][idx[j2]];
+        if (!pf_invert(Xm, Xi, nf)) sing = 1;
+        for (int i2 = 0; i2 < 25; ++i2) sh_Xinv[i2] = 0.0;
+        for (int i2 = 0; i2 < nf; ++i2)
+            for (int j2 = 0; j2 < nf; ++j2) sh_Xinv[idx[i2] * 5 + idx[j2]] = Xi[i2][j2];
+        sh_misc[8] = (double)sing;
+    }
+    __syncthreads();
+    sing = (int)sh_misc[8];
+    PF(4);
+    double Xinv[3][3];
+    for (int i2 = 0; i2 < 3; ++i2)
+        for (int j2 = 0; j2 < 3; ++j2) Xinv[i2][j2] = sh_Xinv[i2 * 5 + j2];
+    // per-channel scales, scale errors, channel S/N
+    double sn[1] = {0.0};
+    for (int n = tid; n < nchan; n += PB) {
+        const int64_t o2 = (int64_t)s * nchan + n;
+        if (mask && !mask[n]) {
+            a.scales[o2] = 0.0; a.scale_errs[o2] = 0.0; a.channel_snrs[o2] = 0.0;
+            continue;
+        }
+        const double *st = st_fit + (int64_t)n * 10;
+        const double C = st[0], Cp = st[1], S6 = st[6], an = C / S6;
+        const double2 w = powers(n);
+        const double dphi[3] = {1.0, kDconst * (w.x - oDM) / P, kDconst * kDconst * (w.y - oGM) / P};
+        double U[3];
+#pragma unroll
+        for (int i2 = 0; i2 < 3; ++i2) U[i2] = (flagmask >> i2 & 1) ? -2.0 * (Cp * dphi[i2]) : 0.0;
+        double quad = 0.0;
+#pragma unroll
+        for (int i2 = 0; i2 < 3; ++i2)
+#pragma unroll
+            for (int j2 = 0; j2 < 3; ++j2)
+                if ((flagmask >> i2 & 1) && (flagmask >> j2 & 1)) quad += U[i2] * Xinv[i2][j2] * U[j2];
+        const double cinv = 1.0 / (2.0 * S6);
+        double var = 2.0 * (cinv + quad * cinv * cinv);
+        double serr = (a.mode == PPF_MODE_LEGACY2) ? pow(S6, -0.5) : sqrt(var);
+        double csnr = an * sqrt(S6);
+        a.scales[o2] = an;
+        a.scale_errs[o2] = serr;
+        a.channel_snrs[o2] = csnr;
+        sn[0] += csnr * csnr;
+    }
+    blk_sum<1, PB>(sn, red);
+    PF(5);
+    if (tid == 0) {
+        PostfitOut o;
+        o.phi_out = phi_out; o.tau_out = tau_out; o.Sd = Sd; o.fun = fun; o.dof = dof;
+        o.phi_guess = phi_guess; o.snr2 = sn[0];
+        for (int i = 0; i < 5; ++i) { o.x[i] = x[i]; o.idx[i] = idx[i]; }
+        for (int i = 0; i < 3; ++i) { o.nu_out[i] = nu_out[i]; o.nu_fit[i] = nu_fit[i]; }
+        o.status = status; o.nfev = nfev; o.k = k; o.nchanx = nchanx; o.nf = nf;
+        o.no_root = no_root; o.sing = sing != 0;
+        postfit_record(a, s, S, o, sh_Xinv);
+    }
+    PF(6);
+    PF_DONE();
 }
 
 // ===========================================================================
@@ -2130,6 +2497,20 @@ hipError_t launch_tr_mom(const SolveArgs &a, hipStream_t st) {
 
 hipError_t launch_postfit(const SolveArgs &a, hipStream_t st) {
     const int pb = a.nchan <= 2048 ? 64 : 256;
+    // sub-ints without scattering: k_postfit_mom, its channel powers in an
+    // LDS table in the one-wave form (128 threads measured slower for it
+    // too: C2 0.382-0.383 vs 0.330-0.334 ms per launch,
+    // profiles/r15/ab_status.txt)
+    if (!(a.pf_skip & kPfSkipMom)) {
+        if (pb == 64)
+            hipLaunchKernelGGL(k_postfit_mom<64>, dim3((unsigned)a.nsub), dim3(64),
+                               (size_t)a.nchan * 2 * sizeof(double), st, a);
+        else
+            hipLaunchKernelGGL(k_postfit_mom<256>, dim3((unsigned)a.nsub), dim3(256), 0, st, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    if (a.pf_skip & kPfSkipFull) return hipSuccess;
     // (128 threads measured slower in round 5: C2 285.3-286.5k vs 287.6-288.2k, C3
     // 145.0-146.5k vs 147.7-148.1k, profiles/r05/ab_pf1_status.txt)
     if (pb == 64) hipLaunchKernelGGL(k_postfit<64>, dim3((unsigned)a.nsub), dim3(64), 0, st, a);
@@ -2141,6 +2522,18 @@ size_t tr_state_bytes() { return sizeof(TRState); }
 int pass_blocks(int nchan) { return (nchan + kPassChans - 1) / kPassChans; }
 
 }  // namespace ppf
+
+#ifdef PPF_PF_PROF
+extern "C" int ppf_debug_pfprof(unsigned long long *out, int reset) {
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ppf::g_pfprof), sizeof(unsigned long long) * 8) != hipSuccess)
+        return -1;
+    if (reset) {
+        unsigned long long z[8] = {};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(ppf::g_pfprof), z, sizeof(z)) != hipSuccess) return -1;
+    }
+    return 0;
+}
+#endif
 
 #ifdef PPF_TM_PROF
 extern "C" int ppf_debug_tprof(unsigned long long *out, int reset) {
