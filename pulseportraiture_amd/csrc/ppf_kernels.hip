@@ -1349,7 +1349,11 @@ __global__ __launch_bounds__(kBlock) void k_align_phases(int nsub, int nchan, co
     const double DM = r[offsetof(ppf_result, params) / sizeof(double) + 1];
     const double nu_ref = r[offsetof(ppf_result, nu_out) / sizeof(double)];
     const bool ok = !mask || mask[i];
-    phases[i] = ok ? phi + kDconst * DM / P[s] * (pow(freqs[i], -2.0) - pow(nu_ref, -2.0)) : 0.0;
+    // nu^-2 as 1 / (nu nu), two correctly rounded operations: the device's
+    // pow(nu, -2.0) was several ulp off, more than the rest of the formula
+    // together (tests/test_gpu_align_groups.py)
+    const double f = freqs[i], f2 = 1.0 / (f * f), r2 = 1.0 / (nu_ref * nu_ref);
+    phases[i] = ok ? phi + kDconst * DM / P[s] * (f2 - r2) : 0.0;
     weights[i] = ok ? scales[i] / (errs[i] * errs[i]) : 0.0;
 }
 

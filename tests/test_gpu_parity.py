@@ -680,7 +680,8 @@ def test_align_accum_matches_numpy(nbin, nchan):
     """ppf_align_accum: sum_s w rotate(x_s, phi_s) per channel (frequency-
     domain accumulation) equals the time-domain rotate-then-sum of the
     oracle to rounding (odd nbin: the unpaired harmonic partials; 37 and
-    100 channels: a partial last channel tile)."""
+    100 channels: a partial last channel tile).  These shapes keep one row
+    per wave of k_align_part_w; several: tests/test_gpu_align_groups.py."""
     import torch
     import oracle as O
     from pulseportraiture_amd import engine
